@@ -9,12 +9,16 @@ loss, bf16, per-parameter clip + AdamW + teacher EMA, DP over RCCL when --gpus >
 
 Prints ONE JSON line on rank 0.  A "step" = teacher fwd (2 global crops) + student fwd (10 crops) + DDINOLoss + backward +
 gradient all-reduce (N>1) + fused clip/AdamW/EMA on a fixed synthetic batch resident in HBM.  `value` = images/s over all
-ranks; the timed region carries no instrumentation.  `roofline` describes the dominant kernel family (the MFMA GEMM: 99% of
+ranks; the timed region carries no instrumentation.  A plain run sets up, warms up, times --steps steps and prints the line;
+--full adds the `roofline` and `cpu_baseline` legs below (each can still be left out with --no-roofline / --no-cpu-baseline).
+--dump-outputs DIR writes what the last timed step computed (loss, DINO centres, a fixed seeded sample of the updated student
+and teacher parameters) as DIR/<name>.npy; the inputs are seeded, so two builds run with the same arguments can be compared
+output for output.  `roofline` describes the dominant kernel family (the MFMA GEMM: 99% of
 the step's FLOPs; SURVEY.md 8d bounds it by the bf16 MFMA peak) from HIP events recorded around every GEMM launch of a few
 extra steps AFTER the timed region (those steps run on ONE stream -- the teacher pass and the weight-gradient GEMMs, which the timed steps
 overlap on side streams, are back in line -- so that a launch's duration is its own); `cpu_baseline` times the reference's PyTorch path on the host cores on a bounded sample
-of the same workload -- the reference's own modules when /root/reference is present (kind "reference"), otherwise the
-oracle's restatement of them (kind "port").
+of the same workload -- the reference's own modules when its source tree is present (kind "reference", oracle/ref_loader.py),
+otherwise the oracle's restatement of them (kind "port").
 """
 import argparse
 import json
@@ -260,6 +264,43 @@ def _reference_baseline(dense, bs, steps):
     return times[len(times) // 2]
 
 
+DUMP_PER_TENSOR = 1 << 15     # --dump-outputs: at most this many entries of each parameter tensor (a seeded sample of larger ones)
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(path, loss, student, teacher, loss_fn, seed=0):
+    """What a caller of the timed step receives after its last call: the loss it returned and the state it updated in place (the
+    DINO centres of the loss, the student and teacher parameters).  Parameters are concatenated in named_parameters() order, a
+    tensor of more than DUMP_PER_TENSOR entries represented by the entries at DUMP_PER_TENSOR indices drawn from a generator seeded
+    with `seed` (the same indices for student and teacher, and for any build with the same parameter shapes)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    g = torch.Generator().manual_seed(seed)
+    index = {}
+    for n, p in student.named_parameters():
+        if p.numel() > DUMP_PER_TENSOR:
+            index[n] = torch.randint(p.numel(), (DUMP_PER_TENSOR,), generator=g)
+
+    def sample(module):
+        parts = []
+        for n, p in module.named_parameters():
+            flat = p.detach().reshape(-1)
+            if n in index:
+                flat = flat[index[n].to(flat.device)]
+            parts.append(flat.float().cpu())
+        return torch.cat(parts).numpy()
+    arrays = {"loss": np.array([loss.item()], dtype=np.float64),
+              "student_params_sample": sample(student), "teacher_params_sample": sample(teacher)}
+    for n, b in loss_fn.named_buffers():  # center, center_grid (DDINOLoss)
+        arrays["loss_" + n.replace(".", "_")] = b.detach().float().cpu().numpy()
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        raise SystemExit("bench.py: --dump-outputs would write %.1f MB (limit %d MB)" % (total / 2 ** 20, DUMP_MAX_BYTES >> 20))
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+    return sorted(arrays)
+
+
 def cpu_baseline():
     """both CPU legs SURVEY.md 8(d) asks for, bounded to ~10-30 s each: BASELINE config 2's CPU twin (2x224 + 8x96 crops, V+R,
     bs 2) as the main entry, BASELINE config 1 (2x224 crops, view-level loss, bs 4) under `config1`"""
@@ -339,18 +380,23 @@ def main():
     ap.add_argument("--drop-path", type=float, default=0.1)
     ap.add_argument("--arch", default="swin_tiny_w7", choices=["swin_tiny_w7", "swin_tiny_w14", "swin_base_w14", "swin_small_w7", "swin_base_w7", "cvt_s1", "deit_tiny", "deit_small", "vit_base", "vil_tiny", "vil_small"],
                     help="BASELINE.json's metric is quoted on swin_tiny_w7 (default); configs 3/4 are swin_tiny_w14 / swin_base_w14")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
+    ap.add_argument("--full", action="store_true", help="also run the legs beyond the headline figure: the GEMM roofline (extra "
+                    "instrumented steps after the timed ones) and the CPU baseline")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="write what the last timed step computed as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out the CPU baseline")
+    ap.add_argument("--no-roofline", action="store_true", help="with --full: leave out the roofline leg")
     ap.add_argument("--single-stream", action="store_true", help="teacher forward and weight-gradient GEMMs on the main stream too (per-kernel profiles: no overlapped durations)")
     ap.add_argument("--augment", action="store_true", help="produce the crops INSIDE the timed step with the GPU crop producer (esvit_amd.data: "
                     "DataAugmentationDINO on decoded uint8 images resident in HBM) instead of feeding fixed crop tensors")
     ap.add_argument("--grad-payload", default="fp32", choices=["fp32", "bf16"], help="wire format of the data-parallel gradient all-reduce "
                     "(bf16: half the bytes per xGMI link; moments and parameters stay fp32)")
     ap.add_argument("--per-group", action="store_true", help="one backbone pass per resolution group (the reference's schedule) instead of the ragged multi-crop route")
-    ap.add_argument("--gemm-table", default=None, help="write a per-shape GEMM time table to this file")
+    ap.add_argument("--gemm-table", default=None, help="with --full: write a per-shape GEMM time table of the roofline leg to this file")
     ap.add_argument("--torch-eager", type=int, default=0, metavar="BATCH",
                     help="also time the reference-path port under torch eager + autocast(bf16) on this GPU at the given batch")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # plain `python bench.py --gpus N`: become N ranks (one process per GPU) under torch.distributed.run
@@ -440,11 +486,13 @@ def main():
         losses.append(loss)  # (device scalars: read after the timed region)
     sync()
     dt = time.perf_counter() - t0
-    # roofline leg, OUTSIDE the timed region: HIP events around every GEMM launch of PROF_STEPS extra steps (two event records
-    # per launch cost ~2.7 us of stream time each, ~1.3 ms per instrumented step)
+    if args.dump_outputs and rank == 0:  # (before the extra steps of --full move the state on)
+        dump_outputs(args.dump_outputs, loss, student, teacher, loss_fn)
+    # roofline leg (--full), OUTSIDE the timed region: HIP events around every GEMM launch of PROF_STEPS extra steps (two event
+    # records per launch cost ~2.7 us of stream time each, ~1.3 ms per instrumented step)
     PROF_STEPS = 4
     prof, prof_steps = None, 0
-    if not args.no_roofline:
+    if args.full and not args.no_roofline:
         ops._EVENT_POOL.extend(torch.cuda.Event(enable_timing=True) for _ in range(2400 * PROF_STEPS))
         prof = []
         ops.GEMM_PROFILE = prof
@@ -516,7 +564,7 @@ def main():
                                "avg_launch_us": tot_ms * 1e3 / len(prof), "gemm_ms_per_step": tot_ms / prof_steps,
                                "flop_per_byte": tot_fl / tot_by, "mfma_busy": pmc_mfma_busy(args.arch, B),
                                "hbm_view": {"achieved": gbs, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": gbs / HBM_PEAK_GBS}}
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline()
         if args.torch_eager and world == 1:
             del trainer, student, teacher, loss_fn, crops

@@ -421,7 +421,7 @@ __global__ __launch_bounds__(FWD3_WAVES * 64, sizeof(T) == 2 ? (HD == 32 ? 4 : 2
 //   * the relative-position-bias gradient stays in accumulator registers across the windows a wave visits (fragment
 //     layout, reduced over `parts` afterwards).  Reducing it into its (2ws-1)^2-entry table in LDS with ds_add_f32 instead
 //     (112 LDS atomics per wave and window) was tried and measured 3x slower -- the LDS atomic unit saturates
-//     (profiles/r01_kernel_stats_w14_lds_atomic_dq.csv) -- and a 32-query strip per wave needs > 256 registers with those
+//     (profiles/r01_kernel_stats_w14_dq_ldsadd.csv) -- and a 32-query strip per wave needs > 256 registers with those
 //     accumulators, hence dq4 below: eight waves, one 16-query tile each.
 // -------------------------------------------------------------------------------------------------------------
 

@@ -749,6 +749,68 @@ def gen_patch_norm(ns):
     print("patch_norm.pt:", {k: tuple(v["y"].shape) for k, v in out.items()})
 
 
+
+def _level1_case(ns, arch):
+    """the reference's own modules behind its UNMODIFIED train_one_epoch (main_esvit.py:499-600, AdamW over utils.get_params_groups,
+    the no-op scaler branch, DDP, clip 3.0, freeze_last_layer 1, epoch 1 of two iterations), then the checkpoint dict of
+    main_esvit.py:476-488 written by utils.save_on_master and read back: what tests/test_integration_cpu.py compares our modules with"""
+    import argparse
+    import tempfile
+    from torch.nn.parallel import DistributedDataParallel as DDP
+    from tests.test_integration_cpu import Loader, NoOpScaler
+    RL.ensure_single_process_group()
+    train_one_epoch = RL.load_train_one_epoch()
+    K = GU.NANO_HEAD["out_dim"]
+    if arch == "swin":
+        build, ncrops = build_nano, 10
+        batches = [GU.make_crops(2, seed=70 + i) for i in range(2)]
+    else:
+        build, ncrops = build_nano_vit, 5
+        batches = [GU.make_crops(2, n_local=3, sizes=GU.NANO_VIT["sizes"], seed=80 + i) for i in range(2)]
+    student, teacher = build(ns), build(ns, teacher=True)
+    GU.fill_state_dict(student.state_dict(), 0)
+    GU.fill_state_dict(teacher.state_dict(), 7)
+    student.head.last_layer.weight_g.data.fill_(1)
+    for p in teacher.parameters():
+        p.requires_grad = False
+    init_s = {n: p.detach().clone() for n, p in student.named_parameters()}
+    init_t = {n: p.detach().clone() for n, p in teacher.named_parameters()}
+    loss_fn = ns.DDINOLoss(K, ncrops, 0.04, 0.07, 5, 10)
+    ddp = DDP(student)
+    opt = torch.optim.AdamW(ns.utils.get_params_groups(ddp))
+    sch = GU.LEVEL1_SCHED
+    n = len(batches)
+    saved = (torch.Tensor.cuda, torch.cuda.synchronize, ns.utils.is_dist_avail_and_initialized)
+    torch.Tensor.cuda = lambda self, *a, **k: self  # main_esvit.py:513 on a CPU-only box
+    torch.cuda.synchronize = lambda *a, **k: None
+    ns.utils.is_dist_avail_and_initialized = lambda: False  # (the metric logger's all-reduce goes through a cuda tensor)
+    try:
+        with tempfile.TemporaryDirectory() as tmp:
+            args = argparse.Namespace(epochs=2, clip_grad=3.0, freeze_last_layer=1, batch_size_per_gpu=2, output_dir=tmp)
+            stats = train_one_epoch(ddp, teacher, teacher, loss_fn, Loader(batches), opt, [9.0] * n + sch["lr"], [9.0] * n + sch["wd"],
+                                    [0.0] * n + sch["mom"], 1, None, NoOpScaler(), args)
+            path = os.path.join(tmp, "ref.pth")
+            ns.utils.save_on_master({"student": ddp.state_dict(), "teacher": teacher.state_dict(), "optimizer": opt.state_dict(), "epoch": 2,
+                                     "args": args, "dino_loss": loss_fn.state_dict(), "fp16_scaler": {}}, path)
+            ckpt = torch.load(path, weights_only=False)
+    finally:
+        torch.Tensor.cuda, torch.cuda.synchronize, ns.utils.is_dist_avail_and_initialized = saved
+    del ckpt["args"]
+    sd = opt.state_dict()
+    k0 = sorted(sd["state"])[0]
+    return {"stats": stats, "names": [n for n, _ in student.named_parameters()],
+            "student": GU.level1_updates(student, init_s), "teacher": GU.level1_updates(teacher, init_t),
+            "center": loss_fn.center.clone(), "center_grid": loss_fn.center_grid.clone(),
+            "opt_groups": [g["params"] for g in sd["param_groups"]], "opt_state_keys": sorted(sd["state"]),
+            "exp_avg0": (k0, sd["state"][k0]["exp_avg"].clone()), "ckpt_layout": GU.layout(ckpt)}
+
+
+def gen_level1(ns):
+    out = {arch: _level1_case(ns, arch) for arch in ("swin", "vit")}
+    torch.save(out, os.path.join(OUT, "level1.pt"))
+    print("level1.pt:", {a: round(c["stats"]["loss"], 5) for a, c in out.items()})
+
+
 def main():
     os.makedirs(OUT, exist_ok=True)
     ns = RL.load()
@@ -781,6 +843,8 @@ def main():
         gen_mixup_smoothing(ns)
     if not only or "ref_checkpoint" in only:
         gen_ref_checkpoint(ns)
+    if not only or "level1" in only:
+        gen_level1(ns)
     if "full" in only:  # minutes of CPU time: regenerated on request only
         gen_full(ns)
     if "full_vit" in only:

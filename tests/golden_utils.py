@@ -282,3 +282,56 @@ def head_nlayers_inputs():
     g = torch.Generator().manual_seed(515)
     c = HEAD_NLAYERS
     return torch.randn(c["rows"], c["in_dim"], generator=g), torch.randn(c["rows"], c["out_dim"], generator=g)
+
+
+# ---- integration level 1 (main_esvit.train_one_epoch) fixture: tests/golden/level1.pt -----------------------------------------------
+LEVEL1_SAMPLE = 1024  # entries kept per parameter update (a seeded, name-keyed sample of larger tensors)
+LEVEL1_SCHED = dict(lr=[3e-4, 2e-4], wd=[0.04, 0.05], mom=[0.99, 0.995])  # the two iterations of epoch 1 (freeze_last_layer = 1)
+
+
+def level1_index(name, numel, k=LEVEL1_SAMPLE):
+    """the entries of parameter `name` the fixture keeps: all of a small tensor, else k sorted indices drawn from a generator
+    seeded with the name (the generator and the tests draw the same ones)"""
+    if numel <= k:
+        return None
+    g = torch.Generator().manual_seed(zlib.crc32(name.encode()))
+    return torch.randperm(numel, generator=g)[:k].sort().values
+
+
+def level1_updates(module, init):
+    """{name: (final - initial) at level1_index(name)} of every parameter of `module`"""
+    out = {}
+    for n, p in module.named_parameters():
+        d = (p.detach() - init[n].detach()).reshape(-1)
+        idx = level1_index(n, d.numel())
+        out[n] = (d if idx is None else d[idx]).clone()
+    return out
+
+
+def layout(obj):
+    """the structure of a checkpoint dict: every tensor replaced by ("tensor", shape, dtype), other leaves kept"""
+    if torch.is_tensor(obj):
+        return ("tensor", tuple(obj.shape), str(obj.dtype))
+    if isinstance(obj, dict):
+        return {k: layout(v) for k, v in obj.items()}
+    if isinstance(obj, (list, tuple)):
+        return type(obj)(layout(v) for v in obj)
+    return obj
+
+
+def materialize(lay, seed=0):
+    """a checkpoint dict with the structure `lay` (from layout()), its tensors filled deterministically"""
+    g = torch.Generator().manual_seed(seed)
+
+    def make(x):
+        if isinstance(x, tuple) and len(x) == 3 and x[0] == "tensor":
+            dt = getattr(torch, x[2].split(".")[-1])
+            if dt.is_floating_point:
+                return torch.randn(x[1], generator=g).to(dt)
+            return torch.randint(0, 7, x[1], generator=g).to(dt)
+        if isinstance(x, dict):
+            return {k: make(v) for k, v in x.items()}
+        if isinstance(x, (list, tuple)):
+            return type(x)(make(v) for v in x)
+        return x
+    return make(lay)

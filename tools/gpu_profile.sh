@@ -5,7 +5,7 @@
 tag=${1:-b128}; batch=${2:-128}
 out=$PWD/gpurun_out/prof_$tag; mkdir -p $out
 export TMPDIR=/tmp
-python bench.py --batch $batch --gemm-table $out/gemm_table.txt > $out/bench.json 2> $out/bench.err
+python bench.py --full --batch $batch --gemm-table $out/gemm_table.txt > $out/bench.json 2> $out/bench.err
 tail -c 2500 $out/bench.json
 repo=$PWD
 cd /tmp
