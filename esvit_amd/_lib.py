@@ -37,6 +37,16 @@ class GemmDesc(C.Structure):
     ]
 
 
+class JpegDesc(C.Structure):
+    _fields_ = [
+        ("n_images", i32), ("n_segments", i32), ("n_lanes", i32), ("n_blocks", i32),
+        ("plane_bytes", i64),
+        ("images", vp), ("segments", vp), ("lane_seg", vp), ("huff", vp), ("quant", vp), ("scan", vp),
+        ("table", vp), ("out", vp), ("status", vp),
+        ("mode", i32), ("max_passes", i32),
+    ]
+
+
 # name -> (restype, argtypes); every symbol declared in include/esvit_hip.h
 SIGNATURES = {
     "esvit_version": (C.c_int, []),
@@ -86,6 +96,7 @@ SIGNATURES = {
     "esvit_weightnorm_fwd": (C.c_int, [C.c_int, vp, vp, C.c_int, C.c_int, vp, vp, vp, vp]),
     "esvit_weightnorm_bwd": (C.c_int, [vp, vp, vp, vp, C.c_int, C.c_int, vp, vp, vp]),
     "esvit_aug_crops": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp]),
+    "esvit_jpeg_decode": (C.c_int, [C.POINTER(JpegDesc), vp, C.c_size_t, vp]),
     "esvit_heads_split": (C.c_int, [C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]),
     "esvit_heads_merge": (C.c_int, [C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]),
     "esvit_softmax_rows_fwd": (C.c_int, [C.c_int, vp, i64, C.c_int, C.c_int, f32, vp]),

@@ -136,6 +136,24 @@ class PackedImages:
             self.data = host.pin_memory().to(device, non_blocking=True) if torch.cuda.is_available() else host.to(device)
         self.table = torch.from_numpy(np.stack([offs, self.H, self.W], axis=1).astype(np.int64)).to(self.data.device)
 
+    @classmethod
+    def from_device(cls, data, table, H, W):
+        """wrap images already packed in device memory (the JPEG decoder's output): ``data`` uint8 with the 4 pad bytes,
+        ``table`` int64 [B, 3] (byte offset, H, W) on the same device, ``H`` / ``W`` the sizes as host arrays"""
+        self = cls.__new__(cls)
+        self.H, self.W = np.asarray(H, np.int64), np.asarray(W, np.int64)
+        if len(self.H) == 0:
+            raise ValueError("PackedImages: an empty batch")
+        if data.dtype != torch.uint8 or data.numel() < int((self.H * self.W * 3).sum()) + 4:
+            raise ValueError("PackedImages.from_device: data must be uint8 and hold every image plus 4 pad bytes")
+        self.data, self.table = data, table
+        return self
+
+    @property
+    def offsets(self):
+        """byte offset of every image in ``data`` (host int64 array: the images are back to back in batch order)"""
+        return np.concatenate([[0], np.cumsum(self.H * self.W * 3)[:-1]]).astype(np.int64)
+
     def __len__(self):
         return len(self.H)
 
@@ -188,6 +206,15 @@ class DataAugmentationDINO:
             def __len__(self):
                 return len(images)
         return (images, self.draw(_Sizes())), torch.as_tensor([y for _, y in batch])
+
+    def collate_encoded(self, batch):
+        """``collate_fn`` for a DataLoader whose dataset yields ``(encoded image bytes, label)`` (:class:`jpeg.EncodedImageFolder`,
+        or a zip / TSV reader's raw bytes): the WORKER parses the headers, decodes the inputs the GPU does not take with Pillow and
+        makes the random draws from the header sizes; the training process uploads, decodes on the GPU and renders
+        (:class:`GpuAugmentedLoader`) -> ``((jpeg.Batch, draws), labels)``"""
+        from . import jpeg
+        enc = jpeg.prepare([x for x, _ in batch])
+        return (enc, self.draw(enc)), torch.as_tensor([y for _, y in batch])
 
     def __call__(self, images, uniforms=None, draws=None):
         if not isinstance(images, (list, tuple, PackedImages)):
@@ -245,10 +272,50 @@ class GpuAugmentedLoader:
         return len(self.loader)
 
     def _render(self, item):
+        crops, labels, pending = self._render_async(item)
+        return self._settle(crops, pending), labels
+
+    def _render_async(self, item):
+        """enqueue the crops of one loader item on the current stream -> (crops, labels, pending): ``pending`` is None, or the
+        status read-back of a GPU-decoded batch that :meth:`_settle` checks before the crops are handed out"""
         images, labels = item
-        if isinstance(images, tuple) and len(images) == 2 and isinstance(images[1], dict):  # DataAugmentationDINO.collate
-            return self.augment(images[0], draws=images[1]), labels
-        return self.augment(images), labels
+        if isinstance(images, tuple) and len(images) == 2 and isinstance(images[1], dict):  # DataAugmentationDINO.collate(_encoded)
+            from . import jpeg
+            if isinstance(images[0], jpeg.Batch):  # encoded bytes: decode on the GPU, then render
+                crops, pending = self._render_encoded(images[0], images[1])
+                return crops, labels, pending
+            return self.augment(images[0], draws=images[1]), labels, None
+        return self.augment(images), labels, None
+
+    def _render_encoded(self, enc, draws):
+        """decode + crops on the current stream, and an asynchronous copy of the per-image status into pinned memory.  An input
+        Pillow cannot decode (a truncated file) raises its OSError here, from the worker's verdict, without touching the device."""
+        from . import jpeg
+        for k, msg in enc.errors.items():
+            raise OSError("%s (image %d of the batch)" % (msg, k))
+        packed, status = jpeg.decode(enc, self.augment.device)
+        host = torch.empty(status.shape, dtype=status.dtype, pin_memory=True)
+        host.copy_(status, non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record()
+        crops = self.augment(packed, draws=draws)
+        return crops, (host, ev, enc, packed, status, draws)
+
+    def _settle(self, crops, pending):
+        """the crops of a malformed image never differ silently from Pillow's: wait for the status copy of the batch, and if the GPU
+        found corrupt entropy data in an image, re-decode it with Pillow into its slot and render the batch again on the current
+        stream (Pillow decodes such data with a warning, not an error).  With prefetch this runs one iteration after the decode was
+        enqueued, just before the batch is yielded: the decode has then finished beside the previous step and the wait is empty."""
+        if pending is None:
+            return crops
+        from . import jpeg
+        host, ev, enc, packed, status, draws = pending
+        ev.synchronize()
+        st = host.numpy()
+        if not (st & jpeg.ST_CORRUPT).any():
+            return crops
+        jpeg.repair(packed, status, enc, st)
+        return self.augment(packed, draws=draws)
 
     def __iter__(self):
         if not self.prefetch:
@@ -266,14 +333,21 @@ class GpuAugmentedLoader:
                 return None
             self._stream.wait_stream(torch.cuda.current_stream())  # (a scratch freed by the consumer is not reused too early)
             with torch.cuda.stream(self._stream):
-                crops, labels = self._render(item)
+                crops, labels, pending = self._render_async(item)
                 ev = torch.cuda.Event()
                 ev.record(self._stream)
-            return crops, labels, ev
+            return crops, labels, ev, pending
         nxt = produce()
         while nxt is not None:
-            crops, labels, ev = nxt
+            crops, labels, ev, pending = nxt
             nxt = produce()  # enqueued BEFORE the consumer's step: it runs beside it
+            if pending is not None:  # checked only now, a whole step after its decode was enqueued (see _settle)
+                with torch.cuda.stream(self._stream):
+                    settled = self._settle(crops, pending)
+                    if settled is not crops:
+                        crops = settled
+                        ev = torch.cuda.Event()
+                        ev.record(self._stream)
             main = torch.cuda.current_stream()
             main.wait_event(ev)
             for c in crops:

@@ -46,6 +46,7 @@ const char* esvit_last_error(void);
  *   ESVIT_Q_UPDATE_CHUNK_ELEMS ()              elements per chunk of the fused update's chunk table
  *   ESVIT_Q_MLP_FUSED (dtype, C)               bit 0: esvit_mlp_fused_fwd exists (bf16, C in {96, 128, 192, 256, 384}), bit 1: esvit_mlp_fused_bwd exists (bf16, C in {96, 128, 192, 256})
  *   ESVIT_Q_AUG_MAX_BOX (S)                    largest crop-box side esvit_aug_crops resizes to S x S
+ *   ESVIT_Q_JPEG_WORKSPACE (n_blocks, plane_bytes, n_lanes | n_segments << 32)  bytes of the esvit_jpeg_decode workspace
  * Unknown `what` returns ESVIT_ERR_ARG. */
 #define ESVIT_Q_ATTN_FRAG_ELEMS 1
 #define ESVIT_Q_ATTN_LSE_ELEMS 2
@@ -57,6 +58,7 @@ const char* esvit_last_error(void);
 #define ESVIT_Q_UPDATE_CHUNK_ELEMS 8
 #define ESVIT_Q_MLP_FUSED 9
 #define ESVIT_Q_AUG_MAX_BOX 10
+#define ESVIT_Q_JPEG_WORKSPACE 11
 int64_t esvit_query(int what, int64_t a, int64_t b, int64_t c);
 
 /* ---- host-side integer index maps (bit-exact vs reference) -------------
@@ -463,6 +465,50 @@ int esvit_bn_bwd_coeffs(const float* red, float n, const float* gamma, const flo
 #define ESVIT_AUG_PARAM_INTS 24
 int esvit_aug_crops(const uint8_t* src, const int64_t* images, const int32_t* params, int n, int S, int max_h, int max_w,
                     uint8_t* planes, float* out, esvit_stream_t stream);
+
+/* ---- JPEG decoder (the input side of the crop producer) ------------------
+ * The reference decodes every file with Image.open(f).convert('RGB') (datasets/build.py ImageFolder, the zip and TSV readers).
+ * esvit_jpeg_decode decodes a batch of baseline Huffman JPEGs (SOF0 / SOF1, 8-bit; grayscale or YCbCr 4:4:4 / 4:2:2 / 4:2:0;
+ * restart intervals; any size) into the packed HWC RGB images esvit_aug_crops reads, bit-exact with Pillow's default decode.
+ * The caller (esvit_amd/jpeg.py) has parsed the headers and laid the batch out; every array below is device memory:
+ *   images    int32 [n_images, ESVIT_JPEG_IMG_INTS]: H, W, ncomp (0: not decoded here -- its slot is filled by the caller), hmax,
+ *             vmax, MCUs per row, MCU rows, blocks per MCU, restart interval, first segment, segments, first coefficient block,
+ *             first plane byte, blocks, plane bytes, status bits to report as they are; from int 16, per component (12 ints):
+ *             h, v, quant table, DC table, AC table, block columns, block rows, first block, first plane byte, downsampled width,
+ *             downsampled height, 0
+ *   segments  int32 [n_segments, ESVIT_JPEG_SEG_INTS]: image, entropy-coded bits, byte offset in `scan`, first MCU, MCUs, first lane,
+ *             lanes (= max(1, ceil(bits / ESVIT_JPEG_LANE_BITS)))
+ *   lane_seg  int32 [n_lanes]: the segment of every lane (a segment's lanes are consecutive)
+ *   huff      int32 [*, ESVIT_JPEG_HUFF_INTS]: 9-bit lookup (length << 8 | symbol), maxcode[18], value offsets[18], symbols[256]
+ *   quant     int32 [*, 64] quantisation tables in natural order
+ *   scan      uint8: the un-stuffed entropy-coded data of every segment, each 4-byte aligned and followed by >= 8 zero bytes
+ *   table     int64 [n_images, 3] (byte offset in `out`, H, W) -- the esvit_aug_crops image table
+ *   out       uint8 packed HWC RGB images;  status  int32 [n_images]: the host bits | 1 where the entropy data is corrupt
+ * mode: ESVIT_JPEG_PARALLEL (self-synchronising parallel entropy decode, bounded by max_passes sync passes (0: the default, 8; at most 64) and
+ * ending in the serial decode of any segment that has not converged) or ESVIT_JPEG_SERIAL (one lane per segment: the reference).
+ * workspace: esvit_query(ESVIT_Q_JPEG_WORKSPACE, n_blocks, plane_bytes, n_lanes | n_segments << 32) bytes. */
+#define ESVIT_JPEG_IMG_INTS 64
+#define ESVIT_JPEG_SEG_INTS 8
+#define ESVIT_JPEG_HUFF_INTS 832
+#define ESVIT_JPEG_LANE_BITS 4096
+#define ESVIT_JPEG_PARALLEL 0
+#define ESVIT_JPEG_SERIAL 1
+typedef struct {
+    int32_t n_images, n_segments, n_lanes, n_blocks;
+    int64_t plane_bytes;
+    const int32_t* images;
+    const int32_t* segments;
+    const int32_t* lane_seg;
+    const int32_t* huff;
+    const int32_t* quant;
+    const uint8_t* scan;
+    const int64_t* table;
+    uint8_t* out;
+    int32_t* status;
+    int32_t mode;
+    int32_t max_passes;
+} esvit_jpeg_desc;
+int esvit_jpeg_decode(const esvit_jpeg_desc* d, void* workspace, size_t ws_bytes, esvit_stream_t stream);
 
 /* ---- global attention of the monolithic ViT backbones --------------------- */
 /* models/vision_transformer.py:67-94 (Attention.forward of deit_tiny / deit_small / vit_base): the score matrix lives in HBM
