@@ -18,6 +18,11 @@
 //                       (aug_finish_plane_kernel: whole-plane fallback for box radii beyond the tile's halo budget)
 // All of it is byte / integer work bound by HBM (source box in, fp32 crop out); the uint8 planes between the kernels are
 // 150 KB per 224^2 crop and live in L2 / MALL.  Arithmetic: augment_math.h, bit-exact against Pillow.
+//
+// Evaluation input (esvit_aug_crops with ESVIT_AUG_EVAL): the eval transforms of eval_knn.py / eval_linear.py have no jitter chain, so
+// the same resize kernel (EVAL = true) goes from the packed bytes straight to the normalised fp32 crop in one launch.  Its rows
+// also name the size the box is resized to, the offset of the S x S window inside that resize (Resize(256) -> CenterCrop(224)
+// is not a resize of a crop box to S x S) and the filter (bicubic or bilinear).
 #include "common.h"
 #include "esvit_hip.h"
 #include "augment_math.h"
@@ -30,14 +35,20 @@ constexpr int NP = ESVIT_AUG_PARAM_INTS;
 // columns of a parameter row (include/esvit_hip.h)
 enum { P_SRC = 0, P_TOP, P_LEFT, P_H, P_W, P_FLIP, P_OP0, P_OP1, P_OP2, P_OP3, P_BRIGHT, P_CONTRAST, P_SAT, P_HUE, P_GRAY, P_BLUR_R1, P_BLUR_WW,
        P_BLUR_FW, P_SOLARIZE };
+// columns of an evaluation-mode row: the first six are those of the crop producer's rows
+constexpr int NR = ESVIT_RESIZE_PARAM_INTS;
+enum { R_RH = 6, R_RW, R_OFF_Y, R_OFF_X, R_FILTER };
 
 // ---------------------------------------------------------------------------------------------------------------------
 // resize: LDS = kx[TS][KX] | ky[TS][KY] | bounds[2][TS][2] | tmp[RMAX][TS] (packed r | g << 8 | b << 16) | stage[RMAX][SWD] dwords
+// EVAL = false: esvit_aug_crops (box -> S x S bicubic; uint8 planes, and the contrast sums zeroed);
+// EVAL = true: the evaluation mode (box -> rh x rw with the row's filter, the S x S window at (off_y, off_x); ToTensor + Normalize
+// fused into the vertical pass: fp32 [n, 3, S, S])
 // ---------------------------------------------------------------------------------------------------------------------
-template <int TS, bool STAGE>
+template <int TS, bool STAGE, bool EVAL>
 __global__ __launch_bounds__(256) void aug_resize_kernel(const uint8_t* __restrict__ src, const int64_t* __restrict__ images,
                                                           const int32_t* __restrict__ params, int S, int KX, int KY, int RMAX, int SWD,
-                                                          uint8_t* __restrict__ planes, int* __restrict__ sums) {
+                                                          uint8_t* __restrict__ planes, int* __restrict__ sums, float* __restrict__ outf) {
     extern __shared__ __align__(16) unsigned char smem[];
     int32_t* kx = reinterpret_cast<int32_t*>(smem);
     int32_t* ky = kx + TS * KX;
@@ -48,20 +59,24 @@ __global__ __launch_bounds__(256) void aug_resize_kernel(const uint8_t* __restri
     const int crop = blockIdx.y;
     const int tiles = (S + TS - 1) / TS;
     const int ty = blockIdx.x / tiles, tx = blockIdx.x % tiles;
-    const int32_t* p = params + (long)crop * NP;
+    const int32_t* p = params + (long)crop * (EVAL ? NR : NP);
     const int top = p[P_TOP], left = p[P_LEFT], h = p[P_H], w = p[P_W], flip = p[P_FLIP];
+    const int rh = EVAL ? p[R_RH] : S, rw = EVAL ? p[R_RW] : S, off_y = EVAL ? p[R_OFF_Y] : 0, off_x = EVAL ? p[R_OFF_X] : 0;
+    const int filter = EVAL ? p[R_FILTER] : (int)aug::FILTER_BICUBIC;
     const int64_t* im = images + (long)p[P_SRC] * 3;
     const long pitch = im[2] * 3;
     const uint8_t* base = src + im[0] + (long)top * pitch + (long)left * 3;
     const int tid = threadIdx.x;
-    if (blockIdx.x == 0 && tid == 0) sums[crop] = 0;  // the accumulator of aug_mean_kernel
+    if (!EVAL && blockIdx.x == 0 && tid == 0) sums[crop] = 0;  // the accumulator of aug_mean_kernel
 
     // the taps of this tile's TS columns and TS rows (Resample.c precompute_coeffs, one output position per thread)
     if (tid < 2 * TS) {
         const int axis = tid / TS, t = tid % TS;
         const int pos = (axis ? ty : tx) * TS + t;
         int first = 0, count = 0;
-        if (pos < S) aug::resample_row(axis ? h : w, S, pos, axis ? KY : KX, &first, &count, (axis ? ky : kx) + t * (axis ? KY : KX));
+        if (pos < S)
+            aug::resample_row_f(filter, axis ? h : w, axis ? rh : rw, (axis ? off_y : off_x) + pos, axis ? KY : KX, &first, &count,
+                                (axis ? ky : kx) + t * (axis ? KY : KX));
         bnd[(axis * TS + t) * 2] = first;
         bnd[(axis * TS + t) * 2 + 1] = count;
     }
@@ -121,7 +136,8 @@ __global__ __launch_bounds__(256) void aug_resize_kernel(const uint8_t* __restri
     __syncthreads();
 
     // vertical pass out of LDS; RandomHorizontalFlip mirrors the column on the way out
-    uint8_t* out = planes + (long)crop * 3 * S * S;
+    uint8_t* out = planes + (EVAL ? 0 : (long)crop * 3 * S * S);
+    float* outc = outf + (EVAL ? (long)crop * 3 * S * S : 0);
     for (int item = tid; item < TS * TS; item += 256) {
         const int yy = item / TS, xx = item % TS;
         if (yy >= ny || xx >= nx) continue;
@@ -140,9 +156,15 @@ __global__ __launch_bounds__(256) void aug_resize_kernel(const uint8_t* __restri
         const int Y = ty * TS + yy, X0 = tx * TS + xx;
         const int X = flip ? S - 1 - X0 : X0;
         const long o = (long)Y * S + X;
-        out[o] = aug::clip8(s0);
-        out[(long)S * S + o] = aug::clip8(s1);
-        out[2L * S * S + o] = aug::clip8(s2);
+        if constexpr (EVAL) {  // ToTensor + Normalize (eval_knn.py:51-52) of Pillow's uint8 result
+            outc[o] = aug::normalize(aug::clip8(s0), 0.485f, 0.229f);
+            outc[(long)S * S + o] = aug::normalize(aug::clip8(s1), 0.456f, 0.224f);
+            outc[2L * S * S + o] = aug::normalize(aug::clip8(s2), 0.406f, 0.225f);
+        } else {
+            out[o] = aug::clip8(s0);
+            out[(long)S * S + o] = aug::clip8(s1);
+            out[2L * S * S + o] = aug::clip8(s2);
+        }
     }
 }
 
@@ -495,30 +517,51 @@ __global__ __launch_bounds__(PLANE_THREADS) void aug_finish_plane_kernel(const i
 
 constexpr size_t LDS_MAX = 160 * 1024;
 
-// rows (columns) of the source one tile of TS outputs can need when the axis is resized in_size -> S
-int tile_rows(int TS, int in_size, int S) {
-    const double scale = (double)in_size / S, support = 2.0 * (scale < 1.0 ? 1.0 : scale);
+// The LDS of the resize follows the largest per-axis scale of the call: `scale` = box side / resized side of the crop that has
+// the largest one, sized for the bicubic support (2, the larger one).  Taps per output position:
+int scale_ksize(double scale) { return (int)ceil(2.0 * (scale < 1.0 ? 1.0 : scale)) * 2 + 1; }
+// rows (columns) of the source one tile of TS outputs can need
+int tile_rows(int TS, double scale) {
+    const double support = 2.0 * (scale < 1.0 ? 1.0 : scale);
     return (int)((TS - 1) * scale + 2 * support) + 3;
 }
-int stage_dwords(int TS, int max_w, int S) { return (tile_rows(TS, max_w, S) * 3 + 3) / 4 + 2; }
+int stage_dwords(int TS, double scale_x) { return (tile_rows(TS, scale_x) * 3 + 3) / 4 + 2; }
 
-size_t resize_lds(int TS, bool staged, int max_h, int max_w, int S) {
-    const int KX = aug::resample_ksize(max_w, S), KY = aug::resample_ksize(max_h, S), RMAX = tile_rows(TS, max_h, S);
-    return ((size_t)TS * KX + (size_t)TS * KY + 4 * TS + (size_t)RMAX * TS + (staged ? (size_t)RMAX * stage_dwords(TS, max_w, S) : 0)) * 4;
+size_t resize_lds(int TS, bool staged, double scale_y, double scale_x) {
+    const int KX = scale_ksize(scale_x), KY = scale_ksize(scale_y), RMAX = tile_rows(TS, scale_y);
+    return ((size_t)TS * KX + (size_t)TS * KY + 4 * TS + (size_t)RMAX * TS + (staged ? (size_t)RMAX * stage_dwords(TS, scale_x) : 0)) * 4;
 }
 
-template <int TS, bool STAGE>
-int launch_resize(const uint8_t* src, const int64_t* images, const int32_t* params, int n, int S, int max_h, int max_w, uint8_t* planes, int* sums,
-                  hipStream_t stream) {
-    auto kern = aug_resize_kernel<TS, STAGE>;
-    const size_t lds = resize_lds(TS, STAGE, max_h, max_w, S);
+template <int TS, bool STAGE, bool EVAL>
+int launch_resize(const uint8_t* src, const int64_t* images, const int32_t* params, int n, int S, double scale_y, double scale_x, uint8_t* planes,
+                  int* sums, float* out, hipStream_t stream) {
+    auto kern = aug_resize_kernel<TS, STAGE, EVAL>;
+    const size_t lds = resize_lds(TS, STAGE, scale_y, scale_x);
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     const int tiles = (S + TS - 1) / TS;
-    hipLaunchKernelGGL(kern, dim3(tiles * tiles, n), dim3(256), lds, stream, src, images, params, S, aug::resample_ksize(max_w, S),
-                       aug::resample_ksize(max_h, S), tile_rows(TS, max_h, S), stage_dwords(TS, max_w, S), planes, sums);
-    ESVIT_CHECK_LAUNCH("aug_crops(resize)");
+    hipLaunchKernelGGL(kern, dim3(tiles * tiles, n), dim3(256), lds, stream, src, images, params, S, scale_ksize(scale_x), scale_ksize(scale_y),
+                       tile_rows(TS, scale_y), stage_dwords(TS, scale_x), planes, sums, out);
+    ESVIT_CHECK_LAUNCH(EVAL ? "resize_crops" : "aug_crops(resize)");
     return ESVIT_OK;
 }
+
+// 32 x 32 tiles while four workgroups fit a CU's LDS (the phases of a workgroup are serial: residency hides them), else 16 x 16,
+// else 8 x 8 with and then without the staged rows; ESVIT_ERR_UNSUPPORTED (no launch) when not even that fits
+template <bool EVAL>
+int launch_resize_tiles(const uint8_t* src, const int64_t* images, const int32_t* params, int n, int S, double scale_y, double scale_x,
+                        uint8_t* planes, int* sums, float* out, hipStream_t stream) {
+    if (resize_lds(32, true, scale_y, scale_x) <= LDS_MAX / 4)
+        return launch_resize<32, true, EVAL>(src, images, params, n, S, scale_y, scale_x, planes, sums, out, stream);
+    if (resize_lds(16, true, scale_y, scale_x) <= LDS_MAX / 2)
+        return launch_resize<16, true, EVAL>(src, images, params, n, S, scale_y, scale_x, planes, sums, out, stream);
+    if (resize_lds(8, true, scale_y, scale_x) <= LDS_MAX)
+        return launch_resize<8, true, EVAL>(src, images, params, n, S, scale_y, scale_x, planes, sums, out, stream);
+    if (resize_lds(8, false, scale_y, scale_x) <= LDS_MAX)
+        return launch_resize<8, false, EVAL>(src, images, params, n, S, scale_y, scale_x, planes, sums, out, stream);
+    return ESVIT_ERR_UNSUPPORTED;
+}
+
+bool resize_fits(double scale_y, double scale_x) { return resize_lds(8, false, scale_y, scale_x) <= LDS_MAX; }
 
 }  // namespace
 
@@ -527,15 +570,35 @@ int64_t esvit_i_aug_max_box(int S) {
     int64_t lo = S, hi = 1 << 20;
     while (lo < hi) {
         const int64_t mid = (lo + hi + 1) / 2;
-        if (resize_lds(8, false, (int)mid, (int)mid, S) <= LDS_MAX) lo = mid;
+        if (resize_fits((double)mid / S, (double)mid / S)) lo = mid;
         else hi = mid - 1;
     }
     return lo;
 }
 
+namespace {
+// esvit_aug_crops with ESVIT_AUG_EVAL in S (and no planes): the evaluation transforms, one launch (include/esvit_hip.h)
+int resize_crops(const uint8_t* src, const int64_t* images, const int32_t* params, int n, int S, int scale_h, int scale_w, float* out,
+                 hipStream_t stream) {
+    ESVIT_CHECK_ARG(n >= 0 && n <= 65535 && S > 0 && S <= 4096 && scale_h > 0 && scale_w > 0,
+                    "esvit_aug_crops (evaluation): bad sizes n=%d S=%d scales %d, %d", n, S, scale_h, scale_w);
+    if (n == 0) return ESVIT_OK;
+    const int rc = launch_resize_tiles<true>(src, images, params, n, S, (double)scale_h / ESVIT_RESIZE_SCALE_ONE,
+                                             (double)scale_w / ESVIT_RESIZE_SCALE_ONE, nullptr, nullptr, out, stream);
+    if (rc == ESVIT_ERR_UNSUPPORTED)
+        esvit_set_error("esvit_aug_crops (evaluation): scales %.4f x %.4f are beyond esvit_query(ESVIT_Q_RESIZE_FITS)",
+                        (double)scale_h / ESVIT_RESIZE_SCALE_ONE, (double)scale_w / ESVIT_RESIZE_SCALE_ONE);
+    return rc;
+}
+}  // namespace
+
 extern "C" int esvit_aug_crops(const uint8_t* src, const int64_t* images, const int32_t* params, int n, int S, int max_h, int max_w,
                                uint8_t* planes, float* out, esvit_stream_t stream_) {
     hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+    if (S & ESVIT_AUG_EVAL) {  // the evaluation transforms: selected by the flag in S, and they take no planes
+        ESVIT_CHECK_ARG(src && images && params && out && !planes, "esvit_aug_crops (evaluation): null pointer, or planes given");
+        return resize_crops(src, images, params, n, S & ~ESVIT_AUG_EVAL, max_h, max_w, out, stream);
+    }
     ESVIT_CHECK_ARG(src && images && params && planes && out, "esvit_aug_crops: null pointer");
     ESVIT_CHECK_ARG(n >= 0 && n <= 65535 && S > 0 && max_h > 0 && max_w > 0, "esvit_aug_crops: bad sizes n=%d S=%d box %dx%d", n, S, max_h, max_w);
     if (n == 0) return ESVIT_OK;
@@ -545,13 +608,8 @@ extern "C" int esvit_aug_crops(const uint8_t* src, const int64_t* images, const 
         return ESVIT_ERR_UNSUPPORTED;
     }
     int* sums = reinterpret_cast<int*>(planes + (size_t)n * 3 * S * S);
-    int rc = ESVIT_ERR_UNSUPPORTED;
-    // 32 x 32 tiles while four workgroups fit a CU's LDS (the phases of a workgroup are serial: residency hides them), else 16 x 16
-    if (resize_lds(32, true, max_h, max_w, S) <= LDS_MAX / 4) rc = launch_resize<32, true>(src, images, params, n, S, max_h, max_w, planes, sums, stream);
-    else if (resize_lds(16, true, max_h, max_w, S) <= LDS_MAX / 2) rc = launch_resize<16, true>(src, images, params, n, S, max_h, max_w, planes, sums, stream);
-    else if (resize_lds(8, true, max_h, max_w, S) <= LDS_MAX) rc = launch_resize<8, true>(src, images, params, n, S, max_h, max_w, planes, sums, stream);
-    else if (resize_lds(8, false, max_h, max_w, S) <= LDS_MAX) rc = launch_resize<8, false>(src, images, params, n, S, max_h, max_w, planes, sums, stream);
-    else esvit_set_error("esvit_aug_crops: crop box %dx%d -> %d is beyond esvit_query(ESVIT_Q_AUG_MAX_BOX)", max_h, max_w, S);
+    const int rc = launch_resize_tiles<false>(src, images, params, n, S, (double)max_h / S, (double)max_w / S, planes, sums, nullptr, stream);
+    if (rc == ESVIT_ERR_UNSUPPORTED) esvit_set_error("esvit_aug_crops: crop box %dx%d -> %d is beyond esvit_query(ESVIT_Q_AUG_MAX_BOX)", max_h, max_w, S);
     if (rc != ESVIT_OK) return rc;
     hipLaunchKernelGGL(aug_mean_kernel, dim3((S * S + MEAN_PX - 1) / MEAN_PX, n), dim3(256), 0, stream, params, S, planes, sums);
     ESVIT_CHECK_LAUNCH("aug_crops(mean)");
@@ -570,4 +628,10 @@ extern "C" int esvit_aug_crops(const uint8_t* src, const int64_t* images, const 
         ESVIT_CHECK_LAUNCH("aug_crops(finish, whole plane)");
     }
     return ESVIT_OK;
+}
+
+// whether an evaluation-mode call whose largest per-axis scales are scale_h, scale_w (units of 1 / ESVIT_RESIZE_SCALE_ONE) fits
+int64_t esvit_i_resize_fits(int64_t scale_h, int64_t scale_w) {
+    if (scale_h <= 0 || scale_w <= 0 || scale_h > 0x7fffffff || scale_w > 0x7fffffff) return 0;
+    return resize_fits((double)scale_h / ESVIT_RESIZE_SCALE_ONE, (double)scale_w / ESVIT_RESIZE_SCALE_ONE) ? 1 : 0;
 }

@@ -35,37 +35,56 @@ AUG_HD double bicubic(double x) {
     return 0.0;
 }
 
-// number of taps a row of coefficients can hold: Resample.c precompute_coeffs, ksize
-AUG_HD int resample_ksize(int in_size, int out_size) {
-    double filterscale = (double)in_size / out_size;
-    if (filterscale < 1.0) filterscale = 1.0;
-    return (int)ceil(2.0 * filterscale) * 2 + 1;
+// Resample.c bilinear_filter
+AUG_HD double bilinear(double x) {
+    if (x < 0.0) x = -x;
+    if (x < 1.0) return 1.0 - x;
+    return 0.0;
 }
 
-// Resample.c precompute_coeffs + normalize_coeffs_8bpc for output position xx of an axis resized in_size -> out_size (the box
-// is the whole axis): first tap, number of taps (<= kmax, the caller's row length) and the fixed-point taps
-AUG_HD void resample_row(int in_size, int out_size, int xx, int kmax, int* first, int* count, int32_t* k) {
+// the filters of Resample.c this header implements, with their support (filterp->support)
+enum { FILTER_BICUBIC = 0, FILTER_BILINEAR = 1 };
+AUG_HD double filter_support(int filter) { return filter == FILTER_BILINEAR ? 1.0 : 2.0; }
+AUG_HD double filter_tap(int filter, double x) { return filter == FILTER_BILINEAR ? bilinear(x) : bicubic(x); }
+
+// number of taps a row of coefficients can hold: Resample.c precompute_coeffs, ksize = ceil(support * filterscale) * 2 + 1
+AUG_HD int resample_ksize_f(int filter, int in_size, int out_size) {
+    double filterscale = (double)in_size / out_size;
+    if (filterscale < 1.0) filterscale = 1.0;
+    return (int)ceil(filter_support(filter) * filterscale) * 2 + 1;
+}
+
+// Resample.c precompute_coeffs + normalize_coeffs_8bpc for output position pos of an axis resized in_size -> out_size (the box
+// is the whole axis): first tap, number of taps (<= kmax, the caller's row length) and the fixed-point taps.  The taps of one
+// output position depend on that position only, so position offset + t of the full resize is pixel t of a window cut from it.
+AUG_HD void resample_row_f(int filter, int in_size, int out_size, int pos, int kmax, int* first, int* count, int32_t* k) {
     const double scale = (double)in_size / out_size;
     double filterscale = scale;
     if (filterscale < 1.0) filterscale = 1.0;
-    const double support = 2.0 * filterscale;
-    const double center = (xx + 0.5) * scale;
+    const double support = filter_support(filter) * filterscale;
+    const double center = (pos + 0.5) * scale;
     const double ss = 1.0 / filterscale;
     int xmin = (int)(center - support + 0.5);
     if (xmin < 0) xmin = 0;
     int xmax = (int)(center + support + 0.5);
     if (xmax > in_size) xmax = in_size;
     xmax -= xmin;
-    if (xmax > kmax) xmax = kmax;  // cannot happen when kmax >= resample_ksize(in_size, out_size)
+    if (xmax > kmax) xmax = kmax;  // cannot happen when kmax >= resample_ksize_f(filter, in_size, out_size)
     double ww = 0.0;
-    for (int x = 0; x < xmax; ++x) ww += bicubic((x + xmin - center + 0.5) * ss);
+    for (int x = 0; x < xmax; ++x) ww += filter_tap(filter, (x + xmin - center + 0.5) * ss);
     for (int x = 0; x < xmax; ++x) {
-        double w = bicubic((x + xmin - center + 0.5) * ss);
+        double w = filter_tap(filter, (x + xmin - center + 0.5) * ss);
         if (ww != 0.0) w /= ww;
         k[x] = w < 0 ? (int32_t)(-0.5 + w * (1 << PRECISION_BITS)) : (int32_t)(0.5 + w * (1 << PRECISION_BITS));
     }
     *first = xmin;
     *count = xmax;
+}
+
+// the bicubic forms the crop producer uses (support 2: the same arithmetic as the general ones with FILTER_BICUBIC)
+AUG_HD int resample_ksize(int in_size, int out_size) { return resample_ksize_f(FILTER_BICUBIC, in_size, out_size); }
+AUG_HD void resample_row(int in_size, int out_size, int xx, int kmax, int* first, int* count, int32_t* k) {
+    resample_row_f(FILTER_BICUBIC, in_size, out_size, xx, kmax, first, count, k);
 }
 
 AUG_HD uint8_t clip8(int32_t ss) {  // Resample.c clip8: arithmetic shift, clamp

@@ -33,6 +33,7 @@ int esvit_i_update_chunk_elems();
 int esvit_i_mlp_fused_supported(int dtype, int C);
 int64_t esvit_i_aug_max_box(int S);
 int64_t esvit_i_jpeg_workspace(int64_t blocks, int64_t plane_bytes, int64_t lanes_segs);
+int64_t esvit_i_resize_fits(int64_t scale_h, int64_t scale_w);
 
 extern "C" int64_t esvit_query(int what, int64_t a, int64_t b, int64_t c) {
     switch (what) {
@@ -47,6 +48,7 @@ extern "C" int64_t esvit_query(int what, int64_t a, int64_t b, int64_t c) {
         case ESVIT_Q_MLP_FUSED: return esvit_i_mlp_fused_supported((int)a, (int)b);
         case ESVIT_Q_AUG_MAX_BOX: return a > 0 ? esvit_i_aug_max_box((int)a) : 0;
         case ESVIT_Q_JPEG_WORKSPACE: return esvit_i_jpeg_workspace(a, b, c);
+        case ESVIT_Q_RESIZE_FITS: return esvit_i_resize_fits(a, b);
     }
     esvit_set_error("esvit_query: unknown question %d", what);
     return ESVIT_ERR_ARG;

@@ -53,20 +53,16 @@ def box_blur_weights(radius, passes=3):
     return r, ww, fw
 
 
-def sample_params(u, src, H, W, size, scale, blur_p, solarize_p):
-    """int32 [n, 24] parameter rows of esvit_aug_crops from uniforms ``u`` [n, NDRAWS] in [0, 1): crop n is cut from image
-    ``src[n]`` of ``H[n] x W[n]`` pixels.  ``blur_p`` / ``solarize_p``: probabilities of the slot (build.py:222,229-230,248)."""
-    u = np.asarray(u, np.float64)
+def random_resized_crop_boxes(u, H, W, scale, ratio=RATIO):
+    """RandomResizedCrop.get_params from uniforms ``u`` [n, >= U_J + 1] (columns U_ATTEMPT .. U_J of the layout above): up to 10
+    draws of (area, log-uniform aspect), the first box that fits wins, else the central crop of the closest admissible aspect
+    ratio -> (top, left, h, w) int64 arrays.  ``scale``: a pair of scalars or of per-crop arrays."""
     n = u.shape[0]
-    H, W = np.asarray(H, np.int64), np.asarray(W, np.int64)
-    rows = np.zeros((n, ops.AUG_PARAM_INTS), np.int32)
-    rows[:, 0] = src
-    # RandomResizedCrop.get_params: up to 10 draws of (area, log-uniform aspect); the first box that fits wins
     area = (H * W).astype(np.float64)[:, None]
     ua, ur = u[:, U_ATTEMPT:U_ATTEMPT + 20:2], u[:, U_ATTEMPT + 1:U_ATTEMPT + 20:2]
     s0, s1 = np.reshape(np.asarray(scale[0], np.float64), (-1, 1)), np.reshape(np.asarray(scale[1], np.float64), (-1, 1))  # scalar or per crop
     target = area * (s0 + (s1 - s0) * ua)
-    lr0, lr1 = math.log(RATIO[0]), math.log(RATIO[1])
+    lr0, lr1 = math.log(ratio[0]), math.log(ratio[1])
     aspect = np.exp(lr0 + (lr1 - lr0) * ur)
     w = np.rint(np.sqrt(target * aspect)).astype(np.int64)  # round(): half to even, as Python's
     h = np.rint(np.sqrt(target / aspect)).astype(np.int64)
@@ -78,11 +74,22 @@ def sample_params(u, src, H, W, size, scale, blur_p, solarize_p):
     left = np.floor(u[:, U_J] * (W - cw + 1)).astype(np.int64)
     # fallback: the central crop of the closest admissible aspect ratio
     in_ratio = W / H
-    fw_ = np.where(in_ratio > RATIO[1], np.rint(H * RATIO[1]).astype(np.int64), W)
-    fh_ = np.where(in_ratio < RATIO[0], np.rint(W / RATIO[0]).astype(np.int64), H)
+    fw_ = np.where(in_ratio > ratio[1], np.rint(H * ratio[1]).astype(np.int64), W)
+    fh_ = np.where(in_ratio < ratio[0], np.rint(W / ratio[0]).astype(np.int64), H)
     cw, ch = np.where(found, cw, fw_), np.where(found, ch, fh_)
     top, left = np.where(found, top, (H - ch) // 2), np.where(found, left, (W - cw) // 2)
-    rows[:, 1], rows[:, 2], rows[:, 3], rows[:, 4] = top, left, ch, cw
+    return top, left, ch, cw
+
+
+def sample_params(u, src, H, W, size, scale, blur_p, solarize_p):
+    """int32 [n, 24] parameter rows of esvit_aug_crops from uniforms ``u`` [n, NDRAWS] in [0, 1): crop n is cut from image
+    ``src[n]`` of ``H[n] x W[n]`` pixels.  ``blur_p`` / ``solarize_p``: probabilities of the slot (build.py:222,229-230,248)."""
+    u = np.asarray(u, np.float64)
+    n = u.shape[0]
+    H, W = np.asarray(H, np.int64), np.asarray(W, np.int64)
+    rows = np.zeros((n, ops.AUG_PARAM_INTS), np.int32)
+    rows[:, 0] = src
+    rows[:, 1], rows[:, 2], rows[:, 3], rows[:, 4] = random_resized_crop_boxes(u, H, W, scale)
     rows[:, 5] = u[:, U_FLIP] < P_FLIP
     # RandomApply(ColorJitter, p = 0.8): a random order of the four operations, one factor each
     apply = u[:, U_APPLY] <= P_JITTER
@@ -279,7 +286,8 @@ class GpuAugmentedLoader:
         """enqueue the crops of one loader item on the current stream -> (crops, labels, pending): ``pending`` is None, or the
         status read-back of a GPU-decoded batch that :meth:`_settle` checks before the crops are handed out"""
         images, labels = item
-        if isinstance(images, tuple) and len(images) == 2 and isinstance(images[1], dict):  # DataAugmentationDINO.collate(_encoded)
+        # DataAugmentationDINO.collate(_encoded): draws {S: rows}; the eval transforms' collate(_encoded): one rows array
+        if isinstance(images, tuple) and len(images) == 2 and isinstance(images[1], (dict, np.ndarray)):
             from . import jpeg
             if isinstance(images[0], jpeg.Batch):  # encoded bytes: decode on the GPU, then render
                 crops, pending = self._render_encoded(images[0], images[1])
@@ -350,6 +358,6 @@ class GpuAugmentedLoader:
                         ev.record(self._stream)
             main = torch.cuda.current_stream()
             main.wait_event(ev)
-            for c in crops:
+            for c in (crops if isinstance(crops, list) else [crops]):  # (a crop list, or the eval transforms' one batch tensor)
                 c.record_stream(main)
             yield crops, labels

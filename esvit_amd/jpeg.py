@@ -533,12 +533,15 @@ def pixels(packed, k):
 class EncodedImageFolder:
     """``root/<class>/<file>`` -> ``(file bytes, class index)`` with torchvision ``ImageFolder``'s ordering: classes are the
     sorted sub-directory names, samples the sorted walk of each class directory (following links) filtered by its image
-    extensions.  The bytes feed :meth:`data.DataAugmentationDINO.collate_encoded`."""
+    extensions.  The bytes feed :meth:`data.DataAugmentationDINO.collate_encoded` or an eval transform's ``collate_encoded``.
+    ``return_index=True``: ``(file bytes, sample index)`` instead, as the reference's ReturnIndexDataset (eval_knn.py:235-238)
+    yields for ``extract_features``."""
 
     EXTENSIONS = (".jpg", ".jpeg", ".png", ".ppm", ".bmp", ".pgm", ".tif", ".tiff", ".webp")
 
-    def __init__(self, root):
+    def __init__(self, root, return_index=False):
         self.root = root
+        self.return_index = return_index
         self.classes = sorted(e.name for e in os.scandir(root) if e.is_dir())
         self.class_to_idx = {c: i for i, c in enumerate(self.classes)}
         self.samples = []
@@ -556,7 +559,7 @@ class EncodedImageFolder:
     def __getitem__(self, i):
         path, target = self.samples[i]
         with open(path, "rb") as f:
-            return f.read(), target
+            return f.read(), (i if self.return_index else target)
 
 
 def sha256(a):

@@ -83,7 +83,7 @@ def relative_position_index(ws):
 
 # esvit_query questions (include/esvit_hip.h)
 (Q_ATTN_FRAG_ELEMS, Q_ATTN_LSE_ELEMS, Q_ATTN_BWD_PARTS, Q_ATTN_BWD_PAD_ROWS, Q_LN_BWD_BLOCKS, Q_COLSUM_BLOCKS, Q_COL_REDUCE_BLOCKS,
- Q_UPDATE_CHUNK_ELEMS, Q_MLP_FUSED, Q_AUG_MAX_BOX, Q_JPEG_WORKSPACE) = range(1, 12)
+ Q_UPDATE_CHUNK_ELEMS, Q_MLP_FUSED, Q_AUG_MAX_BOX, Q_JPEG_WORKSPACE, Q_RESIZE_FITS) = range(1, 13)
 
 
 def query(what, a=0, b=0, c=0):
@@ -1039,6 +1039,40 @@ def aug_crops(src, images, params, S, max_h, max_w, planes=None, out=None):
     assert out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.numel() >= n * 3 * S * S
     check(lib.esvit_aug_crops(_p(src), _p(images), _p(params), n, S, int(max_h), int(max_w), _p(planes), _p(out), _stream()), "aug_crops")
     return out, planes.view(-1)[:n * 3 * S * S].view(n, 3, S, S)
+
+
+# evaluation input (eval_knn.py:48-53, eval_linear.py:50-61)
+AUG_EVAL = 0x40000000  # ESVIT_AUG_EVAL: OR'd into S, selects the evaluation mode
+RESIZE_PARAM_INTS = 16
+RESIZE_SCALE_ONE = 65536
+FILTER_BICUBIC, FILTER_BILINEAR = 0, 1
+
+
+def _scale_fx(pair):
+    """(box side, resized side) -> the ratio in units of 1 / RESIZE_SCALE_ONE, rounded up (exact integer arithmetic), capped"""
+    box, resized = int(pair[0]), int(pair[1])
+    return min((box * RESIZE_SCALE_ONE + resized - 1) // resized, 0x7FFFFFFF)
+
+
+def resize_fits(scale_h, scale_w):
+    """whether resize_crops takes a call whose largest per-axis scales are ``scale_h`` = (box h, resized h) and ``scale_w``"""
+    return bool(query(Q_RESIZE_FITS, _scale_fx(scale_h), _scale_fx(scale_w)))
+
+
+def resize_crops(src, images, params, S, scale_h, scale_w, out=None):
+    """box -> resize -> S x S window -> flip -> ToTensor + Normalize for the n crops described by ``params`` (int32 [n, 16]; the
+    evaluation mode of esvit_aug_crops, include/esvit_hip.h) from packed images as aug_crops reads them.  ``scale_h`` /
+    ``scale_w``: the (box side, resized side) pair of the crop with the largest ratio on that axis.  Returns out fp32 [n, 3, S, S]."""
+    assert src.is_cuda and src.dtype == torch.uint8 and src.is_contiguous()
+    assert images.is_cuda and images.dtype == torch.int64 and images.is_contiguous() and images.shape[-1] == 3
+    assert params.is_cuda and params.dtype == torch.int32 and params.is_contiguous() and params.shape[-1] == RESIZE_PARAM_INTS
+    n = params.shape[0]
+    if out is None:
+        out = torch.empty((n, 3, S, S), dtype=torch.float32, device=src.device)
+    assert out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.numel() >= n * 3 * S * S
+    check(lib.esvit_aug_crops(_p(src), _p(images), _p(params), n, S | AUG_EVAL, _scale_fx(scale_h), _scale_fx(scale_w), None, _p(out), _stream()),
+          "resize_crops")
+    return out
 
 
 # ------------------------------------------------------------------------------------------------

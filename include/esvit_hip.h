@@ -47,6 +47,8 @@ const char* esvit_last_error(void);
  *   ESVIT_Q_MLP_FUSED (dtype, C)               bit 0: esvit_mlp_fused_fwd exists (bf16, C in {96, 128, 192, 256, 384}), bit 1: esvit_mlp_fused_bwd exists (bf16, C in {96, 128, 192, 256})
  *   ESVIT_Q_AUG_MAX_BOX (S)                    largest crop-box side esvit_aug_crops resizes to S x S
  *   ESVIT_Q_JPEG_WORKSPACE (n_blocks, plane_bytes, n_lanes | n_segments << 32)  bytes of the esvit_jpeg_decode workspace
+ *   ESVIT_Q_RESIZE_FITS (scale_h, scale_w)     1 if esvit_aug_crops' evaluation mode takes a call whose largest per-axis scales
+ *                                              are scale_h, scale_w (units of 1 / ESVIT_RESIZE_SCALE_ONE), else 0
  * Unknown `what` returns ESVIT_ERR_ARG. */
 #define ESVIT_Q_ATTN_FRAG_ELEMS 1
 #define ESVIT_Q_ATTN_LSE_ELEMS 2
@@ -59,6 +61,7 @@ const char* esvit_last_error(void);
 #define ESVIT_Q_MLP_FUSED 9
 #define ESVIT_Q_AUG_MAX_BOX 10
 #define ESVIT_Q_JPEG_WORKSPACE 11
+#define ESVIT_Q_RESIZE_FITS 12
 int64_t esvit_query(int what, int64_t a, int64_t b, int64_t c);
 
 /* ---- host-side integer index maps (bit-exact vs reference) -------------
@@ -465,6 +468,24 @@ int esvit_bn_bwd_coeffs(const float* red, float n, const float* gamma, const flo
 #define ESVIT_AUG_PARAM_INTS 24
 int esvit_aug_crops(const uint8_t* src, const int64_t* images, const int32_t* params, int n, int S, int max_h, int max_w,
                     uint8_t* planes, float* out, esvit_stream_t stream);
+
+/* Evaluation mode (S | ESVIT_AUG_EVAL, planes = NULL): the transforms of eval_knn.py:48-53 / eval_linear.py:50-61 for n crops
+ * of one output size S, bit-exact with Pillow, in one launch and without scratch (the flag without planes == NULL is ESVIT_ERR_ARG):
+ * img.crop(box).resize((rw, rh), filter) -> the S x S window at (off_y, off_x) of it -> horizontal flip -> ToTensor -> Normalize.
+ * Resize(256, BICUBIC) -> CenterCrop(224) is box = the image, (rh, rw) = the resized size, the window offset the centre crop's;
+ * RandomResizedCrop(224) -> RandomHorizontalFlip is box = the drawn box, rh = rw = S, offset 0, BILINEAR.
+ *   params  int32 [n, ESVIT_RESIZE_PARAM_INTS], one row per crop:
+ *           0 image row | 1 top | 2 left | 3 h | 4 w  (box, inside the image) | 5 flip | 6 rh | 7 rw  (size the box is resized to)
+ *           8 off_y | 9 off_x  (window, off + S <= resized size) | 10 filter (ESVIT_FILTER_*) | 11.. reserved (0)
+ *   n       <= 65535;  S  <= 4096
+ *   max_h, max_w  the largest h / rh and w / rw of the n crops in units of 1 / ESVIT_RESIZE_SCALE_ONE, rounded up (they size the
+ *           LDS; ESVIT_ERR_UNSUPPORTED, and no launch, when esvit_query(ESVIT_Q_RESIZE_FITS) says no)
+ *   out     fp32 [n, 3, S, S] */
+#define ESVIT_AUG_EVAL 0x40000000
+#define ESVIT_RESIZE_PARAM_INTS 16
+#define ESVIT_RESIZE_SCALE_ONE 65536
+#define ESVIT_FILTER_BICUBIC 0
+#define ESVIT_FILTER_BILINEAR 1
 
 /* ---- JPEG decoder (the input side of the crop producer) ------------------
  * The reference decodes every file with Image.open(f).convert('RGB') (datasets/build.py ImageFolder, the zip and TSV readers).
