@@ -828,6 +828,12 @@ int esvit_big_attn_bwd(int dtype, const void* qkv, const float* qkv_bias, const 
 int esvit_big_relpos_bias_bwd(const float* dbias_ws, int parts, const int64_t* index, int N, int nH, int table_rows, float* dtable,
                               int accumulate, hipStream_t stream);
 
+// the sliding-chunk mode (chunk_attn.hip)
+int esvit_chunk_attn_fwd(int dtype, const void* qkv, const int32_t* chunk_table, int L, int ws, float* scratch, int nx, int nB, int ny, int nH,
+                         int hd, float scale, void* out, float* lse, float* attn_out, hipStream_t stream);
+int esvit_chunk_attn_bwd(int dtype, const void* qkv, const int32_t* chunk_table, int L, const void* dout, const void* fwd_out, const float* lse,
+                         int ws, float* scratch, int nx, int nB, int ny, int nH, int hd, float scale, void* dqkv, hipStream_t stream);
+
 // answers of esvit_query (lib.cpp)
 int esvit_i_attn_frag_elems(int N) { return N <= NP ? FRAG_ELEMS : (N <= esvit_big_npb() ? esvit_big_frag_elems() : -1); }
 int esvit_i_attn_lse_elems(int N) { return N <= NP ? 0 : esvit_big_npb(); }
@@ -851,6 +857,9 @@ extern "C" int esvit_window_attn_fwd(int dtype, const void* qkv, const float* qk
                                      const float* rel_table, int ws, float* bias_frag_ws, const int32_t* region_ids, int nW, int nB, int N,
                                      int nH, int hd, float scale, void* out, float* lse, float* attn_out, esvit_stream_t s_) {
     STREAM(s_);
+    if (ws > 0 && (ws & ESVIT_ATTN_SLIDING_CHUNK))  // Vision Longformer's sliding-chunk attention: nW x N is the token grid (esvit_hip.h)
+        return esvit_chunk_attn_fwd(dtype, qkv, win2tok, L, ws & ~ESVIT_ATTN_SLIDING_CHUNK, bias_frag_ws, nW, nB, N, nH, hd, scale, out, lse, attn_out,
+                                    stream);
     // (N < ws * ws: a "window" of the first N positions of a ws x ws grid -- the 197 / 37 tokens of a ViT crop with a zero table)
     ESVIT_CHECK_ARG(qkv && qkv_bias && win2tok && out && nB > 0 && nW > 0 && nH > 0 && L > 0 && ws > 0 && N > 0 &&
                         (N == ws * ws || (N < ws * ws && N <= esvit_big_npb())),
@@ -896,6 +905,9 @@ extern "C" int esvit_window_attn_bwd(int dtype, const void* qkv, const float* qk
                                      const int32_t* region_ids, int nW, int nB, int N, int nH, int hd, float scale, void* dqkv,
                                      float* dbias_ws, float* dpad_ws, esvit_stream_t s_) {
     STREAM(s_);
+    if (ws > 0 && (ws & ESVIT_ATTN_SLIDING_CHUNK))
+        return esvit_chunk_attn_bwd(dtype, qkv, win2tok, L, dout, fwd_out, lse, ws & ~ESVIT_ATTN_SLIDING_CHUNK, bias_frag_ws, nW, nB, N, nH, hd, scale,
+                                    dqkv, stream);
     ESVIT_CHECK_ARG(qkv && qkv_bias && win2tok && dout && dqkv && dbias_ws && dpad_ws && nB > 0 && nW > 0 && nH > 0 && L > 0 &&
                         ws > 0 && N > 0 && (N == ws * ws || (N < ws * ws && N <= esvit_big_npb())),
                     "esvit_window_attn_bwd: bad args");

@@ -1548,6 +1548,20 @@ def vit_block_attention(x, nH, prm_list):
 # plus its own and the eight adjacent w x w chunks (`chunk`, esvit_softmax_rows_chunked_fwd).  rpe off (the ape = 1 default of
 # the reference's yaml files): no bias tables.
 # ------------------------------------------------------------------------------------------------
+def _chunk_fused(o, chunk, dtype, hd):
+    """does this sliding-chunk stage take the fused kernels (ops.sliding_chunk_attn_fwd)?  The model asks for them with a fourth tuple
+    entry, the chunk side (MsViT._stage under CHUNK_ATTENTION = "fused"); an ops module without the entry (the CPU restatement,
+    oracle/ops_ref.py) or an unsupported shape (fp32 parity mode, other head dims) keeps the dense route."""
+    if not isinstance(chunk, tuple) or len(chunk) < 4:
+        return False
+    sup = getattr(o, "sliding_chunk_attn_supported", None)
+    return sup is not None and bool(sup(dtype, hd, chunk[3], chunk[1]))
+
+
+def _chunk3(chunk):
+    return chunk[:3] if isinstance(chunk, tuple) else chunk
+
+
 def _vil_block_forward(x, nH, dp, chunk, prm, wts, save):
     o = ops_module()
     (g1, b1, bq, bkv, bproj, g2, b2, bfc1, bfc2) = prm
@@ -1564,8 +1578,12 @@ def _vil_block_forward(x, nH, dp, chunk, prm, wts, save):
         bqkv = torch.cat((bq.detach(), bkv.detach()))
     if chunk is None:
         ao, att = vit_attention(o, qkv, bqkv, nB, N, nH, scale, save)
+    elif _chunk_fused(o, chunk, qkv.dtype, C // nH):
+        # fused sliding-chunk kernels: saved = (qkv, out, lse); `ao` rides in `saved` below, so only (qkv, lse) are extra
+        ao, (_, _, lse) = o.sliding_chunk_attn_fwd(qkv, nB, N, nH, scale, chunk[:3])
+        att = (qkv, lse) if save else ()
     else:
-        ao, att = o.vit_attn_fwd(qkv, nB, N, nH, scale, chunk=chunk)
+        ao, att = o.vit_attn_fwd(qkv, nB, N, nH, scale, chunk=_chunk3(chunk))
         att = att if save else ()
     x1 = o.linear_fwd(ao, Wproj, bproj, residual=x2d, rowscale=dp1, rows_per_sample=N, out_f32=True)
     h, _, mean2, rstd2 = o.layernorm_fwd(x1, g2, b2, LN_EPS)
@@ -1625,8 +1643,10 @@ class VilBlockFn(torch.autograd.Function):
         gx1, dyw, dg2, db2 = o.layernorm_bwd_cast(dh, x1, mean2, rstd2, g2, g_in=gy, rowscale=dp1, rows_per_sample=N, gb_out=sink2)
         dWproj, dbproj = _side_run(lambda: _wgrad(dyw, ao, Wproj_p, want_bias=True, bias_param=bproj_p), dyw, ao)
         dao = o.linear_dgrad(dyw, Wproj)
-        if ctx.chunk is not None:
-            dqkv = o.vit_attn_bwd(dao, att, nB, N, nH, scale, chunk=ctx.chunk)
+        if ctx.chunk is not None and _chunk_fused(o, ctx.chunk, ao.dtype, C // nH):
+            dqkv = o.sliding_chunk_attn_bwd(dao, (att[0], ao, att[1]), nB, N, nH, scale, ctx.chunk[:3])
+        elif ctx.chunk is not None:
+            dqkv = o.vit_attn_bwd(dao, att, nB, N, nH, scale, chunk=_chunk3(ctx.chunk))
         else:
             dqkv = vit_attention_bwd(o, dao, att, bqkv, nB, N, nH, scale)
         if split:

@@ -19,6 +19,7 @@ Built: what the reference's yaml files select -- rpe off (ape = 1), SHARE_W, ATT
 no pooled keys, no SE.  Everything else raises NotImplementedError.
 """
 import math
+import os
 from functools import partial
 
 import numpy as np
@@ -42,6 +43,16 @@ _BICUBIC = {}
 #             reference fixtures under tests/golden/ were produced on the CPU, so the tests that compare against them select this.
 # Real size changes (other crop resolutions) are resampled the same way in both modes.
 SAME_SIZE_RESAMPLING = "device"
+
+# Which kernels run the sliding-chunk stages (both are correct routes of the same attention):
+#   "dense"  batched MFMA score GEMMs over all token pairs + a row softmax restricted to the chunk neighbourhood: a [B nH, N, N] score
+#            tensor in the forward and a second one in the backward.  The default.
+#   "fused"  csrc/chunk_attn.hip: per-chunk kernels that keep the scores on the chip, linear in N in time and memory (bf16, head_dim
+#            32 / 48 / 64, 7 x 7 chunks; any other shape, and the fp32 parity mode, keeps the dense route).
+# Initialised from the environment variable ESVIT_VIL_CHUNK_ATTN so that a benchmark run can select either.
+CHUNK_ATTENTION = os.environ.get("ESVIT_VIL_CHUNK_ATTN", "dense")
+if CHUNK_ATTENTION not in ("dense", "fused"):
+    raise ValueError("ESVIT_VIL_CHUNK_ATTN: dense or fused, not %r" % CHUNK_ATTENTION)
 
 
 def _bicubic_matrix(n_in, scale_factor, device):
@@ -300,6 +311,8 @@ class MsViT(nn.Module):
         sparse = isinstance(layer[1].attn, Long2DSCSelfAttention)
         # (chunk table, global tokens, tokens per chunk row): the local tokens are ordered (x, y), i.e. chunk row by chunk row
         chunk = (self._chunk_table(cfg['g'], nx, ny, cfg['f'], x.device), cfg['g'], cfg['f'] * ny) if sparse else None
+        if sparse and CHUNK_ATTENTION == "fused":
+            chunk = chunk + (cfg['f'],)  # (a fourth entry, the chunk side, asks functional.vil_block for the fused kernels)
         for b in range(1, len(layer), 2):
             ab, mb = layer[b], layer[b + 1]
             dp = None

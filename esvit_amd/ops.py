@@ -83,7 +83,7 @@ def relative_position_index(ws):
 
 # esvit_query questions (include/esvit_hip.h)
 (Q_ATTN_FRAG_ELEMS, Q_ATTN_LSE_ELEMS, Q_ATTN_BWD_PARTS, Q_ATTN_BWD_PAD_ROWS, Q_LN_BWD_BLOCKS, Q_COLSUM_BLOCKS, Q_COL_REDUCE_BLOCKS,
- Q_UPDATE_CHUNK_ELEMS, Q_MLP_FUSED, Q_AUG_MAX_BOX, Q_JPEG_WORKSPACE, Q_RESIZE_FITS) = range(1, 13)
+ Q_UPDATE_CHUNK_ELEMS, Q_MLP_FUSED, Q_AUG_MAX_BOX, Q_JPEG_WORKSPACE, Q_RESIZE_FITS, Q_CHUNK_ATTN_WS) = range(1, 14)
 
 
 def query(what, a=0, b=0, c=0):
@@ -1150,3 +1150,55 @@ def vit_attn_bwd(dout, saved, B, N, nH, scale, chunk=None):
     _bmm(dp, qkvh[1], Np, hd, Np, b_kstrided=1, out=dqkvh[0])                  # dq = dS k
     _bmm(dp, qkvh[0], Np, hd, Np, a_kstrided=1, b_kstrided=1, out=dqkvh[1])   # dk = dS^T q
     return heads_merge(dqkvh.view(3, B, nH, Np, hd), N)
+
+
+# ---- fused sliding-chunk attention (csrc/chunk_attn.hip): the scores stay on the chip, nothing grows with N^2 --------------------
+ATTN_SLIDING_CHUNK = 0x40000000  # ESVIT_ATTN_SLIDING_CHUNK: OR'd into ws, selects the sliding-chunk mode of esvit_window_attn_fwd / _bwd
+CHUNK_W = 7                      # the chunk side the kernels are built for (every yaml of the reference)
+CHUNK_MAX_NGLO = 7
+
+
+def sliding_chunk_attn_supported(dtype, hd, w, nglo):
+    """the fused sliding-chunk route exists for this shape: bf16 (the fp32 parity mode keeps the dense route), head_dim 32 / 48 / 64,
+    7 x 7 chunks, at most 7 global tokens"""
+    return dtype == torch.bfloat16 and hd in (32, 48, 64) and w == CHUNK_W and 0 <= nglo <= CHUNK_MAX_NGLO
+
+
+def _chunk_grid(chunk, N):
+    """(table, nglo, tokens per chunk row[, w]) -> (table, nglo, nx, ny, w)"""
+    tab, nglo, rowtok = chunk[:3]
+    w = chunk[3] if len(chunk) > 3 else CHUNK_W
+    assert rowtok > 0 and rowtok % w == 0, "sliding-chunk attention needs the (table, nglo, tokens per chunk row) form"
+    ny = rowtok // w
+    nx = (N - nglo) // ny
+    assert nglo + nx * ny == N and tab.dtype == torch.int32 and tab.numel() == N and tab.is_contiguous()
+    return tab, int(nglo), nx, ny, int(w)
+
+
+def sliding_chunk_attn_fwd(qkv, B, N, nH, scale, chunk):
+    """Vision Longformer's sliding-chunk attention in one set of fused kernels: qkv [B * N, 3C] (tokens [globals | (x, y) row-major])
+    -> (out [B * N, C], saved = (qkv, out, lse fp32 [B, nH, N])).  chunk = (table, nglo, tokens per chunk row) as MsViT._stage builds it."""
+    qkv = _actc(qkv)
+    tab, nglo, nx, ny, w = _chunk_grid(chunk, N)
+    Cc = qkv.shape[1] // 3
+    assert qkv.shape[0] == B * N
+    out = torch.empty((B * N, Cc), dtype=qkv.dtype, device=qkv.device)
+    lse = torch.empty((B, nH, N), dtype=torch.float32, device=qkv.device)
+    ws = workspace(query(Q_CHUNK_ATTN_WS, B * nH, N, 0), qkv.device, slot=3)
+    check(lib.esvit_window_attn_fwd(_code(qkv.dtype), _p(qkv), None, _p(tab), N, None, w | ATTN_SLIDING_CHUNK, _p(ws), None, nx, B, ny, nH, Cc // nH,
+                                    float(scale), _p(out), _p(lse), None, _stream()), "window_attn_fwd(sliding chunk)")
+    return out, (qkv, out, lse)
+
+
+def sliding_chunk_attn_bwd(dout, saved, B, N, nH, scale, chunk):
+    """gradient of sliding_chunk_attn_fwd with respect to qkv: dout [B * N, C] -> dqkv [B * N, 3C]"""
+    qkv, out, lse = saved
+    dout = _actc(dout)
+    tab, nglo, nx, ny, w = _chunk_grid(chunk, N)
+    Cc = qkv.shape[1] // 3
+    assert dout.shape == out.shape and dout.dtype == qkv.dtype
+    dqkv = torch.empty_like(qkv)
+    ws = workspace(query(Q_CHUNK_ATTN_WS, B * nH, N, 1), qkv.device, slot=3)
+    check(lib.esvit_window_attn_bwd(_code(qkv.dtype), _p(qkv), None, _p(tab), N, _p(dout), _p(out), _p(lse), None, w | ATTN_SLIDING_CHUNK, _p(ws), None,
+                                    nx, B, ny, nH, Cc // nH, float(scale), _p(dqkv), None, None, _stream()), "window_attn_bwd(sliding chunk)")
+    return dqkv

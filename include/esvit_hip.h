@@ -49,6 +49,8 @@ const char* esvit_last_error(void);
  *   ESVIT_Q_JPEG_WORKSPACE (n_blocks, plane_bytes, n_lanes | n_segments << 32)  bytes of the esvit_jpeg_decode workspace
  *   ESVIT_Q_RESIZE_FITS (scale_h, scale_w)     1 if esvit_aug_crops' evaluation mode takes a call whose largest per-axis scales
  *                                              are scale_h, scale_w (units of 1 / ESVIT_RESIZE_SCALE_ONE), else 0
+ *   ESVIT_Q_CHUNK_ATTN_WS (nB*nH, L, backward) floats of the scratch the sliding-chunk mode of esvit_window_attn_fwd (backward = 0) /
+ *                                              esvit_window_attn_bwd (backward = 1) takes through bias_frag_ws
  * Unknown `what` returns ESVIT_ERR_ARG. */
 #define ESVIT_Q_ATTN_FRAG_ELEMS 1
 #define ESVIT_Q_ATTN_LSE_ELEMS 2
@@ -62,6 +64,7 @@ const char* esvit_last_error(void);
 #define ESVIT_Q_AUG_MAX_BOX 10
 #define ESVIT_Q_JPEG_WORKSPACE 11
 #define ESVIT_Q_RESIZE_FITS 12
+#define ESVIT_Q_CHUNK_ATTN_WS 13
 int64_t esvit_query(int what, int64_t a, int64_t b, int64_t c);
 
 /* ---- host-side integer index maps (bit-exact vs reference) -------------
@@ -301,7 +304,22 @@ int esvit_attn_branch_fwd(int dtype, const float* x, const float* gamma, const f
  * attn_out (optional, fp32 [nB*nW,nH,N,N]) receives the softmax (swin_transformer.py:146,152). 
  * N <= 64: head_dim 32 or 64.  64 < N <= 224: head_dim 32, or 64 in bf16 -- the head_dim-64 instances (whole ViT crops: one window per
  * image, N < ws * ws allowed, zero table) leave dbias_ws unwritten.
+ *
+ * Sliding-chunk mode (ws | ESVIT_ATTN_SLIDING_CHUNK; chunk_attn.hip): Vision Longformer's attention (layers/slidingchunk_2d.py
+ * mode 0, layers/longformer2d.py) over one token grid per image, fused -- no tensor grows with L^2.  The tokens of an image are
+ * [nglo globals | an nx x ny grid, row-major]; a global token sees and is seen by every token, a grid token also sees the tokens of
+ * its own and the eight adjacent ws x ws chunks.  The arguments mean, in this mode:
+ *   ws           7 | ESVIT_ATTN_SLIDING_CHUNK (other chunk sides: ESVIT_ERR_ARG)
+ *   L            tokens per image, nglo + nx * ny;  nW = nx (grid rows),  N = ny (grid columns);  nglo = L - nW * N <= 7
+ *   win2tok      int32 [L], the chunk table of that grid: -1 for a global token, else chunk row << 16 | chunk column (the kernels use
+ *                the closed form the table spells out, csrc/chunk_geom.h)
+ *   bias_frag_ws fp32 scratch of esvit_query(ESVIT_Q_CHUNK_ATTN_WS, nB * nH, L, 0 forward | 1 backward) floats
+ *   lse          fp32 [nB, nH, L], written by the forward and read by the backward (required), as fwd_out is
+ *   hd           32, 48 or 64;  dtype bf16 only (ESVIT_ERR_ARG otherwise, before any launch: the fp32 parity mode keeps the dense route)
+ *   qkv_bias, rel_table, region_ids, attn_out, dbias_ws, dpad_ws: not used, pass NULL
+ * Every row of out / dqkv is written; no atomics: two launches give identical bits.
  */
+#define ESVIT_ATTN_SLIDING_CHUNK 0x40000000
 int esvit_window_attn_fwd(int dtype, const void* qkv, const float* qkv_bias, const int32_t* win2tok, int L,
                           const float* rel_table, int ws, float* bias_frag_ws, const int32_t* region_ids, int nW, int nB,
                           int N, int nH, int hd, float scale, void* out, float* lse, float* attn_out,
