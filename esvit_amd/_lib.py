@@ -16,6 +16,16 @@ GEMM_AUTO, GEMM_REGSTAGE, GEMM_DMA4, GEMM_DMA8, GEMM_DMA4W, GEMM_P8 = 0, 1, 2, 3
 vp, i32, i64, f32 = C.c_void_p, C.c_int32, C.c_int64, C.c_float
 
 
+class GemmTopk(C.Structure):
+    """esvit_gemm_topk: the k-nearest-neighbour epilogue of esvit_gemm (GemmDesc.topk)"""
+    _fields_ = [
+        ("k", i32), ("merge", i32),
+        ("vals", vp), ("idx", vp),
+        ("idx_base", i64),
+        ("workspace", vp), ("workspace_bytes", i64),
+    ]
+
+
 class GemmDesc(C.Structure):
     _fields_ = [
         ("A", vp), ("B", vp), ("C", vp),
@@ -34,6 +44,7 @@ class GemmDesc(C.Structure):
         ("kernel", i32),
         ("rowstat", vp), ("rowstat_center", vp), ("rowstat_scale", f32),
         ("colstat", vp),
+        ("topk", C.POINTER(GemmTopk)),
     ]
 
 

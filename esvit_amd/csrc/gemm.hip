@@ -10,7 +10,14 @@
 //   ESVIT_GEMM_P8        the 256 x 256 eight-phase loop (gemm_p8.hip): counted DMA waits that never drain the queue, staggered wave
 //                        halves, accumulators in AccVGPRs -- K % 64 == 0, no row map; row statistics on whole tiles.
 // The choice is a pure function of the descriptor (esvit_gemm_select).
+// esvit_gemm_desc::topk (the fused k-nearest-neighbour scan, knn_topk.hip) is dispatched ahead of all of this: it runs the register-staged
+// fp32 loop inside a kernel of its own.
 #include "gemm_kernels.h"
+
+// esvit_gemm_desc::topk: the k-nearest-neighbour epilogue (knn_topk.hip)
+int esvit_knn_topk_check(int dtype, const esvit_gemm_desc& d, bool with_buffers);
+int esvit_knn_topk_launch(int dtype, const esvit_gemm_desc& d, hipStream_t stream);
+void esvit_knn_topk_tile(int* bm, int* bn, int* slots);
 
 namespace {
 
@@ -260,6 +267,12 @@ int run_astat(const esvit_gemm_desc& d, hipStream_t stream) {
 extern "C" int esvit_gemm_select(int dtype, const esvit_gemm_desc* dp, int* tile_m, int* tile_n, int* resident_slots) {
     ESVIT_CHECK_ARG(dp != nullptr, "esvit_gemm_select: null descriptor");
     esvit_gemm_desc d = *dp;
+    if (d.topk) {  // the fused k-NN scan: one loop, one tile
+        const int rc = esvit_knn_topk_check(dtype, d, false);
+        if (rc != ESVIT_OK) return rc;
+        esvit_knn_topk_tile(tile_m, tile_n, resident_slots);
+        return ESVIT_GEMM_REGSTAGE;
+    }
     if (d.batch < 1) d.batch = 1;
     ESVIT_CHECK_ARG(d.M > 0 && d.N > 0 && d.K > 0, "esvit_gemm_select: bad shape M=%d N=%d K=%d", d.M, d.N, d.K);
     {
@@ -277,6 +290,7 @@ extern "C" int esvit_gemm(int dtype, const esvit_gemm_desc* dp, esvit_stream_t s
     hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
     ESVIT_CHECK_ARG(dp != nullptr, "esvit_gemm: null descriptor");
     esvit_gemm_desc d = *dp;
+    if (d.topk) return esvit_knn_topk_launch(dtype, d, stream);
     const int rc = validate(dtype, d);
     if (rc != ESVIT_OK) return rc;
 #ifdef ESVIT_ASTAT

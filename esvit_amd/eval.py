@@ -8,6 +8,11 @@ rank 0's feature matrix.  ``knn_classifier`` (eval_knn.py:193-232) scores every 
 similarity product -- the only heavy step: 50k x 1.28M x C for ImageNet -- is this library's fp32 MFMA GEMM reading the
 train matrix in its stored [N_train, C] layout (no transposed copy); top-k, the one-hot vote and the ranking are
 PyTorch indexing ops with the reference's tie behaviour.
+
+``knn_classifier_multi`` is the fused route: ONE pass of ``ops.knn_topk`` at ``max(ks)`` -- similarity and
+selection in one kernel, the [chunk, N_train] block never stored -- and a deterministic vote for every k from the prefix of the
+sorted lists.  ``knn_topk_streamed`` scores a train matrix that arrives in pieces (host-resident features).  ``KNN_ROUTE``
+(``ESVIT_KNN_ROUTE``) = "fused" sends ``knn_classifier`` through it; the default "gemm" is the per-k dense route.
 """
 import os
 
@@ -15,6 +20,10 @@ import torch
 import torch.distributed as dist
 
 from . import ops
+
+
+# which route knn_classifier takes: "gemm" (dense similarity block + torch.topk, once per k) or "fused" (knn_classifier_multi)
+KNN_ROUTE = os.environ.get("ESVIT_KNN_ROUTE", "gemm")
 
 
 def _dist_on():
@@ -78,6 +87,10 @@ def extract_features(model, data_loader, use_cuda=True):
 def knn_classifier(train_features, train_labels, test_features, test_labels, k, T, num_classes=1000, num_chunks=100):
     """-> (top1 %, top5 %).  Features are L2-normalised fp32 rows ([N_train, C], [N_test, C]) on the GPU.  The test set is
     scored in ``num_chunks`` chunks exactly as the reference does (eval_knn.py:197-198)."""
+    if KNN_ROUTE == "fused":
+        return knn_classifier_multi(train_features, train_labels, test_features, test_labels, (k,), T, num_classes=num_classes, num_chunks=num_chunks)[k]
+    if KNN_ROUTE != "gemm":
+        raise ValueError("esvit_amd.eval.KNN_ROUTE is %r: 'gemm' or 'fused'" % (KNN_ROUTE,))
     train_features = train_features.float().contiguous()
     test_features = test_features.float().contiguous()
     train_labels, test_labels = train_labels.to(train_features.device), test_labels.to(train_features.device)
@@ -101,6 +114,109 @@ def knn_classifier(train_features, train_labels, test_features, test_labels, k, 
         top5 += correct.narrow(1, 0, min(5, num_classes)).sum().item()
         total += bs
     return top1 * 100.0 / total, top5 * 100.0 / total
+
+
+# ------------------------------------------------------------------------------------------------------------------------
+# the fused route: one top-k pass at max(ks), every k voted from its prefix
+# ------------------------------------------------------------------------------------------------------------------------
+def _topk_host(test, train, k, out=None, idx_base=0):
+    """torch restatement of ops.knn_topk with its two orders (host tensors, or features the kernel does not take): larger
+    similarity first, on equal similarities the smaller train row first (a STABLE descending sort over columns in row order).
+    The similarity is accumulated in fp64 and rounded once, so that a column's value does not depend on the piece of the train
+    matrix it arrived in -- what the kernel's fixed summation order gives on the GPU."""
+    sim = (test.double() @ train.double().t()).float()
+    cols = torch.arange(idx_base, idx_base + train.shape[0], dtype=torch.int32, device=sim.device).view(1, -1).expand(sim.shape[0], -1)
+    if out is not None:  # the incoming lists hold earlier (smaller) row numbers: in front, so that the stable sort keeps them first on ties
+        sim, cols = torch.cat([out[0], sim], 1), torch.cat([out[1], cols], 1)
+    if k > sim.shape[1]:
+        raise ValueError("knn_topk: k=%d exceeds the %d train rows" % (k, sim.shape[1]))
+    vals, order = torch.sort(sim, dim=1, descending=True, stable=True)
+    vals, idx = vals[:, :k].contiguous(), torch.gather(cols, 1, order[:, :k]).contiguous()
+    if out is not None:
+        out[0].copy_(vals)
+        out[1].copy_(idx)
+        return out
+    return vals, idx
+
+
+def _knn_topk(test, train, k, out=None, idx_base=0):
+    if ops.knn_topk_supported(test, train):
+        return ops.knn_topk(test.contiguous(), train.contiguous(), k, out=out, idx_base=idx_base)
+    return _topk_host(test.float(), train.float(), k, out=out, idx_base=idx_base)
+
+
+@torch.no_grad()
+def knn_topk_streamed(test, train_chunks, k):
+    """-> (vals [N_test, k], idx int32 [N_test, k]) of ``test`` against the concatenation of ``train_chunks`` (an iterable of
+    [n_i, C] pieces, which may be host tensors: each is uploaded to the device of ``test``, scored and merged into the running
+    lists, so the whole train matrix never has to be resident).  Equal, bit for bit, to the one-shot call on the concatenation.
+    The first piece must hold at least k rows."""
+    test = test.float().contiguous()
+    out, base = None, 0
+    for piece in train_chunks:
+        piece = piece.to(test.device, non_blocking=True).float().contiguous()
+        if piece.shape[0] == 0:
+            continue
+        if out is None and k > piece.shape[0]:
+            raise ValueError("knn_topk_streamed: the first piece holds %d rows, fewer than k=%d" % (piece.shape[0], k))
+        out = _knn_topk(test, piece, k, out=out, idx_base=base)
+        base += piece.shape[0]
+    if out is None:
+        raise ValueError("knn_topk_streamed: no train rows")
+    return out
+
+
+def _vote(vals, labels, targets, ks, T, num_classes):
+    """-> {k: (top-1 hits, top-5 hits)} of one chunk of test rows.  Class c collects exp(sim / T) of the neighbours labelled c, added
+    one neighbour at a time in neighbour order (fp32; gather -> add -> scatter with one index per row: no atomics, deterministic),
+    so the votes after k neighbours serve k.  The target's rank: classes with a strictly larger vote, plus classes with an equal
+    vote and a smaller id."""
+    rows = vals.shape[0]
+    weights = vals.clone().div_(T).exp_()
+    probs = torch.zeros(rows, num_classes, device=vals.device)
+    class_id = torch.arange(num_classes, device=vals.device).view(1, -1)
+    tcol = targets.view(-1, 1)
+    hits, want = {}, set(ks)
+    for j in range(max(ks)):
+        lab = labels[:, j:j + 1]
+        probs.scatter_(1, lab, probs.gather(1, lab) + weights[:, j:j + 1])
+        if j + 1 in want:
+            mine = probs.gather(1, tcol)
+            rank = (probs > mine).sum(1) + ((probs == mine) & (class_id < tcol)).sum(1)
+            hits[j + 1] = ((rank == 0).sum().item(), (rank < min(5, num_classes)).sum().item())
+    return hits
+
+
+@torch.no_grad()
+def knn_classifier_multi(train_features, train_labels, test_features, test_labels, ks, T, num_classes=1000, num_chunks=100):
+    """-> {k: (top1 %, top5 %)} for every k of ``ks`` from ONE neighbour search at max(ks): with a total order (larger similarity
+    first, then the smaller train row) the k nearest are the first k of the max(ks) nearest.  On the GPU (fp32 features, C % 4 == 0)
+    the search is ops.knn_topk; on host tensors its torch restatement.  The vote is chunked so that its scratch stays within the
+    reference's own (N_test / num_chunks) * k * num_classes floats (eval_knn.py:199)."""
+    ks = tuple(int(k) for k in ks)
+    kmax = max(ks)
+    if min(ks) < 1:
+        raise ValueError("knn_classifier_multi: k must be positive")
+    if kmax > train_features.shape[0]:
+        raise ValueError("knn_classifier_multi: k=%d exceeds the %d train rows" % (kmax, train_features.shape[0]))
+    train_features = train_features.float().contiguous()
+    test_features = test_features.float().contiguous()
+    dev = train_features.device
+    train_labels, test_labels = train_labels.to(dev), test_labels.to(dev)
+    num_test = test_labels.shape[0]
+    if test_features.is_cuda and kmax > ops.KNN_MAX_K:  # (beyond the kernel's k: the restatement)
+        vals, idx = _topk_host(test_features, train_features, kmax)
+    else:
+        vals, idx = _knn_topk(test_features, train_features, kmax)
+    labels = train_labels[idx.long()]
+    rows_per_vote = max(1, num_test // num_chunks) * kmax  # rows * num_classes floats <= the reference's rows * k * num_classes
+    top = {k: [0, 0] for k in ks}
+    for i in range(0, num_test, rows_per_vote):
+        sl = slice(i, min(i + rows_per_vote, num_test))
+        for k, (h1, h5) in _vote(vals[sl], labels[sl], test_labels[sl], ks, T, num_classes).items():
+            top[k][0] += h1
+            top[k][1] += h5
+    return {k: (top[k][0] * 100.0 / num_test, top[k][1] * 100.0 / num_test) for k in ks}
 
 
 # ------------------------------------------------------------------------------------------------------------------------

@@ -10,7 +10,7 @@ import os
 import numpy as np
 import torch
 
-from ._lib import BF16, EPI_GELU, EPI_GELU_BWD, EPI_NONE, EPI_QGELU, EPI_QGELU_BWD, F32, GEMM_AUTO, GEMM_DMA8, GEMM_P8, GemmDesc, check, lib
+from ._lib import BF16, EPI_GELU, EPI_GELU_BWD, EPI_NONE, EPI_QGELU, EPI_QGELU_BWD, F32, GEMM_AUTO, GEMM_DMA8, GEMM_P8, GemmDesc, GemmTopk, check, lib
 
 _ACT_DTYPE = torch.bfloat16
 
@@ -83,7 +83,7 @@ def relative_position_index(ws):
 
 # esvit_query questions (include/esvit_hip.h)
 (Q_ATTN_FRAG_ELEMS, Q_ATTN_LSE_ELEMS, Q_ATTN_BWD_PARTS, Q_ATTN_BWD_PAD_ROWS, Q_LN_BWD_BLOCKS, Q_COLSUM_BLOCKS, Q_COL_REDUCE_BLOCKS,
- Q_UPDATE_CHUNK_ELEMS, Q_MLP_FUSED, Q_AUG_MAX_BOX, Q_JPEG_WORKSPACE, Q_RESIZE_FITS, Q_CHUNK_ATTN_WS) = range(1, 14)
+ Q_UPDATE_CHUNK_ELEMS, Q_MLP_FUSED, Q_AUG_MAX_BOX, Q_JPEG_WORKSPACE, Q_RESIZE_FITS, Q_CHUNK_ATTN_WS, Q_TOPK_WS) = range(1, 15)
 
 
 def query(what, a=0, b=0, c=0):
@@ -254,6 +254,49 @@ def linear_fwd(x, w, bias=None, *, gelu=False, want_preact=False, residual=None,
           rowscale=rowscale, rows_per_sample=rows_per_sample, aux=pre, ldaux=N,
           epilogue=(EPI_QGELU if quick else EPI_GELU) if gelu else EPI_NONE, out_f32=out_f32)
     return (y, pre) if gelu and want_preact else y
+
+
+KNN_MAX_K = 256  # the largest k of esvit_gemm_desc::topk
+
+
+def knn_topk_supported(test, train):
+    """does the fused k-NN scan take these feature matrices (fp32 rows of a multiple of 4 features on the GPU)?"""
+    return (test.is_cuda and train.is_cuda and test.dtype == torch.float32 and train.dtype == torch.float32 and test.dim() == 2 and train.dim() == 2 and
+            test.shape[1] == train.shape[1] and test.shape[1] % 4 == 0 and test.shape[0] > 0 and train.shape[0] > 0)
+
+
+def knn_topk(test, train, k, *, out=None, idx_base=0, return_similarity=False):
+    """The k most similar train rows of every test row in one pass (esvit_gemm_desc::topk): test [Nt, C], train [Ntr, C], fp32.
+    -> (vals fp32 [Nt, k], idx int32 [Nt, k]) sorted by larger similarity first, on equal similarities the smaller row number first;
+    the [Nt, Ntr] similarities are never stored unless return_similarity asks for them (-> (vals, idx, similarity), tests / small sets).
+    out = (vals, idx) of an earlier call: this call's rows (numbered from idx_base) are merged into those lists in place, so a train
+    matrix scored piece by piece ends with the lists of the whole."""
+    test, train = _f32c(test), _f32c(train)
+    Nt, Cc = test.shape
+    Ntr = train.shape[0]
+    k = int(k)
+    assert train.shape[1] == Cc
+    if not 1 <= k <= KNN_MAX_K:
+        raise ValueError("knn_topk: k=%d outside 1 .. %d" % (k, KNN_MAX_K))
+    if out is None and k > Ntr:
+        raise ValueError("knn_topk: k=%d exceeds the %d train rows" % (k, Ntr))
+    if out is None:
+        vals = torch.empty((Nt, k), dtype=torch.float32, device=test.device)
+        idx = torch.empty((Nt, k), dtype=torch.int32, device=test.device)
+    else:
+        vals, idx = out
+        assert vals.shape == (Nt, k) and idx.shape == (Nt, k) and vals.dtype == torch.float32 and idx.dtype == torch.int32
+        assert vals.is_contiguous() and idx.is_contiguous()
+    sim = torch.empty((Nt, Ntr), dtype=torch.float32, device=test.device) if return_similarity else None
+    nbytes = query(Q_TOPK_WS, Nt, Ntr, k)
+    if nbytes <= 0:
+        raise RuntimeError("esvit_query(Q_TOPK_WS) failed (%d): %s" % (nbytes, lib.esvit_last_error().decode()))
+    ws = workspace((nbytes + 3) // 4, test.device, slot="knn_topk")
+    t = GemmTopk(k=k, merge=0 if out is None else 1, vals=_p(vals), idx=_p(idx), idx_base=int(idx_base), workspace=_p(ws), workspace_bytes=ws.numel() * 4)
+    d = _gemm_desc(dict(A=test, B=train, C=sim, M=Nt, N=Ntr, K=Cc, lda=Cc, ldb=Cc, ldc=Ntr, out_f32=0, kernel=GEMM_AUTO))
+    d.topk = C.pointer(t)
+    check(lib.esvit_gemm(F32, C.byref(d), _stream()), "esvit_gemm(topk)")
+    return (vals, idx, sim) if return_similarity else (vals, idx)
 
 
 def linear_dgrad(dy, w, *, gelu_preact=None, out_f32=False, quick=False):

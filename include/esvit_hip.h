@@ -51,6 +51,9 @@ const char* esvit_last_error(void);
  *                                              are scale_h, scale_w (units of 1 / ESVIT_RESIZE_SCALE_ONE), else 0
  *   ESVIT_Q_CHUNK_ATTN_WS (nB*nH, L, backward) floats of the scratch the sliding-chunk mode of esvit_window_attn_fwd (backward = 0) /
  *                                              esvit_window_attn_bwd (backward = 1) takes through bias_frag_ws
+ *   ESVIT_Q_TOPK_WS (M, N, k)                  BYTES of esvit_gemm_topk::workspace for M test rows scored against N train rows at this k
+ *                                              (per-(row, split) candidate lists; grows with M, k and the split count, and no longer
+ *                                              with N once the splits saturate), ESVIT_ERR_ARG for k outside 1 .. 256
  * Unknown `what` returns ESVIT_ERR_ARG. */
 #define ESVIT_Q_ATTN_FRAG_ELEMS 1
 #define ESVIT_Q_ATTN_LSE_ELEMS 2
@@ -65,6 +68,7 @@ const char* esvit_last_error(void);
 #define ESVIT_Q_JPEG_WORKSPACE 11
 #define ESVIT_Q_RESIZE_FITS 12
 #define ESVIT_Q_CHUNK_ATTN_WS 13
+#define ESVIT_Q_TOPK_WS 14
 int64_t esvit_query(int what, int64_t a, int64_t b, int64_t c);
 
 /* ---- host-side integer index maps (bit-exact vs reference) -------------
@@ -87,6 +91,30 @@ int esvit_shift_mask(int H, int W, int ws, int shift, float* mask, int* n_window
 #define ESVIT_EPI_GELU_BWD 2 /* out = acc * gelu'(aux) */
 #define ESVIT_EPI_QGELU 3     /* QuickGELU (cvt_v4_transformer.py:44-46): out = v*sigmoid(1.702 v), v = acc+bias; aux receives v */
 #define ESVIT_EPI_QGELU_BWD 4 /* out = acc * d/dv[v*sigmoid(1.702 v)] at v = aux */
+
+/* The k-nearest-neighbour epilogue of esvit_gemm (esvit_gemm_desc::topk; eval_knn.py:197-210 without the [rows, N_train] similarity
+ * block): A = test features [M, K], B = train features [N, K], both fp32 row-major as stored (dtype ESVIT_F32, K % 4 == 0).  Per test
+ * row the k largest similarities and the numbers of their train rows come out sorted by ONE total order -- larger similarity first,
+ * on equal similarities the smaller train row number first --, so the list for any k' < k is the first k' columns of the list for k,
+ * and two launches give the same bits.  Every similarity is accumulated over K in one fixed order (v_mfma_f32_16x16x4_f32) that does
+ * not depend on where the train row lies in B: scoring B piece by piece with merge = 1 ends with exactly the lists of the whole.
+ *   k          1 .. 256; k <= N unless merge
+ *   vals, idx  fp32 / int32 [M, k], row-major
+ *   idx_base   added to every row number of this call's B (the position of the piece in the whole train matrix)
+ *   merge      1: the incoming contents of vals / idx are a valid sorted list (global row numbers) that takes part
+ *   workspace  >= esvit_query(ESVIT_Q_TOPK_WS, M, N, k) bytes, 16-byte aligned; contents need not be initialised
+ * C may be NULL -- then nothing of size M x N is written; otherwise the dense fp32 similarities [M, ldc] are stored from the same
+ * accumulators the selection saw (tests, small problems).  No other epilogue field combines with it: bias, residual, rowmap, rowscale,
+ * aux, split-K, colsum, rowstat, k-strided operands, batch > 1 and alpha != 1 are rejected with ESVIT_ERR_ARG before any device call. */
+typedef struct {
+    int32_t k;
+    int32_t merge;
+    float* vals;
+    int32_t* idx;
+    int64_t idx_base;
+    void* workspace;
+    int64_t workspace_bytes;
+} esvit_gemm_topk;
 
 typedef struct {
     const void* A;
@@ -131,6 +159,8 @@ typedef struct {
      * each 64-row wave tile per column -- esvit_partial_reduce folds them into the batch sum the centre update needs
      * (main_esvit.py:752-770) without another pass over the logits. */
     float* colstat;
+    /* optional: the fused k-nearest-neighbour selection (see esvit_gemm_topk above); NULL = off, every other call is what it was */
+    const esvit_gemm_topk* topk;
 } esvit_gemm_desc;
 
 /* main loops of the family (esvit_gemm_desc.kernel; what esvit_gemm_select returns) */
