@@ -129,8 +129,8 @@ __global__ __launch_bounds__(NT) void dino_ce_kernel(const T* __restrict__ s, co
     const int nterms = (t0 >= 0) + (t1 >= 0);
 
     // The kernel is bound by VALU issue (four exponentials per logit at quarter rate), so every exponential is ONE fused
-    // multiply-add feeding v_exp_f32 (base 2): exp(x * inv_st - m) = exp2(x * A - m * A), A = inv_st * log2(e), and the constants of
-    // the teacher terms are folded per column / per row.
+    // multiply-add feeding v_exp_f32 (base 2): exp(x * inv_st - m) = exp2(x * A - m * A), A = inv_st * log2(e); a teacher term is
+    // exp2((y - c) * At - off) with the row's constant folded into off.
     constexpr float LOG2E = 1.4426950408889634f;
     const float A = inv_st * LOG2E;
 
@@ -177,9 +177,10 @@ __global__ __launch_bounds__(NT) void dino_ce_kernel(const T* __restrict__ s, co
             for (int e = 0; e < V; ++e) {
                 const float xe = x.get(e);
                 const float ps = __builtin_amdgcn_exp2f(fmaf(xe, A, C));
+                // (the centre is subtracted from the logit BEFORE the scaling: teacher logits and centre share their offset, and folding
+                // -c * At into the constant would round it at the size of that offset times At instead of at the size of y - c)
                 const float ck = cv[e / 4][e & 3];
-                const float nbk = -ck * At;  // (y - c) * inv_tt * log2(e) = y * At + nbk
-                const float pt = __builtin_amdgcn_exp2f(fmaf(y0.get(e), At, nbk - off0)) + __builtin_amdgcn_exp2f(fmaf(y1.get(e), At, nbk - off1));
+                const float pt = __builtin_amdgcn_exp2f(fmaf(y0.get(e) - ck, At, -off0)) + __builtin_amdgcn_exp2f(fmaf(y1.get(e) - ck, At, -off1));
                 dot = fmaf(pt, xe, dot);
                 o.set(e, fmaf(ps, gsn, -gs * pt));
             }
@@ -202,7 +203,7 @@ __global__ __launch_bounds__(NT) void dino_ce_kernel(const T* __restrict__ s, co
                 for (int e = 0; e < V; ++e) {
                     const float xe = x.get(e);
                     const float ps = __builtin_amdgcn_exp2f(fmaf(xe, A, C));
-                    const float pt = __builtin_amdgcn_exp2f(fmaf(y.get(e), At, -cv[e / 4][e & 3] * At - off));
+                    const float pt = __builtin_amdgcn_exp2f(fmaf(y.get(e) - cv[e / 4][e & 3], At, -off));
                     dot = fmaf(pt, xe, dot);
                     o.set(e, fmaf(ps, gsn, -gs * pt));
                 }

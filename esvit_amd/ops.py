@@ -240,9 +240,7 @@ def linear_fwd(x, w, bias=None, *, gelu=False, want_preact=False, residual=None,
         cst = torch.empty((M // 64, N), dtype=torch.float32, device=x.device) if (want_cs and kern != GEMM_P8) else None
         _gemm(x.dtype, A=x, B=w, C=y, M=M, N=N, K=K, lda=K, ldb=K, ldc=N, rowstat=st, rowstat_center=cen, rowstat_scale=float(inv_temp) * LOG2E,
               colstat=cst, kernel=kern)
-        mx = torch.empty((M,), dtype=torch.float32, device=x.device)
-        lse = torch.empty_like(mx)
-        check(lib.esvit_rowstat_combine(_p(st), M, nb, _p(mx), _p(lse), _stream()), "rowstat_combine")
+        mx, lse = rowstat_combine(st)
         if cst is not None:
             mx.esvit_col_sums = colsum(cst)
         return y, mx, lse
@@ -865,6 +863,16 @@ def teacher_row_stats(t, center, inv_temp):
     return mx, lse
 
 
+def rowstat_combine(st):
+    """fold the block statistics the last-layer GEMM leaves behind (esvit_gemm_desc::rowstat: fp32 [R, nb, 2] pairs of a block's
+    maximum in base-2 units and its sum of 2^(z - max)) into the natural-log (row_max, row_lse) of teacher_row_stats"""
+    st = _f32c(st)
+    R, nb, two = st.shape
+    assert two == 2
+    mx = torch.empty((R,), dtype=torch.float32, device=st.device)
+    lse = torch.empty_like(mx)
+    check(lib.esvit_rowstat_combine(_p(st), R, nb, _p(mx), _p(lse), _stream()), "rowstat_combine")
+    return mx, lse
 
 
 def region_match(sim, Tt, crop_id, cm_row, tmatch):

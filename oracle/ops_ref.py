@@ -668,6 +668,12 @@ def teacher_row_stats(t, center, inv_temp):
     return mx, torch.log(torch.exp(z - mx[:, None]).sum(1))
 
 
+def rowstat_combine(st):
+    m, sm = st[..., 0], st[..., 1]
+    M = m.max(1).values
+    return M * 0.6931471805599453, torch.log((sm * torch.exp2(m - M[:, None])).sum(1))
+
+
 def row_argmax(sim, Tt):
     ld = sim.shape[-1]
     return sim.reshape(-1, ld)[:, :Tt].argmax(1).to(torch.int32)
