@@ -314,6 +314,9 @@ __global__ void region_match_kernel(const float* __restrict__ sim, int B, int S,
 
 #define STREAM(s_) hipStream_t stream = reinterpret_cast<hipStream_t>(s_)
 
+// probe.hip: the terms = 0 mode of esvit_dino_ce_fwd_bwd
+int esvit_i_probe_ce(const float* s, const int32_t* target, const float* row_w, int64_t Rs, int K, float* row_loss, float* ds, hipStream_t stream);
+
 extern "C" int esvit_teacher_row_stats(int dtype, const void* t, const float* center, float inv_temp, int64_t R, int K,
                                        float* row_max, float* row_lse, esvit_stream_t s_) {
     STREAM(s_);
@@ -346,6 +349,14 @@ extern "C" int esvit_dino_ce_fwd_bwd(int dtype, const void* s, const void* t, co
                                      float inv_student_temp, float inv_teacher_temp, int64_t Rs, int K, float* row_loss, void* ds,
                                      const int32_t* row_order, const float* s_row_max, const float* s_row_lse, esvit_stream_t s_) {
     STREAM(s_);
+    if (terms == 0) {  // class-index cross-entropy of the linear-probe sweep (probe.hip): tmatch holds one class per row
+        ESVIT_CHECK_ARG(!t && !center && !t_row_max && !t_row_lse && !term_w && !row_order && !s_row_max && !s_row_lse,
+                        "esvit_dino_ce_fwd_bwd(terms = 0): class-index targets take no teacher rows, centre, term weights, row order or row statistics");
+        ESVIT_CHECK_ARG(dtype == ESVIT_F32, "esvit_dino_ce_fwd_bwd(terms = 0): fp32 logits only");
+        ESVIT_CHECK_ARG(s && tmatch && row_loss && (row_w || !ds) && Rs > 0 && Rs <= 0x7fffffffL && K >= 4 && K % 4 == 0,
+                        "esvit_dino_ce_fwd_bwd(terms = 0): bad args (Rs=%ld, K=%d: a multiple of 4)", (long)Rs, K);
+        return esvit_i_probe_ce((const float*)s, tmatch, row_w, Rs, K, row_loss, (float*)ds, stream);
+    }
     ESVIT_CHECK_ARG((s_row_max == nullptr) == (s_row_lse == nullptr) && !(s_row_max && term_w),
                     "esvit_dino_ce_fwd_bwd: student row statistics come as a (max, lse) pair, for the two-term form");
     ESVIT_CHECK_ARG(s && t && center && t_row_max && t_row_lse && tmatch && row_loss && ds && Rs > 0 && K > 0 && K % 8 == 0,

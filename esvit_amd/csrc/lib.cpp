@@ -36,6 +36,7 @@ int64_t esvit_i_jpeg_workspace(int64_t blocks, int64_t plane_bytes, int64_t lane
 int64_t esvit_i_resize_fits(int64_t scale_h, int64_t scale_w);
 int64_t esvit_i_chunk_attn_ws(int64_t Z, int64_t L, int64_t backward);
 int64_t esvit_i_topk_ws(int64_t M, int64_t N, int64_t k);
+int64_t esvit_i_probe_ce_reg_row();
 
 extern "C" int64_t esvit_query(int what, int64_t a, int64_t b, int64_t c) {
     switch (what) {
@@ -53,6 +54,7 @@ extern "C" int64_t esvit_query(int what, int64_t a, int64_t b, int64_t c) {
         case ESVIT_Q_RESIZE_FITS: return esvit_i_resize_fits(a, b);
         case ESVIT_Q_CHUNK_ATTN_WS: return esvit_i_chunk_attn_ws(a, b, c);
         case ESVIT_Q_TOPK_WS: return esvit_i_topk_ws(a, b, c);
+        case ESVIT_Q_PROBE_CE_REG_ROW: return esvit_i_probe_ce_reg_row();
     }
     esvit_set_error("esvit_query: unknown question %d", what);
     return ESVIT_ERR_ARG;

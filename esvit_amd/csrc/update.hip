@@ -222,6 +222,64 @@ __global__ __launch_bounds__(256) void clip_momentum_ema_kernel(const long* __re
     }
 }
 
+// ESVIT_RULE_SGD_MEMBERS: torch.optim.SGD(momentum, dampening 0, no nesterov) for G independent MEMBERS (the classifiers of a linear-probe
+// sweep) in one launch.  buf = momentum buf + (g + wd p), p -= lr buf, with lr and wd PER TENSOR from slot 9 of its table row
+// (bits(lr) | bits(wd) << 32): the learning rates reach the device as data.  No clipping, no teacher, no weight copies.
+// The non-finite guard is per member: the member id rides in the upper half of the flags slot, a workgroup looks at the statistics of
+// the tensors that carry its own id only, and a member is left alone -- parameters and buffers keep their values, skipped[member]
+// goes up by one -- when one of them is NaN / inf OR when skipped[member] is already non-zero (a member that diverged once stays
+// frozen; the caller thaws it by clearing its counter).  The counter is written by ONE workgroup per member and launch (chunk 0 of the
+// member's first tensor) with a plain store; every other workgroup of the member reaches the same verdict from either value.
+__global__ __launch_bounds__(256) void sgd_members_kernel(const long* __restrict__ tensors, int ntensors, const int* __restrict__ chunks,
+                                                          const float* __restrict__ stats, float momentum, int* __restrict__ skipped) {
+    const int tid = chunks[2 * blockIdx.x], ci = chunks[2 * blockIdx.x + 1];
+    const long* tt = tensors + (long)tid * TFIELDS;
+    const long member = (long)((unsigned long)tt[7] >> 32);
+    int bad = 0, earlier = 0;
+    for (int i = threadIdx.x; i < ntensors; i += 256) {
+        const long f = tensors[(long)i * TFIELDS + 7];
+        if ((long)((unsigned long)f >> 32) != member) continue;
+        if (f & 1) bad |= !(fabsf(stats[i]) <= 3.0e38f);
+        earlier |= i < tid;
+    }
+    const int frozen = skipped[member];
+    const bool skip = __syncthreads_or(bad) != 0 || frozen != 0;
+    const bool first = __syncthreads_or(earlier) == 0 && ci == 0;
+    if (skip) {
+        if (first && threadIdx.x == 0) skipped[member] = frozen + 1;
+        return;
+    }
+    if (!(tt[7] & 1)) return;
+    float* p = reinterpret_cast<float*>(tt[0]);
+    const float* g = reinterpret_cast<const float*>(tt[1]);
+    float* mu = reinterpret_cast<float*>(tt[2]);
+    const long n = tt[5];
+    const float lr = __uint_as_float((unsigned)(tt[9] & 0xffffffffL));
+    const float wd = __uint_as_float((unsigned)((unsigned long)tt[9] >> 32));
+    const long base = (long)ci * CHUNK;
+#pragma unroll
+    for (int i = 0; i < CHUNK / 256 / 4; ++i) {
+        const long o = base + (i * 256 + threadIdx.x) * 4;
+        if (o + 4 <= n) {
+            f32x4 pv = *reinterpret_cast<f32x4*>(p + o), mv = *reinterpret_cast<f32x4*>(mu + o);
+            const f32x4 gv = *reinterpret_cast<const f32x4*>(g + o);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                mv[e] = momentum * mv[e] + (gv[e] + wd * pv[e]);
+                pv[e] -= lr * mv[e];
+            }
+            *reinterpret_cast<f32x4*>(mu + o) = mv;
+            *reinterpret_cast<f32x4*>(p + o) = pv;
+        } else {
+            for (long j = o; j < n; ++j) {
+                const float me = momentum * mu[j] + (g[j] + wd * p[j]);
+                mu[j] = me;
+                p[j] -= lr * me;
+            }
+        }
+    }
+}
+
 }  // namespace
 
 int esvit_i_update_chunk_elems() { return CHUNK; }  // esvit_query
@@ -246,6 +304,12 @@ extern "C" int esvit_fused_clip_update_ema(int rule, const int64_t* tensors, int
                                            float ema_m, int32_t* skipped, esvit_stream_t s_) {
     hipStream_t stream = reinterpret_cast<hipStream_t>(s_);
     ESVIT_CHECK_ARG(tensors && chunks && sqnorms && ntensors > 0 && nchunks > 0, "esvit_fused_clip_update_ema: bad args");
+    if (rule == ESVIT_RULE_SGD_MEMBERS) {
+        ESVIT_CHECK_ARG(skipped, "esvit_fused_clip_update_ema(ESVIT_RULE_SGD_MEMBERS): skipped (int32, one counter per member) is required");
+        hipLaunchKernelGGL(sgd_members_kernel, dim3(nchunks), dim3(256), 0, stream, (const long*)tensors, ntensors, chunks, sqnorms, beta1, skipped);
+        ESVIT_CHECK_LAUNCH("fused_clip_update_ema(members)");
+        return ESVIT_OK;
+    }
     ESVIT_CHECK_ARG(rule == ESVIT_RULE_ADAMW || rule == ESVIT_RULE_SGD || rule == ESVIT_RULE_LARS, "esvit_fused_clip_update_ema: bad rule %d", rule);
     if (rule == ESVIT_RULE_ADAMW)
         hipLaunchKernelGGL(clip_adamw_ema_kernel, dim3(nchunks), dim3(256), 0, stream, (const long*)tensors, chunks, sqnorms, ntensors, clip, lr, wd,

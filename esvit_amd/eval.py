@@ -308,3 +308,7 @@ def validate_network(val_loader, model, linear_classifier, n, avgpool, depths):
     if _dist_on():
         dist.all_reduce(acc)
     return {"loss": (acc[0] / acc[1].clamp(min=1)).item(), "acc1": (acc[2] / acc[4].clamp(min=1)).item(), "acc5": (acc[3] / acc[4].clamp(min=1)).item()}
+
+
+# the linear-probe sweep (esvit_amd/probe.py): every (learning rate, weight decay) of the probe from one frozen-feature pass
+from .probe import LinearProbeSweep, train_linear_sweep_epoch, validate_linear_sweep  # noqa: E402,F401

@@ -83,7 +83,7 @@ def relative_position_index(ws):
 
 # esvit_query questions (include/esvit_hip.h)
 (Q_ATTN_FRAG_ELEMS, Q_ATTN_LSE_ELEMS, Q_ATTN_BWD_PARTS, Q_ATTN_BWD_PAD_ROWS, Q_LN_BWD_BLOCKS, Q_COLSUM_BLOCKS, Q_COL_REDUCE_BLOCKS,
- Q_UPDATE_CHUNK_ELEMS, Q_MLP_FUSED, Q_AUG_MAX_BOX, Q_JPEG_WORKSPACE, Q_RESIZE_FITS, Q_CHUNK_ATTN_WS, Q_TOPK_WS) = range(1, 15)
+ Q_UPDATE_CHUNK_ELEMS, Q_MLP_FUSED, Q_AUG_MAX_BOX, Q_JPEG_WORKSPACE, Q_RESIZE_FITS, Q_CHUNK_ATTN_WS, Q_TOPK_WS, Q_PROBE_CE_REG_ROW) = range(1, 16)
 
 
 def query(what, a=0, b=0, c=0):
@@ -907,6 +907,33 @@ def dino_ce(s, t, center, t_max, t_lse, tmatch, row_w, inv_student_temp, inv_tea
     return row_loss, ds
 
 
+def probe_ce(logits, targets, row_w, row_loss=None, want_grad=True, inplace=True):
+    """class-index cross-entropy of G classifiers sharing a batch (esvit_dino_ce_fwd_bwd, terms = 0).  logits fp32 [Rs, C] (the
+    [B, G * C] GEMM output viewed as Rs = B * G rows), targets int32 [Rs], row_w fp32 [Rs] (the gradient scale of each row).
+    -> (row_loss fp32 [Rs, 2] = (lse - z_t, rank of the target), dlogits): dlogits is `logits` itself overwritten (inplace), a new
+    tensor, or None with want_grad=False (validation: the logits are left as they are)."""
+    logits = _f32c(logits)
+    Rs, C = logits.shape
+    assert targets.dtype == torch.int32 and targets.numel() == Rs and targets.is_contiguous()
+    if row_loss is None:
+        row_loss = torch.empty((Rs, 2), dtype=torch.float32, device=logits.device)
+    assert row_loss.numel() == 2 * Rs and row_loss.is_contiguous() and row_loss.dtype == torch.float32
+    ds = None
+    if want_grad:
+        assert row_w is not None and row_w.numel() == Rs
+        row_w = _f32c(row_w)
+        ds = logits if inplace else torch.empty_like(logits)
+    check(lib.esvit_dino_ce_fwd_bwd(_code(logits.dtype), _p(logits), None, None, None, None, _p(targets), _p(row_w), 0, None, 1.0, 1.0, Rs, C,
+                                    _p(row_loss), _p(ds), None, None, None, _stream()),
+          "dino_ce_fwd_bwd(class index)")
+    return row_loss, ds
+
+
+def probe_ce_reg_row():
+    """longest row the class-index CE keeps in registers; longer rows take the workgroup-per-row kernel"""
+    return query(Q_PROBE_CE_REG_ROW)
+
+
 def sum_f32(x):
     x = _f32c(x)
     out = torch.empty((), dtype=torch.float32, device=x.device)
@@ -933,7 +960,7 @@ def update_chunk_elems():
     return query(Q_UPDATE_CHUNK_ELEMS)
 
 
-RULE_ADAMW, RULE_SGD, RULE_LARS = 0, 1, 2
+RULE_ADAMW, RULE_SGD, RULE_LARS, RULE_SGD_MEMBERS = 0, 1, 2, 3
 
 
 def grad_sqnorm(tensors, ntensors, chunks, nchunks, sqnorms, stats=1):
@@ -941,7 +968,8 @@ def grad_sqnorm(tensors, ntensors, chunks, nchunks, sqnorms, stats=1):
 
 
 def fused_clip_update_ema(rule, tensors, ntensors, chunks, nchunks, sqnorms, clip, lr, wd, beta1, beta2, eps, ema_m, skipped=None):
-    """rule AdamW: (beta1, beta2, eps); SGD: beta1 = momentum; LARS: beta1 = momentum, beta2 = eta"""
+    """rule AdamW: (beta1, beta2, eps); SGD: beta1 = momentum; LARS: beta1 = momentum, beta2 = eta; SGD_MEMBERS: beta1 = momentum, lr and
+    wd per tensor in the table's slot 9, the member id in the upper half of the flags slot, `skipped` int32 [members] required"""
     check(lib.esvit_fused_clip_update_ema(int(rule), _p(tensors), ntensors, _p(chunks), nchunks, _p(sqnorms), clip, lr, wd, beta1, beta2,
                                           eps, ema_m, _p(skipped), _stream()), "fused_clip_update_ema")
 

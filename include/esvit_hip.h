@@ -54,6 +54,8 @@ const char* esvit_last_error(void);
  *   ESVIT_Q_TOPK_WS (M, N, k)                  BYTES of esvit_gemm_topk::workspace for M test rows scored against N train rows at this k
  *                                              (per-(row, split) candidate lists; grows with M, k and the split count, and no longer
  *                                              with N once the splits saturate), ESVIT_ERR_ARG for k outside 1 .. 256
+ *   ESVIT_Q_PROBE_CE_REG_ROW ()                longest row (floats) the class-index mode of esvit_dino_ce_fwd_bwd keeps in registers (one wave
+ *                                              per row); longer rows take one workgroup per row and three sweeps
  * Unknown `what` returns ESVIT_ERR_ARG. */
 #define ESVIT_Q_ATTN_FRAG_ELEMS 1
 #define ESVIT_Q_ATTN_LSE_ELEMS 2
@@ -69,6 +71,7 @@ const char* esvit_last_error(void);
 #define ESVIT_Q_RESIZE_FITS 12
 #define ESVIT_Q_CHUNK_ATTN_WS 13
 #define ESVIT_Q_TOPK_WS 14
+#define ESVIT_Q_PROBE_CE_REG_ROW 15
 int64_t esvit_query(int what, int64_t a, int64_t b, int64_t c);
 
 /* ---- host-side integer index maps (bit-exact vs reference) -------------
@@ -407,7 +410,18 @@ int esvit_region_match(const float* sim, int B, int S, int Tt, int ld, const int
  * passes the image-major order so that the student rows of one image, which share their <= 98 teacher rows, run together and
  * re-read them from cache instead of HBM.  Results do not depend on it.
  * s_row_max / s_row_lse (optional pair, fp32 [Rs]): statistics of z = s / tau_s already known (esvit_rowstat_combine of the
- * last-layer GEMM's side output): lse(z) = s_row_max + s_row_lse and the kernel's first pass over the row is skipped. */
+ * last-layer GEMM's side output): lse(z) = s_row_max + s_row_lse and the kernel's first pass over the row is skipped.
+ *
+ * terms = 0: CLASS-INDEX cross-entropy (F.cross_entropy on a classifier's logits; the linear-probe sweep, eval_linear.py:262).
+ * s fp32 [Rs, K] (dtype ESVIT_F32 only, K % 4 == 0, K >= 4): for G classifiers sharing a batch of B samples the logits [B, G*K] are
+ * Rs = B*G such rows.  tmatch int32 [Rs]: the class of each row, in [0, K).  row_w fp32 [Rs]: the gradient scale of the row
+ * (1 / (B * world) for a batch mean; may be NULL when ds is).  t, center, t_row_max, t_row_lse, term_w, row_order, s_row_max and
+ * s_row_lse must be NULL; the temperatures are ignored.  Outputs: row_loss fp32 [Rs, 2] = (lse(z) - z_t, rank of the target), with
+ * rank = #{j : z_j > z_t} + #{j < t : z_j == z_t}, the target's position in the stable descending order -- a count, exact as a float,
+ * and "among the top k" is rank < k;  ds fp32 [Rs, K] = row_w[r] (softmax(z)_j - [j == t]).  ds may be s (in place) or NULL (no
+ * gradient, s untouched).  A row with a NaN / inf logit or a class outside [0, K) gives loss NaN, rank K and a NaN gradient row, and
+ * leaves every other row as it would have been.  No atomics: identical launches give identical bits.  Rows of up to
+ * esvit_query(ESVIT_Q_PROBE_CE_REG_ROW) floats are held in registers by one wave; longer rows take a workgroup and three sweeps. */
 int esvit_dino_ce_fwd_bwd(int dtype, const void* s, const void* t, const float* center,
                           const float* t_row_max, const float* t_row_lse, const int32_t* tmatch,
                           const float* row_w, int terms, const float* term_w, float inv_student_temp,
@@ -430,10 +444,15 @@ int esvit_center_ema(float* center, const float* colsum, float momentum, float d
  *   ESVIT_RULE_SGD    torch.optim.SGD(momentum)  (beta1 = momentum; beta2, eps unused): mu = momentum mu + (c g + wd p)
  *   ESVIT_RULE_LARS   utils.LARS (utils.py:519-557) (beta1 = momentum, beta2 = eta): mu = momentum mu + q (c g + wd p),
  *                     q = eta |p| / |c g + wd p| for tensors of group 0 (ndim != 1), 1 otherwise;  p -= lr mu
+ *   ESVIT_RULE_SGD_MEMBERS  torch.optim.SGD(momentum, dampening 0, no nesterov) for independent MEMBERS (the classifiers of a
+ *                     linear-probe sweep) in one launch (beta1 = momentum): mu = momentum mu + (g + wd p), p -= lr mu, with lr and wd
+ *                     PER TENSOR from the table's slot 9, bits(lr) | bits(wd) << 32; the lr, wd, clip, beta2, eps, ema_m arguments,
+ *                     the group slot, the teacher and the bf16 copies are ignored.  Bits 32.. of the flags slot hold the tensor's
+ *                     member id; the non-finite guard is per member and `skipped` is REQUIRED: int32 [members] (see below).
  * (c = the clip factor of the tensor).  Tensor table (device, int64[ntensors*12]):
  *   [p, g, exp_avg (SGD: momentum_buffer, LARS: mu), exp_avg_sq (AdamW only), teacher_p (0 = none), numel,
- *    group (0: weight decay, 1: none), flags (bit0: has gradient; otherwise only the EMA is applied),
- *    bits(1-beta1^t) | bits(1-beta2^t) << 32 (AdamW), reserved,
+ *    group (0: weight decay, 1: none), flags (bit0: has gradient; otherwise only the EMA is applied; bits 32..: member id, SGD_MEMBERS),
+ *    bits(1-beta1^t) | bits(1-beta2^t) << 32 (AdamW), reserved (SGD_MEMBERS: bits(lr) | bits(wd) << 32),
  *    bf16 copy of p (0 = none), bf16 copy of teacher_p (0 = none)]   -- the copies are refreshed in the same pass
  * chunk table (device, int32[nchunks*2]): [tensor_id, chunk_index], chunk =
  * esvit_query(ESVIT_Q_UPDATE_CHUNK_ELEMS, 0, 0, 0) elements.
@@ -442,10 +461,15 @@ int esvit_center_ema(float* center, const float* colsum, float momentum, float d
  * Non-finite guard: if ANY statistic is NaN / inf (a non-finite loss poisons every gradient) the update launch is a no-op --
  * student, moments, teacher and weight copies keep their values (the reference exits before its update, main_esvit.py:546-551);
  * `skipped` (device int32, may be NULL) is then incremented by one, so that a host that looks at the loss only now and then can still
- * count the updates that did not happen (a gradient overflow with a finite loss) and correct its step counters. */
+ * count the updates that did not happen (a gradient overflow with a finite loss) and correct its step counters.
+ * ESVIT_RULE_SGD_MEMBERS narrows the guard to the member: a non-finite statistic of ANY tensor of member m (its weight, its bias)
+ * makes the update of m's tensors a no-op and adds one to skipped[m]; every other member is updated as if m were not in the launch.
+ * A member whose counter is non-zero stays frozen -- later launches leave it alone and keep counting -- until the caller clears
+ * skipped[m].  The statistics are esvit_grad_sqnorm(stats = 1). */
 #define ESVIT_RULE_ADAMW 0
 #define ESVIT_RULE_SGD 1
 #define ESVIT_RULE_LARS 2
+#define ESVIT_RULE_SGD_MEMBERS 3
 int esvit_grad_sqnorm(const int64_t* tensors, int ntensors, const int32_t* chunks, int nchunks, int stats,
                       float* sqnorms, esvit_stream_t stream);
 int esvit_fused_clip_update_ema(int rule, const int64_t* tensors, int ntensors, const int32_t* chunks, int nchunks,
