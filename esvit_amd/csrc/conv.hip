@@ -390,6 +390,24 @@ __global__ __launch_bounds__(256) void col_sums2_kernel(const T* __restrict__ a,
     }
 }
 
+// The same sums for C > 1024 (more channel lanes than a workgroup has threads; the DINO head's BatchNorm at hidden_dim = 2048): the
+// channel lanes are tiled over gridDim.y, a workgroup is 256 channel lanes x ONE position lane, so there is no fold over position
+// lanes.  Same workspace layout.
+template <typename T>
+__global__ __launch_bounds__(256) void col_sums2_wide_kernel(const T* __restrict__ a, const T* __restrict__ b, long rows, int C,
+                                                             float* __restrict__ ws) {
+    const int c = (blockIdx.y * blockDim.x + threadIdx.x) * 4;
+    if (c >= C) return;
+    f32x4 s1 = {0.f, 0.f, 0.f, 0.f}, s2 = {0.f, 0.f, 0.f, 0.f};
+    for (long r = blockIdx.x; r < rows; r += gridDim.x) {
+        const f32x4 av = load4c(a + r * C + c);
+        s1 += av;
+        s2 += av * load4c(b + r * C + c);
+    }
+    store4c(ws + (long)blockIdx.x * 2 * C + c, s1);
+    store4c(ws + (long)blockIdx.x * 2 * C + C + c, s2);
+}
+
 // ACT 0: y = a1 x1 + a2 x2 + a3;  1: y = GELU(a1 x1 + a3);  2: y = x2 * GELU'(a1 x1 + a3);  3: y = max(a1 x1 + a3, 0);
 // 4: y = x2 where a1 x1 + a3 > 0, else 0  (BatchNorm + ReLU of the residual stem and its backward)
 template <typename T, int ACT>
@@ -505,6 +523,10 @@ inline int reduce_blocks(long rows) {
     return (int)nb;
 }
 
+// load4c / store4c move four channels at once: 8 bytes of bf16, 16 of fp32
+inline int chan_align(int dtype) { return dtype == ESVIT_BF16 ? 8 : 16; }
+inline bool chan_aligned(int dtype, const void* p) { return (uintptr_t)p % chan_align(dtype) == 0; }
+
 }  // namespace
 
 #define STREAM(s_) hipStream_t stream = reinterpret_cast<hipStream_t>(s_)
@@ -566,8 +588,12 @@ extern "C" int esvit_dwconv3x3(int dtype, const void* x, const float* w, int fli
     STREAM(s_);
     ESVIT_CHECK_ARG(x && w && y && nB > 0 && H > 0 && W > 0 && C > 0 && C % 4 == 0, "esvit_dwconv3x3: bad args (C=%d)", C);
     ESVIT_CHECK_ARG(dtype == ESVIT_BF16 || dtype == ESVIT_F32, "esvit_dwconv3x3: bad dtype");
-    ESVIT_CHECK_ARG(C / 4 <= 256, "esvit_dwconv3x3: C=%d too wide", C);
-    if (dtype == ESVIT_BF16 && C % 8 == 0 && C / 8 <= 256 && ((uintptr_t)x % 16 == 0) && ((uintptr_t)y % 16 == 0) && ((uintptr_t)w % 16 == 0)) {
+    const bool strip = dtype == ESVIT_BF16 && C % 8 == 0 && C / 8 <= 256 && ((uintptr_t)x % 16 == 0) && ((uintptr_t)y % 16 == 0) && ((uintptr_t)w % 16 == 0);
+    // the per-channel kernel has C/4 channel lanes in one workgroup and moves four channels per load (the strip kernel: C/8 lanes)
+    ESVIT_CHECK_ARG(strip || C / 4 <= 256, "esvit_dwconv3x3: C=%d too wide", C);
+    ESVIT_CHECK_ARG(strip || (chan_aligned(dtype, x) && chan_aligned(dtype, y)), "esvit_dwconv3x3: x, y must be aligned to four channels (%d bytes)",
+                    chan_align(dtype));
+    if (strip) {
         const int cvn = C / 8;
         const dim3 blk(cvn, 256 / cvn > 0 ? 256 / cvn : 1);
         const long strips = (long)nB * H * ((W + DW_SW - 1) / DW_SW);
@@ -595,9 +621,12 @@ extern "C" int esvit_dwconv3x3_wgrad(int dtype, const void* x, const void* dy, i
     STREAM(s_);
     ESVIT_CHECK_ARG(x && dy && dw && ws && nB > 0 && H > 0 && W > 0 && C > 0, "esvit_dwconv3x3_wgrad: bad args");
     ESVIT_CHECK_ARG(dtype == ESVIT_BF16 || dtype == ESVIT_F32, "esvit_dwconv3x3_wgrad: bad dtype");
-    ESVIT_CHECK_ARG(C % 4 == 0 && C / 4 <= 256, "esvit_dwconv3x3_wgrad: bad C=%d", C);
+    const bool strip = dtype == ESVIT_BF16 && C % 8 == 0 && C / 8 <= 256 && ((uintptr_t)x % 16 == 0) && ((uintptr_t)dy % 16 == 0);
+    ESVIT_CHECK_ARG(C % 4 == 0 && (strip || C / 4 <= 256), "esvit_dwconv3x3_wgrad: bad C=%d", C);
+    ESVIT_CHECK_ARG(strip || (chan_aligned(dtype, x) && chan_aligned(dtype, dy)),
+                    "esvit_dwconv3x3_wgrad: x, dy must be aligned to four channels (%d bytes)", chan_align(dtype));
     const int nblk = reduce_blocks((long)nB * H * W);
-    if (dtype == ESVIT_BF16 && C % 8 == 0 && C / 8 <= 256 && ((uintptr_t)x % 16 == 0) && ((uintptr_t)dy % 16 == 0)) {
+    if (strip) {
         const int cvn = C / 8;
         const dim3 blk(cvn, 256 / cvn > 0 ? 256 / cvn : 1);
         const size_t lds_s = (size_t)blk.x * blk.y * 72 * sizeof(float);
@@ -624,8 +653,21 @@ extern "C" int esvit_col_sums2(int dtype, const void* a, const void* b, int64_t 
     STREAM(s_);
     ESVIT_CHECK_ARG(a && b && out && ws && rows > 0 && C > 0, "esvit_col_sums2: bad args");
     ESVIT_CHECK_ARG(dtype == ESVIT_BF16 || dtype == ESVIT_F32, "esvit_col_sums2: bad dtype");
-    ESVIT_CHECK_ARG(C % 4 == 0 && C / 4 <= 256, "esvit_col_sums2: bad C=%d", C);
+    ESVIT_CHECK_ARG(C % 4 == 0, "esvit_col_sums2: bad C=%d", C);
+    ESVIT_CHECK_ARG(chan_aligned(dtype, a) && chan_aligned(dtype, b) && (uintptr_t)ws % 16 == 0,
+                    "esvit_col_sums2: a, b must be aligned to four channels (%d bytes) and ws to 16", chan_align(dtype));
     const int nblk = reduce_blocks(rows);
+    if (C / 4 > 256) {
+        const dim3 grid(nblk, ceil_div(C / 4, 256));
+        if (dtype == ESVIT_BF16)
+            hipLaunchKernelGGL(col_sums2_wide_kernel<bf16>, grid, dim3(256), 0, stream, reinterpret_cast<const bf16*>(a),
+                               reinterpret_cast<const bf16*>(b), (long)rows, C, ws);
+        else
+            hipLaunchKernelGGL(col_sums2_wide_kernel<float>, grid, dim3(256), 0, stream, reinterpret_cast<const float*>(a),
+                               reinterpret_cast<const float*>(b), (long)rows, C, ws);
+        ESVIT_CHECK_LAUNCH("col_sums2(wide)");
+        return esvit_partial_reduce(ws, nblk, 2 * C, 2L * C, out, 0, stream);
+    }
     const dim3 block = chan_block(C);
     const size_t lds = (size_t)block.x * block.y * 2 * sizeof(f32x4);
     if (dtype == ESVIT_BF16)
@@ -704,6 +746,7 @@ extern "C" int esvit_pad_crop_tokens(int dtype, const void* src, int nB, int Hs,
     ESVIT_CHECK_ARG(src && dst && nB > 0 && Hs > 0 && Ws > 0 && Hd > 0 && Wd > 0 && C > 0, "esvit_pad_crop_tokens: bad args");
     ESVIT_CHECK_ARG(dtype == ESVIT_BF16 || dtype == ESVIT_F32, "esvit_pad_crop_tokens: bad dtype");
     ESVIT_CHECK_ARG(C % (dtype == ESVIT_BF16 ? 8 : 4) == 0, "esvit_pad_crop_tokens: C=%d must be a multiple of the 16-byte vector", C);
+    ESVIT_CHECK_ARG((uintptr_t)src % 16 == 0 && (uintptr_t)dst % 16 == 0, "esvit_pad_crop_tokens: src, dst must be aligned to 16 bytes");
     if (dtype == ESVIT_BF16)
         hipLaunchKernelGGL(pad_crop_kernel<bf16>, dim3(grid_for((long)nB * Hd * Wd * (C / 8))), dim3(256), 0, stream,
                            reinterpret_cast<const bf16*>(src), nB, Hs, Ws, Hd, Wd, C, reinterpret_cast<bf16*>(dst));

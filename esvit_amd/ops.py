@@ -1041,6 +1041,11 @@ def col_affine2(x1, a1, a3, x2=None, a2=None, act=0):
     3: y = max(a1[c] * x1 + a3[c], 0);  4: y = x2 where a1[c] * x1 + a3[c] > 0 else 0  (act dtype in / out, fp32 coefficients)"""
     x1 = _actc(x1)
     rows, Cc = x1.shape
+    assert a1.numel() == Cc and a3.numel() == Cc, (a1.shape, a3.shape, Cc)
+    if x2 is not None:
+        assert x2.dtype == x1.dtype and x2.shape == x1.shape and x2.is_contiguous(), (x2.dtype, tuple(x2.shape), x2.is_contiguous())
+    if a2 is not None:
+        assert _f32c(a2).numel() == Cc, (a2.shape, Cc)
     y = torch.empty_like(x1)
     check(lib.esvit_col_affine2(_code(x1.dtype), _p(x1), _p(x2), rows, Cc, _p(_f32c(a1)), _p(a2), _p(_f32c(a3)), int(act), _p(y), _stream()),
           "col_affine2")

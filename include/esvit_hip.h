@@ -490,7 +490,12 @@ int esvit_fused_clip_update_ema(int rule, const int64_t* tensors, int ntensors, 
  *   act 1: y = GELU(a1[c]*x1 + a3[c]) and act 2: y = x2 * GELU'(a1[c]*x1 + a3[c]) -- BatchNorm1d + GELU of DINOHead(use_bn=True)
  *   (vision_transformer.py:391-402) and its backward, the normalised value rebuilt from the pre-norm activation;
  *   act 3: y = max(a1[c]*x1 + a3[c], 0) and act 4: y = x2 where a1[c]*x1 + a3[c] > 0, else 0 -- BatchNorm2d + ReLU of the
- *   residual stem (cvt_v4_transformer.py:385-430) and its backward. */
+ *   residual stem (cvt_v4_transformer.py:385-430) and its backward.
+ * Widths and alignment (refused with ESVIT_ERR_ARG, nothing is launched): esvit_col_sums2 takes any C % 4 == 0; esvit_dwconv3x3
+ *   and esvit_dwconv3x3_wgrad take C % 4 == 0 up to 1024, and bf16 with C % 8 == 0 and 16-byte aligned tensors up to 2048.
+ *   These three move four channels per load: x, y, dy, a, b must be aligned to 8 bytes in bf16 and 16 in fp32 (ws: 16).
+ *   esvit_pad_crop_tokens wants src and dst on 16 bytes.  The BatchNorm variance is sum(d^2)/n - mean^2 in fp32: the relative
+ *   error of rstd grows as 8 (1 + (mean/std)^2) 2^-24 (tests/test_conv_gpu.py holds it to that). */
 int esvit_conv_im2col(int dtype, const void* src, int nchw, int nB, int H, int W, int Cin, int k, int stride, int pad,
                       int Ho, int Wo, int Kpad, void* cols, esvit_stream_t stream);
 int esvit_conv_col2im(int dtype, const void* dcols, int nB, int H, int W, int Cin, int k, int stride, int pad, int Ho,
