@@ -834,6 +834,12 @@ int esvit_chunk_attn_fwd(int dtype, const void* qkv, const int32_t* chunk_table,
 int esvit_chunk_attn_bwd(int dtype, const void* qkv, const int32_t* chunk_table, int L, const void* dout, const void* fwd_out, const float* lse,
                          int ws, float* scratch, int nx, int nB, int ny, int nH, int hd, float scale, void* dqkv, hipStream_t stream);
 
+// the global mode (flash_attn.hip)
+int esvit_flash_attn_fwd(int dtype, const void* qkv, int L, int ws, int nW, int nB, int N, int nH, int hd, float scale, void* out, float* lse,
+                         float* attn_out, hipStream_t stream);
+int esvit_flash_attn_bwd(int dtype, const void* qkv, int L, const void* dout, const void* fwd_out, const float* lse, int ws, float* scratch,
+                         int nW, int nB, int N, int nH, int hd, float scale, void* dqkv, hipStream_t stream);
+
 // answers of esvit_query (lib.cpp)
 int esvit_i_attn_frag_elems(int N) { return N <= NP ? FRAG_ELEMS : (N <= esvit_big_npb() ? esvit_big_frag_elems() : -1); }
 int esvit_i_attn_lse_elems(int N) { return N <= NP ? 0 : esvit_big_npb(); }
@@ -857,6 +863,8 @@ extern "C" int esvit_window_attn_fwd(int dtype, const void* qkv, const float* qk
                                      const float* rel_table, int ws, float* bias_frag_ws, const int32_t* region_ids, int nW, int nB, int N,
                                      int nH, int hd, float scale, void* out, float* lse, float* attn_out, esvit_stream_t s_) {
     STREAM(s_);
+    if (ws > 0 && (ws & ESVIT_ATTN_GLOBAL))  // flash attention over whole crops of any length: one "window" of L tokens per image (esvit_hip.h)
+        return esvit_flash_attn_fwd(dtype, qkv, L, ws, nW, nB, N, nH, hd, scale, out, lse, attn_out, stream);
     if (ws > 0 && (ws & ESVIT_ATTN_SLIDING_CHUNK))  // Vision Longformer's sliding-chunk attention: nW x N is the token grid (esvit_hip.h)
         return esvit_chunk_attn_fwd(dtype, qkv, win2tok, L, ws & ~ESVIT_ATTN_SLIDING_CHUNK, bias_frag_ws, nW, nB, N, nH, hd, scale, out, lse, attn_out,
                                     stream);
@@ -905,6 +913,8 @@ extern "C" int esvit_window_attn_bwd(int dtype, const void* qkv, const float* qk
                                      const int32_t* region_ids, int nW, int nB, int N, int nH, int hd, float scale, void* dqkv,
                                      float* dbias_ws, float* dpad_ws, esvit_stream_t s_) {
     STREAM(s_);
+    if (ws > 0 && (ws & ESVIT_ATTN_GLOBAL))
+        return esvit_flash_attn_bwd(dtype, qkv, L, dout, fwd_out, lse, ws, bias_frag_ws, nW, nB, N, nH, hd, scale, dqkv, stream);
     if (ws > 0 && (ws & ESVIT_ATTN_SLIDING_CHUNK))
         return esvit_chunk_attn_bwd(dtype, qkv, win2tok, L, dout, fwd_out, lse, ws & ~ESVIT_ATTN_SLIDING_CHUNK, bias_frag_ws, nW, nB, N, nH, hd, scale,
                                     dqkv, stream);

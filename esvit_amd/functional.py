@@ -1391,6 +1391,13 @@ class VitPatchEmbedFn(torch.autograd.Function):
 
 VIT_WINDOW_TOKENS = 224  # crops of at most this many tokens run through the fused windowed kernels (one "window" per image)
 _VIT_WIN = {}
+# longer crops (patch 8, evaluation above 224^2): "gemm" = the batched-GEMM route of ops.vit_attn_fwd, which keeps P [B nH, N, N] for
+# the backward; "flash" = the fused kernels of flash_attn.hip (ops.global_attn_fwd), linear in N.  The speed of the two is compared by
+# tools/bench_vit_attn.py; until that A/B has been read the default stays "gemm".
+VIT_LONG_ATTENTION = os.environ.get("ESVIT_VIT_LONG_ATTN", "gemm")
+if VIT_LONG_ATTENTION not in ("gemm", "flash"):
+    raise ValueError("ESVIT_VIT_LONG_ATTN: gemm or flash, not %r" % VIT_LONG_ATTENTION)
+_FLASH_TAGS = {}
 
 
 def _vit_window(N, nH, device):
@@ -1414,11 +1421,29 @@ def _vit_fused_route(N, hd, dtype):
     return N <= VIT_WINDOW_TOKENS and (hd == 32 or (hd == 64 and dtype == torch.bfloat16))
 
 
+def _vit_flash_route(o, N, hd, dtype):
+    """does this crop take the flash kernels?  Asked for with VIT_LONG_ATTENTION = "flash"; an ops module without the entry (the CPU
+    restatement, oracle/ops_ref.py) or an unsupported shape (fp32 parity mode, other head dims) keeps the batched-GEMM route."""
+    if VIT_LONG_ATTENTION != "flash" or N <= VIT_WINDOW_TOKENS or not hasattr(o, "global_attn_fwd"):
+        return False
+    sup = getattr(o, "global_attn_supported", None)
+    return sup is not None and bool(sup(dtype, hd))
+
+
+def _flash_tag(device):
+    """an empty tensor that pads the flash route's saved tuple to five entries: (q | k | v, P) has two, the windowed routes three or four"""
+    t = _FLASH_TAGS.get(str(device))
+    if t is None:
+        t = _FLASH_TAGS[str(device)] = torch.empty(0, dtype=torch.float32, device=device)
+    return t
+
+
 def vit_attention(o, qkv, bqkv, nB, N, nH, scale, save, out=None):
     """Attention.forward between the projections (vision_transformer.py:76-83) -> (out, tensors for vit_attention_bwd).  A crop is ONE
     window of the fused MFMA kernels: the 37 tokens of a 96^2 crop in the 64-slot kernels of window_attn.hip, the 197 tokens of a
     224^2 crop in the 224-slot flash-style kernels of window_attn_big.hip (head_dim 64 in bf16) -- no score matrix in HBM.  What
-    does not fit (fp32 parity mode at head_dim 64, longer sequences) takes the batched-GEMM route of ops.vit_attn_fwd."""
+    does not fit (fp32 parity mode at head_dim 64, longer sequences) takes the batched-GEMM route of ops.vit_attn_fwd, or, for longer
+    sequences under VIT_LONG_ATTENTION = "flash", the any-length kernels of flash_attn.hip."""
     hd = qkv.shape[1] // 3 // nH
     if _vit_fused_route(N, hd, qkv.dtype):
         win2tok, ws, table = _vit_window(N, nH, qkv.device)
@@ -1427,6 +1452,12 @@ def vit_attention(o, qkv, bqkv, nB, N, nH, scale, save, out=None):
         if not save:
             return ao, ()
         return ao, ((qkv, ao, frag) if lse is None else (qkv, ao, frag, lse))
+    if _vit_flash_route(o, N, hd, qkv.dtype):
+        ao, (_, _, lse) = o.global_attn_fwd(qkv, nB, N, nH, scale, out=out)
+        if not save:
+            return ao, ()
+        tag = _flash_tag(qkv.device)
+        return ao, (qkv, ao, lse, tag, tag)
     ao, att = o.vit_attn_fwd(qkv, nB, N, nH, scale)
     if out is not None:
         out.copy_(ao)
@@ -1435,6 +1466,8 @@ def vit_attention(o, qkv, bqkv, nB, N, nH, scale, save, out=None):
 
 
 def vit_attention_bwd(o, dao, att, bqkv, nB, N, nH, scale, dqkv_out=None):
+    if len(att) == 5:  # the flash route: (qkv, out, log-sum-exp, tag, tag)
+        return o.global_attn_bwd(dao, att[:3], nB, N, nH, scale, dqkv=dqkv_out)
     if len(att) >= 3:  # the windowed routes: (qkv, out, bias fragments[, log-sum-exp of the 224-slot kernels])
         qkv, ao, frag = att[:3]
         lse = att[3] if len(att) == 4 else None

@@ -83,7 +83,8 @@ def relative_position_index(ws):
 
 # esvit_query questions (include/esvit_hip.h)
 (Q_ATTN_FRAG_ELEMS, Q_ATTN_LSE_ELEMS, Q_ATTN_BWD_PARTS, Q_ATTN_BWD_PAD_ROWS, Q_LN_BWD_BLOCKS, Q_COLSUM_BLOCKS, Q_COL_REDUCE_BLOCKS,
- Q_UPDATE_CHUNK_ELEMS, Q_MLP_FUSED, Q_AUG_MAX_BOX, Q_JPEG_WORKSPACE, Q_RESIZE_FITS, Q_CHUNK_ATTN_WS, Q_TOPK_WS, Q_PROBE_CE_REG_ROW) = range(1, 16)
+ Q_UPDATE_CHUNK_ELEMS, Q_MLP_FUSED, Q_AUG_MAX_BOX, Q_JPEG_WORKSPACE, Q_RESIZE_FITS, Q_CHUNK_ATTN_WS, Q_TOPK_WS, Q_PROBE_CE_REG_ROW,
+ Q_GLOBAL_ATTN_WS) = range(1, 17)
 
 
 def query(what, a=0, b=0, c=0):
@@ -1234,6 +1235,47 @@ def vit_attn_bwd(dout, saved, B, N, nH, scale, chunk=None):
     _bmm(dp, qkvh[1], Np, hd, Np, b_kstrided=1, out=dqkvh[0])                  # dq = dS k
     _bmm(dp, qkvh[0], Np, hd, Np, a_kstrided=1, b_kstrided=1, out=dqkvh[1])   # dk = dS^T q
     return heads_merge(dqkvh.view(3, B, nH, Np, hd), N)
+
+
+# ---- flash attention for crops of any length (csrc/flash_attn.hip): the scores stay on the chip, nothing grows with N^2 -------------
+ATTN_GLOBAL = 0x20000000  # ESVIT_ATTN_GLOBAL: passed as ws, selects the global mode of esvit_window_attn_fwd / _bwd
+
+
+def global_attn_supported(dtype, hd):
+    """the flash route exists for this shape: bf16 (the fp32 parity mode keeps the batched-GEMM route), head_dim 32 / 64"""
+    return dtype == torch.bfloat16 and hd in (32, 64)
+
+
+def global_attn_fwd(qkv, B, N, nH, scale, out=None):
+    """Attention.forward between the projections (vision_transformer.py:76-83) for any N in one fused kernel: qkv [B * N, 3C] ->
+    (out [B * N, C], saved = (qkv, out, lse fp32 [B, nH, N])).  out: optional destination whose first B * N rows are written."""
+    qkv = _actc(qkv)
+    Cc = qkv.shape[1] // 3
+    assert qkv.shape[0] == B * N
+    if out is None:
+        out = torch.empty((B * N, Cc), dtype=qkv.dtype, device=qkv.device)
+    assert out.dtype == qkv.dtype and out.is_contiguous() and out.shape[0] >= B * N and out.shape[1] == Cc
+    lse = torch.empty((B, nH, N), dtype=torch.float32, device=qkv.device)
+    ws = workspace(query(Q_GLOBAL_ATTN_WS, B * nH, N, 0), qkv.device, slot=3)
+    check(lib.esvit_window_attn_fwd(_code(qkv.dtype), _p(qkv), None, None, N, None, ATTN_GLOBAL, _p(ws), None, 1, B, N, nH, Cc // nH,
+                                    float(scale), _p(out), _p(lse), None, _stream()), "window_attn_fwd(global)")
+    return out, (qkv, out, lse)
+
+
+def global_attn_bwd(dout, saved, B, N, nH, scale, dqkv=None):
+    """gradient of global_attn_fwd with respect to qkv: dout [B * N, C] -> dqkv [B * N, 3C] (dqkv: optional destination whose first
+    B * N rows are written)"""
+    qkv, out, lse = saved
+    dout = _actc(dout)
+    Cc = qkv.shape[1] // 3
+    assert dout.shape == (B * N, Cc) and out.shape[0] >= B * N and dout.dtype == qkv.dtype
+    if dqkv is None:
+        dqkv = torch.empty_like(qkv)
+    assert dqkv.dtype == qkv.dtype and dqkv.is_contiguous() and dqkv.shape[0] >= B * N and dqkv.shape[1] == 3 * Cc
+    ws = workspace(query(Q_GLOBAL_ATTN_WS, B * nH, N, 1), qkv.device, slot=3)
+    check(lib.esvit_window_attn_bwd(_code(qkv.dtype), _p(qkv), None, None, N, _p(dout), _p(out), _p(lse), None, ATTN_GLOBAL, _p(ws), None,
+                                    1, B, N, nH, Cc // nH, float(scale), _p(dqkv), None, None, _stream()), "window_attn_bwd(global)")
+    return dqkv
 
 
 # ---- fused sliding-chunk attention (csrc/chunk_attn.hip): the scores stay on the chip, nothing grows with N^2 --------------------

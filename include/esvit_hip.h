@@ -56,6 +56,8 @@ const char* esvit_last_error(void);
  *                                              with N once the splits saturate), ESVIT_ERR_ARG for k outside 1 .. 256
  *   ESVIT_Q_PROBE_CE_REG_ROW ()                longest row (floats) the class-index mode of esvit_dino_ce_fwd_bwd keeps in registers (one wave
  *                                              per row); longer rows take one workgroup per row and three sweeps
+ *   ESVIT_Q_GLOBAL_ATTN_WS (nB*nH, L, backward) floats of the scratch the global mode of esvit_window_attn_fwd (backward = 0: none) /
+ *                                              esvit_window_attn_bwd (backward = 1) takes through bias_frag_ws; linear in L
  * Unknown `what` returns ESVIT_ERR_ARG. */
 #define ESVIT_Q_ATTN_FRAG_ELEMS 1
 #define ESVIT_Q_ATTN_LSE_ELEMS 2
@@ -72,6 +74,7 @@ const char* esvit_last_error(void);
 #define ESVIT_Q_CHUNK_ATTN_WS 13
 #define ESVIT_Q_TOPK_WS 14
 #define ESVIT_Q_PROBE_CE_REG_ROW 15
+#define ESVIT_Q_GLOBAL_ATTN_WS 16
 int64_t esvit_query(int what, int64_t a, int64_t b, int64_t c);
 
 /* ---- host-side integer index maps (bit-exact vs reference) -------------
@@ -351,8 +354,21 @@ int esvit_attn_branch_fwd(int dtype, const float* x, const float* gamma, const f
  *   hd           32, 48 or 64;  dtype bf16 only (ESVIT_ERR_ARG otherwise, before any launch: the fp32 parity mode keeps the dense route)
  *   qkv_bias, rel_table, region_ids, attn_out, dbias_ws, dpad_ws: not used, pass NULL
  * Every row of out / dqkv is written; no atomics: two launches give identical bits.
+ *
+ * Global mode (ws = ESVIT_ATTN_GLOBAL; flash_attn.hip): plain softmax attention of every token of an image over every token
+ * of that image (vision_transformer.py:76-83) for crops of ANY length, fused -- online softmax over 64-key blocks, no tensor grows
+ * with L^2, nothing is padded in memory.  The arguments mean, in this mode:
+ *   ws           ESVIT_ATTN_GLOBAL alone (together with ESVIT_ATTN_SLIDING_CHUNK: ESVIT_ERR_ARG)
+ *   L            tokens per image, >= 1;  nW = 1;  N = L
+ *   bias_frag_ws fp32 scratch of esvit_query(ESVIT_Q_GLOBAL_ATTN_WS, nB * nH, L, 0 forward | 1 backward) floats (forward: none, may be NULL)
+ *   lse          fp32 [nB, nH, L], written by the forward and read by the backward (required), as out / fwd_out is
+ *   hd           32 or 64;  dtype bf16 only (ESVIT_ERR_ARG otherwise, before any launch: the fp32 parity mode keeps the batched-GEMM route)
+ *   scale        multiplies the fp32 scores (q enters the product as the bf16 it is)
+ *   win2tok, qkv_bias, rel_table, region_ids, attn_out, dbias_ws, dpad_ws: not used, pass NULL
+ * Every row of out / dqkv is written by exactly one workgroup; no atomics: two launches give identical bits.
  */
 #define ESVIT_ATTN_SLIDING_CHUNK 0x40000000
+#define ESVIT_ATTN_GLOBAL 0x20000000
 int esvit_window_attn_fwd(int dtype, const void* qkv, const float* qkv_bias, const int32_t* win2tok, int L,
                           const float* rel_table, int ws, float* bias_frag_ws, const int32_t* region_ids, int nW, int nB,
                           int N, int nH, int hd, float scale, void* out, float* lse, float* attn_out,
