@@ -97,7 +97,6 @@ constexpr int AB_FRAG = 16 * 256;   // floats per head of the fragment-order bia
 constexpr int K_BYTES = 64 * 64;    // K image [64 slots][32 d] bf16: 64-byte rows, 16-byte units XOR-swizzled by (row >> 1) & 3
 constexpr int VT_LD = 136;          // V^T image [32 d][64 slots] bf16: 128-byte rows padded to 136 (8-byte fragment reads, conflict-free)
 constexpr int KV_BYTES = K_BYTES + ((32 * VT_LD + 1023) / 1024) * 1024;  // one K | V^T pair
-constexpr unsigned AB_OOB = 0x7ffffff0u;
 constexpr float LOG2E = 1.4426950408889634f;
 
 template <int I>
@@ -123,7 +122,7 @@ __device__ __forceinline__ void mem_fence_compiler() { asm volatile("" ::: "memo
 // optimiser, which otherwise turns the select into two predicated copies of the access.
 __device__ __forceinline__ unsigned row_off(int row, unsigned off) {
     const unsigned m = (unsigned)(row >> 31);
-    unsigned v = (off & ~m) | (AB_OOB & m);
+    unsigned v = (off & ~m) | (BUF_OOB & m);
     asm volatile("" : "+v"(v));
     return v;
 }
@@ -204,8 +203,8 @@ __device__ __forceinline__ void attn_branch_fwd_body(const ABParams& p) {
     const int vb = (8 * (c >> 2) + (c & 3)) * 4;  // this lane's channel inside the head's 32 v biases (+ 16 t bytes)
 
     // ---- weight streaming ----
-    const __amdgpu_buffer_rsrc_t rp = mk_rsrc(p.Wproj, (long)C * C * 2);
-    const __amdgpu_buffer_rsrc_t rbf = mk_rsrc(p.bias_frag, (long)NH * AB_FRAG * 4);
+    const __amdgpu_buffer_rsrc_t rp = make_rsrc(p.Wproj, (long)C * C * 2);
+    const __amdgpu_buffer_rsrc_t rbf = make_rsrc(p.bias_frag, (long)NH * AB_FRAG * 4);
     // Every wave issues exactly PPQ + PPP pieces per step and no memory operation of the loop sits under a branch: the step's
     // closing wait counts operations, and hipcc's own wait insertion (for the register loads) is exact only on branch-free code.
     // A piece beyond the slice reads through an out-of-range offset (zeros) into the dummy KiB.
@@ -214,14 +213,14 @@ __device__ __forceinline__ void attn_branch_fwd_body(const ABParams& p) {
     for (int i = 0; i < AC::PPQ; ++i) {
         const int piece = wave + NW * i;
         voffq[i] = piece < 3 * Cf::PA ? Cf::voff_a(piece % Cf::PA, lane)
-                                      : (piece == 3 * Cf::PA ? ((lane >> 3) < 3 ? (lane >> 3) : 2) * C * 4 + (lane & 7) * 16 : (int)AB_OOB);
+                                      : (piece == 3 * Cf::PA ? ((lane >> 3) < 3 ? (lane >> 3) : 2) * C * 4 + (lane & 7) * 16 : (int)BUF_OOB);
     }
 #pragma unroll
     for (int i = 0; i < AC::PPP; ++i) {
         const int piece = wave + NW * i;
         const int pp = piece * 64 + lane;
         const int r = pp >> 2, u = pp & 3;
-        voffp[i] = piece < Cf::PB ? (r * C + Cf::swb(u, r) * 8) * 2 : (int)AB_OOB;
+        voffp[i] = piece < Cf::PB ? (r * C + Cf::swb(u, r) * 8) * 2 : (int)BUF_OOB;
     }
     auto issue_q = [&](int h, int buf) {  // q | k | v rows + biases of head h -> ring slot buf
 #pragma unroll
@@ -230,7 +229,7 @@ __device__ __forceinline__ void attn_branch_fwd_body(const ABParams& p) {
             const int part = piece / Cf::PA;  // 0..2: q | k | v rows, 3: the bias piece (another descriptor, same instruction)
             const bool isb = piece == 3 * Cf::PA;
             const int dst = piece < AC::NPQ ? AC::OFF_Q + buf * AC::QBUF + piece * 1024 : AC::OFF_DUMMY;
-            const __amdgpu_buffer_rsrc_t r = mk_rsrc(isb ? (const void*)p.bqkv : (const void*)p.Wqkv, isb ? 3L * C * 4 : 3L * C * C * 2);
+            const __amdgpu_buffer_rsrc_t r = make_rsrc(isb ? (const void*)p.bqkv : (const void*)p.Wqkv, isb ? 3L * C * 4 : 3L * C * C * 2);
             __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (lds_void*)(smem + dst), 16, voffq[i], isb ? h * 32 * 4 : (part * C + h * 32) * C * 2, 0, 0);
         }
     };
@@ -248,15 +247,15 @@ __device__ __forceinline__ void attn_branch_fwd_body(const ABParams& p) {
     const int iters = (groups + gridDim.x - 1) / gridDim.x;
     const int steps = iters * NH;
     const bool masked = p.region_ids != nullptr;
-    const __amdgpu_buffer_rsrc_t rx = mk_rsrc(p.x, p.rows * C * 4), ry = mk_rsrc(p.y, p.rows * C * 4);
-    const __amdgpu_buffer_rsrc_t rrs = mk_rsrc(p.rowscale, p.rowscale ? p.rows * 4 : 0);
+    const __amdgpu_buffer_rsrc_t rx = make_rsrc(p.x, p.rows * C * 4), ry = make_rsrc(p.y, p.rows * C * 4);
+    const __amdgpu_buffer_rsrc_t rrs = make_rsrc(p.rowscale, p.rowscale ? p.rows * 4 : 0);
     __amdgpu_buffer_rsrc_t rxw = rrs, rqkv = rrs, rao = rrs, rmean = rrs, rrstd = rrs;
     if constexpr (SAVE) {
-        rxw = mk_rsrc(p.xw, p.rows * C * 2);
-        rqkv = mk_rsrc(p.qkv, p.rows * 3L * C * 2);
-        rao = mk_rsrc(p.ao, p.rows * C * 2);
-        rmean = mk_rsrc(p.mean, p.rows * 4);
-        rrstd = mk_rsrc(p.rstd, p.rows * 4);
+        rxw = make_rsrc(p.xw, p.rows * C * 2);
+        rqkv = make_rsrc(p.qkv, p.rows * 3L * C * 2);
+        rao = make_rsrc(p.ao, p.rows * C * 2);
+        rmean = make_rsrc(p.mean, p.rows * 4);
+        rrstd = make_rsrc(p.rstd, p.rows * 4);
     }
 
     // window `it` of this wave: two unconditional loads (clamped indices, see above) whose results are only LOOKED AT a window
@@ -311,7 +310,7 @@ __device__ __forceinline__ void attn_branch_fwd_body(const ABParams& p) {
     for (int i = 0; i < NXL; ++i) xn[i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rx, xoff(row_nxt, i), 0, 0));
     const bool has_rs = p.rowscale != nullptr;
     rs_n = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rrs, row_off(row_nxt, (unsigned)row_nxt * 4), 0, 0));
-    wait_vm<0>();
+    wait_vmcnt<0>();
     __syncthreads();
 
     // the attention + projection half of a step: pair (window of `row_cur`, head hp); kvo: LDS offset of the window's K image of
@@ -378,8 +377,8 @@ __device__ __forceinline__ void attn_branch_fwd_body(const ABParams& p) {
         }
         TL(4);
         if constexpr (SAVE) {  // attention output row, channels 32 hp + (d = 4g + e | 16 + 4g + e) -> 8 consecutive after the row swap
-            unsigned x0 = pack2(o[0][0] * inv, o[0][1] * inv), x1 = pack2(o[0][2] * inv, o[0][3] * inv);
-            unsigned y0 = pack2(o[1][0] * inv, o[1][1] * inv), y1 = pack2(o[1][2] * inv, o[1][3] * inv);
+            unsigned x0 = esvit_pack2_bf16(o[0][0] * inv, o[0][1] * inv), x1 = esvit_pack2_bf16(o[0][2] * inv, o[0][3] * inv);
+            unsigned y0 = esvit_pack2_bf16(o[1][0] * inv, o[1][1] * inv), y1 = esvit_pack2_bf16(o[1][2] * inv, o[1][3] * inv);
             row_swap(x0, y0);
             row_swap(x1, y1);
             sv_o = u32x4{x0, x1, y0, y1};
@@ -513,7 +512,7 @@ __device__ __forceinline__ void attn_branch_fwd_body(const ABParams& p) {
                             }
                         }
                         if constexpr (SAVE) {
-                            unsigned x0 = pack2(hv[0], hv[1]), x1 = pack2(hv[2], hv[3]), y0 = pack2(hv[4], hv[5]), y1 = pack2(hv[6], hv[7]);
+                            unsigned x0 = esvit_pack2_bf16(hv[0], hv[1]), x1 = esvit_pack2_bf16(hv[2], hv[3]), y0 = esvit_pack2_bf16(hv[4], hv[5]), y1 = esvit_pack2_bf16(hv[6], hv[7]);
                             row_swap(x0, y0);
                             row_swap(x1, y1);
                             const unsigned vo = row_off(row_q, (unsigned)row_q * (C * 2) + (32 * ks + 16 * (g & 1) + 4 * (g & ~1)) * 2);
@@ -570,7 +569,7 @@ __device__ __forceinline__ void attn_branch_fwd_body(const ABParams& p) {
                         }
                     }
                     u32x4 pk = {};
-                    if constexpr (TRANSPOSED && (part != 0 || SAVE)) pk = u32x4{pack2(a0[0], a0[1]), pack2(a0[2], a0[3]), pack2(a1[0], a1[1]), pack2(a1[2], a1[3])};
+                    if constexpr (TRANSPOSED && (part != 0 || SAVE)) pk = u32x4{esvit_pack2_bf16(a0[0], a0[1]), esvit_pack2_bf16(a0[2], a0[3]), esvit_pack2_bf16(a1[0], a1[1]), esvit_pack2_bf16(a1[2], a1[3])};
                     if constexpr (part == 0) {
                         const float qs = p.scale * LOG2E;  // scores in the base-2 domain
 #pragma unroll
@@ -583,8 +582,8 @@ __device__ __forceinline__ void attn_branch_fwd_body(const ABParams& p) {
                         *reinterpret_cast<u32x4*>(smem + kvo + kw) = pk;
                         if constexpr (SAVE) sv_k = pk;
                     } else {
-                        *reinterpret_cast<u32x2*>(smem + kvo + K_BYTES + vw) = u32x2{pack2(v0[0], v0[1]), pack2(v0[2], v0[3])};
-                        *reinterpret_cast<u32x2*>(smem + kvo + K_BYTES + vw + 4 * VT_LD) = u32x2{pack2(v1[0], v1[1]), pack2(v1[2], v1[3])};
+                        *reinterpret_cast<u32x2*>(smem + kvo + K_BYTES + vw) = u32x2{esvit_pack2_bf16(v0[0], v0[1]), esvit_pack2_bf16(v0[2], v0[3])};
+                        *reinterpret_cast<u32x2*>(smem + kvo + K_BYTES + vw + 4 * VT_LD) = u32x2{esvit_pack2_bf16(v1[0], v1[1]), esvit_pack2_bf16(v1[2], v1[3])};
                         if constexpr (SAVE) sv_v = pk;
                     }
                 });
@@ -616,7 +615,7 @@ __device__ __forceinline__ void attn_branch_fwd_body(const ABParams& p) {
             // allowance of rounds 5-6 -- row loads + this step's output / side-output stores -- could be met with a weight slice still on its
             // way; profiles/r06_gemm_astat_probe.txt.  Same step time.)
             constexpr int LATE = NPFL;
-            if (!AC::RES || it == 0) wait_vm<LATE>();
+            if (!AC::RES || it == 0) wait_vmcnt<LATE>();
             TL(8);
             chunk_barrier();
             TL(9);

@@ -6,7 +6,7 @@
 //   local queries   chunk_fwd_local: one workgroup per (image, head, chunk), four waves, one 16-slot query tile each (49 live of 64
 //                   slots).  K and V of the neighbourhood [globals | 21 x 21 square, clipped] are staged once by slot (448 slots,
 //                   dead slots are zero rows whose scores are set to -1e30); a wave forms S^T = scale K Q^T for its tile (28 MFMA
-//                   tiles in registers), the softmax in registers, P V with the transpose read of V, as window_attn_big.hip's
+//                   tiles in registers), the softmax in registers, P V with the transpose read of V (mfma.h: frag_v_perm), as window_attn_big.hip's
 //                   attn_big_fwd3 does for 224 slots.  The per-query log-sum-exp is saved.
 //   global queries  nglo rows against all L keys: chunk_fwd_global_part walks 512-key ranges on the VALU (nglo L hd products: a
 //                   thousandth of the local work), one (max, sum, P V) partial per range; chunk_fwd_global_combine merges the
@@ -43,7 +43,6 @@ constexpr int WAVES = OWS / 16;     // 4
 constexpr int NTHR = WAVES * 64;
 constexpr int GSPLIT = 512;         // tokens per range of the global-token kernels
 constexpr int GMAX = 8;             // rows reserved per range for the global tokens (nglo <= 7)
-constexpr unsigned OOB = 0x7ffffff0u;  // past every buffer range (< 2 GiB), as window_attn.hip
 typedef int i32x4 __attribute__((ext_vector_type(4)));
 
 template <int HD>
@@ -88,7 +87,7 @@ struct RowStage {
         for (int it = 0; it < ITERS; ++it) {
             const int v = tid + it * NT;
             const int rl = v / Cfg::VPRP, dv = v % Cfg::VPRP;
-            bf16x8 y = __builtin_bit_cast(bf16x8, esvit_u32x4{0u, 0u, 0u, 0u});
+            bf16x8 y = __builtin_bit_cast(bf16x8, u32x4{0u, 0u, 0u, 0u});
             if (v < NROWS * Cfg::VPRP && dv < Cfg::VPR) {
                 const int t = tok[rl];
                 if (t >= 0) y = *reinterpret_cast<const bf16x8*>(g + (tok_base + t) * row_stride + dv * 8);
@@ -105,43 +104,6 @@ struct RowStage {
         }
     }
 };
-
-// B operand of a product over 32 neighbourhood slots from two score tiles in registers, and the matching A operand read of a
-// [slot][channel] image (window_attn_big.hip: frag_p_regs / frag_v_perm)
-__device__ __forceinline__ Frag<bf16> frag_regs(const f32x4& lo, const f32x4& hi) {
-    Frag<bf16> f;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-        f.v[e] = (bf16)lo[e];
-        f.v[4 + e] = (bf16)hi[e];
-    }
-    return f;
-}
-__device__ __forceinline__ Frag<bf16> frag_perm(const bf16* img, int LD, int d0, int ks, int c, int g) {
-    typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
-    Frag<bf16> f;
-    const bf16* p0 = img + (32 * ks + 4 * g + (c >> 2)) * LD + d0 + 4 * (c & 3);
-    const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(p0));
-    const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(p0 + 16 * LD));
-    const s16x8 both = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-    f.v = __builtin_bit_cast(bf16x8, both);
-    return f;
-}
-
-// one 16-slot tile of result rows from transposed accumulators acc[j][r] = result[channel 16 j + 4g + r][slot c]: 16-byte pieces
-// through a buffer descriptor over the image's rows (channels >= HD, the zero padding of head_dim 48, are dropped)
-template <int HD>
-__device__ __forceinline__ void store_tile_rows(const f32x4 (&acc)[CCfg<HD>::DT], float mul, bf16* __restrict__ img_rows, int L, int row_elems,
-                                                int col0, int tok, int g) {
-    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(img_rows, 0, (int)((long)L * row_elems * 2), 0x00020000);
-#pragma unroll
-    for (int j = 0; j < CCfg<HD>::DT; j += 2) {
-        const esvit_u32x4 x = esvit_pack_tile_pair_bf16(acc[j] * mul, acc[j + 1] * mul);  // (every lane takes part in the exchange)
-        const int ch = 16 * j + esvit_tile_pair_ch0(g);
-        const bool ok = tok >= 0 && ch < HD;
-        buffer_store_b128(x, rs, ok ? (unsigned)(tok * row_elems + ch) * 2u : OOB, (unsigned)col0 * 2u);
-    }
-}
 
 // does this wave's tile of own slots hold a live token at all (wave-uniform)
 __device__ __forceinline__ bool tile_live(const int* owntok, int wave, int lane) {
@@ -225,11 +187,11 @@ __global__ __launch_bounds__(NTHR) void chunk_fwd_local_kernel(const bf16* __res
     for (int j = 0; j < DT; ++j) o[j] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int ks = 0; ks < NBS / 32; ++ks) {
-        const Frag<bf16> pf = frag_regs(p[2 * ks] * inv, p[2 * ks + 1] * inv);
+        const Frag<bf16> pf = frag_p_regs<bf16>(p[2 * ks] * inv, p[2 * ks + 1] * inv);
 #pragma unroll
-        for (int j = 0; j < DT; ++j) mma(frag_perm(Vs, LDQ, 16 * j, ks, c, g), pf, o[j]);  // O^T [channel][query]: operands exchanged
+        for (int j = 0; j < DT; ++j) mma(frag_v_perm<bf16>(Vs, LDQ, 16 * j, ks, c, g), pf, o[j]);  // O^T [channel][query]: operands exchanged
     }
-    store_tile_rows<HD>(o, 1.f, out + tok_base * C, L, C, u.h * HD, tok, g);
+    store_tile_rows<HD, Cfg::HDP>(o, 1.f, out + tok_base * C, L, C, u.h * HD, tok, g);
 }
 
 // -------------------------------------------------------------------------------------------------------------
@@ -310,11 +272,11 @@ __global__ __launch_bounds__(NTHR) void chunk_bwd_dq_local_kernel(const bf16* __
             for (int kd = 0; kd < KS; ++kd) mma(frag_kc<bf16>(Vs, LDQ, 16 * i, 32 * kd, c, g), of[kd], dp);
             ds2[a] = pj[i] * (dp - dl);
         }
-        const Frag<bf16> sf = frag_regs(ds2[0], ds2[1]);
+        const Frag<bf16> sf = frag_p_regs<bf16>(ds2[0], ds2[1]);
 #pragma unroll
-        for (int j = 0; j < DT; ++j) mma(frag_perm(Ks, LDQ, 16 * j, ks, c, g), sf, acc[j]);  // dQ^T [channel][query]
+        for (int j = 0; j < DT; ++j) mma(frag_v_perm<bf16>(Ks, LDQ, 16 * j, ks, c, g), sf, acc[j]);  // dQ^T [channel][query]
     }
-    store_tile_rows<HD>(acc, scale, dqkv + tok_base * 3 * C, L, 3 * C, u.h * HD, tok, g);
+    store_tile_rows<HD, Cfg::HDP>(acc, scale, dqkv + tok_base * 3 * C, L, 3 * C, u.h * HD, tok, g);
 }
 
 // -------------------------------------------------------------------------------------------------------------
@@ -391,11 +353,11 @@ __global__ __launch_bounds__(NTHR) void chunk_bwd_dkv_local_kernel(const bf16* _
         for (int j = 0; j < DT; ++j) av[j] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int ks = 0; ks < NBS / 32; ++ks) {
-            const Frag<bf16> pf = frag_regs(p[2 * ks], p[2 * ks + 1]);
+            const Frag<bf16> pf = frag_p_regs<bf16>(p[2 * ks], p[2 * ks + 1]);
 #pragma unroll
-            for (int j = 0; j < DT; ++j) mma(frag_perm(Os, LDQ, 16 * j, ks, c, g), pf, av[j]);  // dV^T [channel][key]
+            for (int j = 0; j < DT; ++j) mma(frag_v_perm<bf16>(Os, LDQ, 16 * j, ks, c, g), pf, av[j]);  // dV^T [channel][key]
         }
-        store_tile_rows<HD>(av, 1.f, dqkv + tok_base * 3 * C, L, 3 * C, 2 * C + u.h * HD, tok, g);
+        store_tile_rows<HD, Cfg::HDP>(av, 1.f, dqkv + tok_base * 3 * C, L, 3 * C, 2 * C + u.h * HD, tok, g);
     }
     // dS = P o (dP - delta), dP[q][key] = sum_d dO[q][d] V[key][d]; dS overwrites P
 #pragma unroll
@@ -412,11 +374,11 @@ __global__ __launch_bounds__(NTHR) void chunk_bwd_dkv_local_kernel(const bf16* _
         for (int j = 0; j < DT; ++j) ak[j] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int ks = 0; ks < NBS / 32; ++ks) {
-            const Frag<bf16> sf = frag_regs(p[2 * ks], p[2 * ks + 1]);
+            const Frag<bf16> sf = frag_p_regs<bf16>(p[2 * ks], p[2 * ks + 1]);
 #pragma unroll
-            for (int j = 0; j < DT; ++j) mma(frag_perm(Qs, LDQ, 16 * j, ks, c, g), sf, ak[j]);  // dK^T [channel][key]
+            for (int j = 0; j < DT; ++j) mma(frag_v_perm<bf16>(Qs, LDQ, 16 * j, ks, c, g), sf, ak[j]);  // dK^T [channel][key]
         }
-        store_tile_rows<HD>(ak, scale, dqkv + tok_base * 3 * C, L, 3 * C, C + u.h * HD, tok, g);
+        store_tile_rows<HD, Cfg::HDP>(ak, scale, dqkv + tok_base * 3 * C, L, 3 * C, C + u.h * HD, tok, g);
     }
 }
 

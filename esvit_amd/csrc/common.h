@@ -22,6 +22,8 @@ typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 typedef short s16x4 __attribute__((ext_vector_type(4)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
+typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 
 // ---------------------------------------------------------------------------
 // error plumbing (host)
@@ -44,6 +46,9 @@ void esvit_set_error(const char* fmt, ...);
             return ESVIT_ERR_HIP;                                                       \
         }                                                                               \
     } while (0)
+
+// every entry point takes its stream as a void*
+#define STREAM(s_) hipStream_t stream = reinterpret_cast<hipStream_t>(s_)
 
 // ---------------------------------------------------------------------------
 // element access helpers: activations are stored either as f32 or bf16
@@ -107,6 +112,34 @@ __device__ __forceinline__ Vec16<T> zero16() {
 }
 
 // ---------------------------------------------------------------------------
+// raw buffers, counted waits and the barrier of the LDS-DMA loops
+// ---------------------------------------------------------------------------
+// descriptor over `bytes` bytes from `base` (what is left of an operand from a tile's first element, say), capped to the 32-bit
+// range field and to zero from below: a lane whose offset is at or past the range loads zeros and stores nothing
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* base, long bytes) {
+    const long capped = bytes > 0xfffffff0L ? 0xfffffff0L : (bytes < 0 ? 0 : bytes);
+    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, (int)capped, 0x00020000);
+}
+constexpr unsigned BUF_OOB = 0x7ffffff0u;  // a lane offset past every buffer range (ranges are below 2 GiB): "this lane takes no part"
+
+// counted wait: at most N of this wave's LDS-DMA loads still in flight (loads retire in order)
+template <int N>
+__device__ __forceinline__ void wait_vmcnt() {
+    static_assert(N >= 0 && N < 64, "vmcnt immediate");
+    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
+}
+
+// Workgroup barrier of the chunk loops.  NOT __syncthreads(): its fence makes hipcc emit s_waitcnt vmcnt(0) in front of the
+// s_barrier, which drains the LDS-DMA of the chunk after next (and, in the backward, the hidden-tile stores to HBM) at every
+// chunk -- the loop would run at memory latency.  The data hazards are covered explicitly: the counted vmcnt before the barrier
+// (this wave's DMA pieces of the next chunk have landed), lgkmcnt(0) (this wave's LDS reads of the current chunk have returned).
+__device__ __forceinline__ void chunk_barrier() {
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+    asm volatile("" ::: "memory");
+}
+
+// ---------------------------------------------------------------------------
 // 16-byte raw-buffer store with the uniform part of the address added to the per-lane offset instead of riding in the instruction's
 // SGPR offset field.  Measured on MI355X (tools/probe/diag_attn64b.py, tools/isa_store_hazard.py): with every CU fully occupied, a
 // `buffer_store_dwordx4 ... offen` with an SGPR offset that is DIRECTLY followed by a VALU write of its first data register stored the
@@ -114,11 +147,10 @@ __device__ __forceinline__ Vec16<T> zero16() {
 // then a write of its data VGPRs" wait state.  With a constant-zero offset field the compiler inserts that wait state itself.
 // (Out-of-range lanes stay out of range: the offsets are unsigned 32-bit and the ranges are below 2 GiB.)
 // ---------------------------------------------------------------------------
-typedef unsigned int esvit_u32x4 __attribute__((ext_vector_type(4)));
 template <int AUX = 0, typename V>
 __device__ __forceinline__ void buffer_store_b128(const V& data, __amdgpu_buffer_rsrc_t rsrc, unsigned lane_offset, unsigned uniform_offset) {
     static_assert(sizeof(V) == 16, "buffer_store_b128 takes 16 bytes");
-    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(esvit_u32x4, data), rsrc, (int)(lane_offset + uniform_offset), 0, AUX);
+    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, data), rsrc, (int)(lane_offset + uniform_offset), 0, AUX);
 }
 
 // ---------------------------------------------------------------------------
@@ -127,20 +159,36 @@ __device__ __forceinline__ void buffer_store_b128(const V& data, __amdgpu_buffer
 // is a 16-byte vector as it is.  bf16: two tiles t, t + 1 are packed to 2 x 2 dwords and one pair is exchanged between lanes g and
 // g ^ 1 (v_permlane16_swap), after which an even g holds channels 16 t + 4g .. + 7 and an odd g channels 16 (t + 1) + 4 (g - 1) .. + 7.
 // ---------------------------------------------------------------------------
-typedef unsigned int esvit_u32x2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ unsigned esvit_pack2_bf16(float a, float b) {
     typedef __bf16 bf16x2_ __attribute__((ext_vector_type(2)));
     const bf16x2_ v = {(bf16)a, (bf16)b};
     return __builtin_bit_cast(unsigned, v);
 }
-__device__ __forceinline__ esvit_u32x4 esvit_pack_tile_pair_bf16(const f32x4& t0, const f32x4& t1) {
+__device__ __forceinline__ u32x4 esvit_pack_tile_pair_bf16(const f32x4& t0, const f32x4& t1) {
     unsigned x0 = esvit_pack2_bf16(t0[0], t0[1]), x1 = esvit_pack2_bf16(t0[2], t0[3]);
     unsigned y0 = esvit_pack2_bf16(t1[0], t1[1]), y1 = esvit_pack2_bf16(t1[2], t1[3]);
-    const esvit_u32x2 a = __builtin_amdgcn_permlane16_swap(x0, y0, false, false), b = __builtin_amdgcn_permlane16_swap(x1, y1, false, false);
-    return esvit_u32x4{a[0], b[0], a[1], b[1]};
+    const u32x2 a = __builtin_amdgcn_permlane16_swap(x0, y0, false, false), b = __builtin_amdgcn_permlane16_swap(x1, y1, false, false);
+    return u32x4{a[0], b[0], a[1], b[1]};
 }
 // first channel (relative to tile t) of the 8 consecutive channels a lane holds after esvit_pack_tile_pair_bf16
 __device__ __forceinline__ int esvit_tile_pair_ch0(int g) { return 16 * (g & 1) + 4 * (g & ~1); }
+// one 16-column tile of bf16 result rows from transposed accumulators acc[j][r] = result[channel 16 j + 4g + r][column c]: 16-byte
+// pieces through a buffer descriptor over the `rows` rows of `row_elems` elements at img_rows; the lane's row is tok (< 0: not
+// stored), the tile's first channel sits at column col0 of the row.  HDP > HD: the accumulators carry the zero padding of a head
+// dim that is no multiple of 32 (chunk attention's 48 in 64), and channels >= HD are dropped.  (The image is below 2 GiB -- the entry
+// points check -- so its range needs no cap.)
+template <int HD, int HDP = HD>
+__device__ __forceinline__ void store_tile_rows(const f32x4 (&acc)[HDP / 16], float mul, bf16* __restrict__ img_rows, int rows, int row_elems,
+                                                int col0, int tok, int g) {
+    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(img_rows, 0, (int)((long)rows * row_elems * 2), 0x00020000);
+#pragma unroll
+    for (int j = 0; j < HDP / 16; j += 2) {
+        const u32x4 x = esvit_pack_tile_pair_bf16(acc[j] * mul, acc[j + 1] * mul);  // (every lane takes part in the exchange)
+        const int ch = 16 * j + esvit_tile_pair_ch0(g);
+        const bool ok = tok >= 0 && (HDP == HD || ch < HD);
+        buffer_store_b128(x, rs, ok ? (unsigned)(tok * row_elems + ch) * 2u : BUF_OOB, (unsigned)col0 * 2u);
+    }
+}
 
 // ---------------------------------------------------------------------------
 // butterfly steps across the four 16-lane rows of a wave on the VALU
@@ -263,13 +311,24 @@ __device__ __forceinline__ float erf_fast(float x) {
 }
 // erf-GELU (reference: nn.GELU default, "none" approximation) and its derivative
 __device__ __forceinline__ float gelu_f(float x) { return 0.5f * x * (1.f + erf_fast(x * 0.70710678118654752f)); }
-__device__ __forceinline__ float gelu_grad_f(float x) {  // one exponential: exp(-x^2 / 2) serves the erf fit and the density (as mlp_fused16's gelu_both)
+__device__ __forceinline__ float gelu_grad_f(float x) {  // one exponential: exp(-x^2 / 2) serves the erf fit and the density (as gelu_both below)
     const float ax = fabsf(x) * 0.70710678118654752f;
     const float t = __builtin_amdgcn_rcpf(1.f + 0.3275911f * ax);
     const float e = __expf(-0.5f * x * x);
     const float poly = t * (0.254829592f + t * (-0.284496736f + t * (1.421413741f + t * (-1.453152027f + t * 1.061405429f))));
     const float cdf = 0.5f * (1.f + copysignf(1.f - poly * e, x));
     return cdf + x * 0.39894228040143268f * e;
+}
+// exact erf-GELU and its derivative from ONE exponential: erf's exp(-u^2) with u = v / sqrt(2) is the Gaussian of GELU'
+__device__ __forceinline__ void gelu_both(float v, float& g, float& dg) {
+    const float av = fabsf(v) * 0.70710678118654752f;
+    const float t = __builtin_amdgcn_rcpf(1.f + 0.3275911f * av);
+    const float e = __expf(-0.5f * v * v);
+    const float poly = t * (0.254829592f + t * (-0.284496736f + t * (1.421413741f + t * (-1.453152027f + t * 1.061405429f))));
+    const float erfv = copysignf(1.f - poly * e, v);
+    const float cdf = 0.5f * (1.f + erfv);
+    g = v * cdf;
+    dg = cdf + v * 0.39894228040143268f * e;
 }
 
 // QuickGELU of the CvT feed-forward (cvt_v4_transformer.py:44-46) and its derivative

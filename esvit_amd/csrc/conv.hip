@@ -529,8 +529,6 @@ inline bool chan_aligned(int dtype, const void* p) { return (uintptr_t)p % chan_
 
 }  // namespace
 
-#define STREAM(s_) hipStream_t stream = reinterpret_cast<hipStream_t>(s_)
-
 extern "C" int esvit_conv_im2col(int dtype, const void* src, int nchw, int nB, int H, int W, int Cin, int k, int stride, int pad, int Ho,
                                  int Wo, int Kpad, void* cols, esvit_stream_t s_) {
     STREAM(s_);

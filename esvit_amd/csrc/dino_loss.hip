@@ -312,8 +312,6 @@ __global__ void region_match_kernel(const float* __restrict__ sim, int B, int S,
 
 }  // namespace
 
-#define STREAM(s_) hipStream_t stream = reinterpret_cast<hipStream_t>(s_)
-
 // probe.hip: the terms = 0 mode of esvit_dino_ce_fwd_bwd
 int esvit_i_probe_ce(const float* s, const int32_t* target, const float* row_w, int64_t Rs, int K, float* row_loss, float* ds, hipStream_t stream);
 

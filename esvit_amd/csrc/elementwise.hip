@@ -203,7 +203,6 @@ __global__ void center_ema_kernel(float* __restrict__ center, const float* __res
 
 }  // namespace
 
-#define STREAM(s_) hipStream_t stream = reinterpret_cast<hipStream_t>(s_)
 #define BAD_DTYPE(name)                        \
     esvit_set_error(name ": bad dtype");       \
     return ESVIT_ERR_ARG

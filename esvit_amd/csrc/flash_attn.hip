@@ -8,7 +8,7 @@
 //             once; K and V stream through a two-deep LDS ring in 64-key blocks (the next block's global loads are issued before the
 //             current block's MFMAs and stored after them: one barrier per block).  A wave forms S^T = K Q^T for its tile (4 MFMA tiles
 //             in registers: P lands in B-operand order), keeps a running max and sum per query in fp32, rescales O when the max moves,
-//             and adds P V with the transpose read of V, as chunk_attn.hip does for its 448 slots at once.  out = O / l,
+//             and adds P V with the transpose read of V (mfma.h: frag_v_perm), as chunk_attn.hip does for its 448 slots at once.  out = O / l,
 //             lse = m + log l.  Slots >= N of the last query / key block are zero rows in LDS; their scores are set to -1e30 before
 //             the max (the first key block always holds key 0, so the running max is finite from the first step); their output and lse
 //             rows are never stored.
@@ -35,7 +35,6 @@ constexpr int BLKT = 64;            // tokens per query block and per key block 
 constexpr int NT16 = BLKT / 16;     // 16-token tiles per block
 constexpr int WAVES = BLKT / 16;    // one 16-token tile of the workgroup's own block per wave
 constexpr int NTHR = WAVES * 64;
-constexpr unsigned OOB = 0x7ffffff0u;  // past every buffer range (< 2 GiB), as window_attn.hip
 
 template <int HD>
 struct FCfg {
@@ -59,7 +58,7 @@ struct RowStage {
         for (int it = 0; it < ITERS; ++it) {
             const int v = tid + it * NTHR;
             const int t = row0 + v / Cfg::VPR, dv = v % Cfg::VPR;
-            bf16x8 y = __builtin_bit_cast(bf16x8, esvit_u32x4{0u, 0u, 0u, 0u});
+            bf16x8 y = __builtin_bit_cast(bf16x8, u32x4{0u, 0u, 0u, 0u});
             if (t < N) y = *reinterpret_cast<const bf16x8*>(g + (long)t * row_stride + dv * 8);
             x[it] = y;
         }
@@ -72,42 +71,6 @@ struct RowStage {
         }
     }
 };
-
-// B operand of a product over 32 tokens from two score tiles in registers, and the matching A operand read of a [token][channel]
-// image (chunk_attn.hip: frag_regs / frag_perm)
-__device__ __forceinline__ Frag<bf16> frag_regs(const f32x4& lo, const f32x4& hi) {
-    Frag<bf16> f;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-        f.v[e] = (bf16)lo[e];
-        f.v[4 + e] = (bf16)hi[e];
-    }
-    return f;
-}
-__device__ __forceinline__ Frag<bf16> frag_perm(const bf16* img, int LD, int d0, int ks, int c, int g) {
-    typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
-    Frag<bf16> f;
-    const bf16* p0 = img + (32 * ks + 4 * g + (c >> 2)) * LD + d0 + 4 * (c & 3);
-    const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(p0));
-    const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(p0 + 16 * LD));
-    const s16x8 both = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-    f.v = __builtin_bit_cast(bf16x8, both);
-    return f;
-}
-
-// one 16-token tile of result rows from transposed accumulators acc[j][r] = result[channel 16 j + 4g + r][token c]: 16-byte pieces
-// through a buffer descriptor over the image's N rows (tok < 0: a slot >= N, not stored)
-template <int HD>
-__device__ __forceinline__ void store_tile_rows(const f32x4 (&acc)[FCfg<HD>::DT], float mul, bf16* __restrict__ img_rows, int N, int row_elems,
-                                                int col0, int tok, int g) {
-    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(img_rows, 0, (int)((long)N * row_elems * 2), 0x00020000);
-#pragma unroll
-    for (int j = 0; j < FCfg<HD>::DT; j += 2) {
-        const esvit_u32x4 x = esvit_pack_tile_pair_bf16(acc[j] * mul, acc[j + 1] * mul);  // (every lane takes part in the exchange)
-        const int ch = 16 * j + esvit_tile_pair_ch0(g);
-        buffer_store_b128(x, rs, tok >= 0 ? (unsigned)(tok * row_elems + ch) * 2u : OOB, (unsigned)col0 * 2u);
-    }
-}
 
 struct Unit {
     int z, b, h, blk;
@@ -208,9 +171,9 @@ __global__ __launch_bounds__(NTHR) void flash_fwd_kernel(const bf16* __restrict_
             for (int j = 0; j < DT; ++j) o[j] = o[j] * alpha;
 #pragma unroll
             for (int ks = 0; ks < BLKT / 32; ++ks) {
-                const Frag<bf16> pf = frag_regs(p[2 * ks], p[2 * ks + 1]);
+                const Frag<bf16> pf = frag_p_regs<bf16>(p[2 * ks], p[2 * ks + 1]);
 #pragma unroll
-                for (int j = 0; j < DT; ++j) mma(frag_perm(Vs, LDQ, 16 * j, ks, c, g), pf, o[j]);  // O^T: operands exchanged
+                for (int j = 0; j < DT; ++j) mma(frag_v_perm<bf16>(Vs, LDQ, 16 * j, ks, c, g), pf, o[j]);  // O^T: operands exchanged
             }
         }
         if (more) {  // the other half of the ring: every wave left it at the barrier that ended block kb - 1
@@ -246,7 +209,7 @@ __global__ __launch_bounds__(NTHR) void flash_delta_kernel(const bf16* __restric
 #pragma unroll
     for (int kd = 0; kd < KS; ++kd) {
         Frag<bf16> of, df;
-        of.v = df.v = __builtin_bit_cast(bf16x8, esvit_u32x4{0u, 0u, 0u, 0u});
+        of.v = df.v = __builtin_bit_cast(bf16x8, u32x4{0u, 0u, 0u, 0u});
         if (t < N) {
             of.v = *reinterpret_cast<const bf16x8*>(fout + off + 32 * kd);
             df.v = *reinterpret_cast<const bf16x8*>(dout + off + 32 * kd);
@@ -337,9 +300,9 @@ __global__ __launch_bounds__(NTHR) void flash_bwd_dq_kernel(const bf16* __restri
                         ds2[a][r] = pe * (dp[r] - dl);
                     }
                 }
-                const Frag<bf16> sf = frag_regs(ds2[0], ds2[1]);
+                const Frag<bf16> sf = frag_p_regs<bf16>(ds2[0], ds2[1]);
 #pragma unroll
-                for (int j = 0; j < DT; ++j) mma(frag_perm(Ks, LDQ, 16 * j, ks, c, g), sf, acc[j]);  // dQ^T += K^T dS^T
+                for (int j = 0; j < DT; ++j) mma(frag_v_perm<bf16>(Ks, LDQ, 16 * j, ks, c, g), sf, acc[j]);  // dQ^T += K^T dS^T
             }
         }
         if (more) {
@@ -447,11 +410,11 @@ __global__ __launch_bounds__(NTHR) void flash_bwd_dkv_kernel(const bf16* __restr
                         ds2[a][r] = pe * (dp[r] - d4[r]);
                     }
                 }
-                const Frag<bf16> pf = frag_regs(p2[0], p2[1]), sf = frag_regs(ds2[0], ds2[1]);
+                const Frag<bf16> pf = frag_p_regs<bf16>(p2[0], p2[1]), sf = frag_p_regs<bf16>(ds2[0], ds2[1]);
 #pragma unroll
                 for (int j = 0; j < DT; ++j) {
-                    mma(frag_perm(Os, LDQ, 16 * j, ks, c, g), pf, av[j]);  // dV^T += dO^T P
-                    mma(frag_perm(Qs, LDQ, 16 * j, ks, c, g), sf, ak[j]);  // dK^T += Q^T dS
+                    mma(frag_v_perm<bf16>(Os, LDQ, 16 * j, ks, c, g), pf, av[j]);  // dV^T += dO^T P
+                    mma(frag_v_perm<bf16>(Qs, LDQ, 16 * j, ks, c, g), sf, ak[j]);  // dK^T += Q^T dS
                 }
             }
         }

@@ -1,13 +1,11 @@
 // Shared pieces of the 16-token-per-wave fused kernels (mlp_fused16.hip, attn_branch.hip): LDS weight images with their
-// conflict-free swizzles, LDS-DMA plumbing, bf16 packing / row swaps, in-register LayerNorm statistics.  See mlp_fused16.hip for
-// the fragment conventions.  Everything here has internal linkage (included inside each translation unit once).
+// conflict-free swizzles, row swaps, in-register LayerNorm statistics, the bf16 tile store.  See mlp_fused16.hip for the fragment
+// conventions; descriptors, counted waits, the chunk barrier, bf16 packing and gelu_both are common.h's.  Everything here has internal
+// linkage (included inside each translation unit once).
 #pragma once
 #include "common.h"
 
 namespace {
-
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int HCH = 32;  // hidden units per chunk
 
@@ -48,29 +46,6 @@ struct Cfg16 {
     }
 };
 
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t mk_rsrc(const void* base, long bytes) {
-    const long capped = bytes > 0xfffffff0L ? 0xfffffff0L : (bytes < 0 ? 0 : bytes);
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, (int)capped, 0x00020000);
-}
-
-template <int N>
-__device__ __forceinline__ void wait_vm() {
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-
-// raw barrier of the chunk loops (NOT __syncthreads(): its fence drains vmcnt, i.e. the LDS-DMA in flight and the stores)
-__device__ __forceinline__ void chunk_barrier() {
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-}
-
-__device__ __forceinline__ unsigned pack2(float a, float b) {
-    typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-    const bf16x2 v = {(bf16)a, (bf16)b};
-    return __builtin_bit_cast(unsigned, v);
-}
-
 // lanes g (even) and g + 1 each hold two 4-element groups x | y.  Afterwards the even lane holds (own x, partner's x) and the
 // odd lane (partner's y, own y): v_permlane16_swap exchanges the odd 16-lane rows of its first operand with the even rows of
 // its second.
@@ -81,17 +56,6 @@ __device__ __forceinline__ void row_swap(unsigned& x, unsigned& y) {
 }
 
 __device__ __forceinline__ f32x4 mfma16(bf16x8 a, bf16x8 b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0); }
-
-__device__ __forceinline__ void gelu_both(float v, float& g, float& dg) {  // exact erf-GELU and GELU' from one exponential
-    const float av = fabsf(v) * 0.70710678118654752f;
-    const float t = __builtin_amdgcn_rcpf(1.f + 0.3275911f * av);
-    const float e = __expf(-0.5f * v * v);
-    const float poly = t * (0.254829592f + t * (-0.284496736f + t * (1.421413741f + t * (-1.453152027f + t * 1.061405429f))));
-    const float erfv = copysignf(1.f - poly * e, v);
-    const float cdf = 0.5f * (1.f + erfv);
-    g = v * cdf;
-    dg = cdf + v * 0.39894228040143268f * e;
-}
 
 // LayerNorm statistics of a token whose C channels are spread over the four lanes (c, g = 0..3); v: this lane's C / 4 values
 template <int N>
@@ -119,13 +83,11 @@ template <int MT>
 __device__ __forceinline__ void store_bf16_tiles(bf16* __restrict__ dst_row, const float (&v)[MT][4], int g, bool ok) {
 #pragma unroll
     for (int mt = 0; mt < MT; mt += 2) {
-        unsigned x0 = pack2(v[mt][0], v[mt][1]), x1 = pack2(v[mt][2], v[mt][3]);
-        unsigned y0 = pack2(v[mt + 1][0], v[mt + 1][1]), y1 = pack2(v[mt + 1][2], v[mt + 1][3]);
-        row_swap(x0, y0);
-        row_swap(x1, y1);
-        // even g: tile mt, channels 4g .. 4g+7;  odd g: tile mt + 1, channels 4(g-1) .. 4(g-1)+7
+        const u32x4 x = esvit_pack_tile_pair_bf16(f32x4{v[mt][0], v[mt][1], v[mt][2], v[mt][3]}, f32x4{v[mt + 1][0], v[mt + 1][1], v[mt + 1][2], v[mt + 1][3]});
+        // even g: tile mt, channels 4g .. 4g+7;  odd g: tile mt + 1, channels 4(g-1) .. 4(g-1)+7  (= 16 mt + esvit_tile_pair_ch0(g);
+        // summed in that order the forward kernel's registers are allocated differently, so the sum stays as it was)
         const int ch = 16 * (mt + (g & 1)) + 4 * (g & ~1);
-        if (ok) *reinterpret_cast<u32x4*>(dst_row + ch) = u32x4{x0, x1, y0, y1};
+        if (ok) *reinterpret_cast<u32x4*>(dst_row + ch) = x;
     }
 }
 

@@ -392,24 +392,6 @@ __device__ __forceinline__ void gemm_epilogue(const esvit_gemm_desc& p, f32x4 (&
 // Inputs of row block i+1 (residual / GELU pre-activation) are requested before the stores of row block i: vmcnt retires in order.
 enum { EK_PLAIN = 0, EK_GELU = 1, EK_RES = 2, EK_GELU_BWD = 3 };
 
-__device__ __forceinline__ unsigned pack_bf16x2(float a, float b) {
-    typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
-    const bf16x2_t v = {(bf16)a, (bf16)b};
-    return __builtin_bit_cast(unsigned, v);
-}
-typedef unsigned u32x2_t __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
-
-// four columns (block j) | four columns (block j + 1) of one row per lane -> eight consecutive columns per lane:
-// even g: block j, columns 4g .. 4g+7;  odd g: block j + 1, columns 4(g-1) .. 4(g-1)+7
-__device__ __forceinline__ u32x4_t pair_rows(const f32x4& x, const f32x4& y) {
-    const unsigned x0 = pack_bf16x2(x[0], x[1]), x1 = pack_bf16x2(x[2], x[3]);
-    const unsigned y0 = pack_bf16x2(y[0], y[1]), y1 = pack_bf16x2(y[2], y[3]);
-    const u32x2_t s0 = __builtin_amdgcn_permlane16_swap(x0, y0, false, false);
-    const u32x2_t s1 = __builtin_amdgcn_permlane16_swap(x1, y1, false, false);
-    return u32x4_t{s0[0], s1[0], s0[1], s1[1]};
-}
-
 // Output stores of the direct epilogues.  Non-temporal stores were measured in round 4 (profiles/r04_p8_timeline.txt,
 // r04_gemm_instep_ab.txt, r04_pmc_traffic_nt.json): on the 256 x 128 two-set loop they stop the write stream from evicting the operand
 // panels (187 -> 163 us on 87040 x 1536 x 384); on the 128-row kernels of the step they change nothing in time (four-way same-box A/B)
@@ -426,12 +408,12 @@ __device__ __forceinline__ void store_stream(V* dst, const V& v) {
 // bf16 row block: v[j] = this lane's four columns of block j -> dst (the lane's row, at the wave tile's first column)
 template <int FN>
 __device__ __forceinline__ void store_row_bf16(bf16* dst, const f32x4 (&v)[FN], int g) {
-    const int pc = 16 * (g & 1) + 4 * (g & ~1);  // column of the lane's 8-vector inside a block pair
+    const int pc = esvit_tile_pair_ch0(g);  // column of the lane's 8-vector inside a block pair
 #pragma unroll
-    for (int j = 0; j + 1 < FN; j += 2) store_stream(reinterpret_cast<u32x4_t*>(dst + 16 * j + pc), pair_rows(v[j], v[j + 1]));
+    for (int j = 0; j + 1 < FN; j += 2) store_stream(reinterpret_cast<u32x4*>(dst + 16 * j + pc), esvit_pack_tile_pair_bf16(v[j], v[j + 1]));
     if constexpr (FN & 1)
-        store_stream(reinterpret_cast<u32x2_t*>(dst + 16 * (FN - 1) + 4 * g),
-                     u32x2_t{pack_bf16x2(v[FN - 1][0], v[FN - 1][1]), pack_bf16x2(v[FN - 1][2], v[FN - 1][3])});
+        store_stream(reinterpret_cast<u32x2*>(dst + 16 * (FN - 1) + 4 * g),
+                     u32x2{esvit_pack2_bf16(v[FN - 1][0], v[FN - 1][1]), esvit_pack2_bf16(v[FN - 1][2], v[FN - 1][3])});
 }
 
 // core: one FM x FN block of transposed 16 x 16 accumulator fragments whose first row / first column are wrow0 / wcol0
@@ -469,7 +451,7 @@ __device__ __forceinline__ void epilogue_direct_at(const esvit_gemm_desc& p, f32
 
     // inputs of the next row block: residual (4 fp32 per block) + DropPath scale, or the GELU pre-activation (4 bf16 per block)
     f32x4 in_r[2][KIND == EK_RES ? FN : 1];
-    u32x2_t in_a[2][KIND == EK_GELU_BWD ? FN : 1];
+    u32x2 in_a[2][KIND == EK_GELU_BWD ? FN : 1];
     float rs[2] = {1.f, 1.f};
     auto load_in = [&](auto ic) {
         constexpr int i = decltype(ic)::value;
@@ -481,7 +463,7 @@ __device__ __forceinline__ void epilogue_direct_at(const esvit_gemm_desc& p, f32
         } else if constexpr (KIND == EK_GELU_BWD) {
             const bf16* ap = auxp + x_off + 16 * i * x_ld;
 #pragma unroll
-            for (int j = 0; j < FN; ++j) in_a[i & 1][j] = *reinterpret_cast<const u32x2_t*>(ap + 16 * j);
+            for (int j = 0; j < FN; ++j) in_a[i & 1][j] = *reinterpret_cast<const u32x2*>(ap + 16 * j);
         }
     };
     if constexpr (KIND == EK_RES || KIND == EK_GELU_BWD) load_in(std::integral_constant<int, 0>{});
@@ -509,7 +491,7 @@ __device__ __forceinline__ void epilogue_direct_at(const esvit_gemm_desc& p, f32
             f32x4 x[FN];
 #pragma unroll
             for (int j = 0; j < FN; ++j) {
-                const u32x2_t a = in_a[i & 1][j];
+                const u32x2 a = in_a[i & 1][j];
                 x[j] = f32x4{__builtin_bit_cast(float, a[0] << 16), __builtin_bit_cast(float, a[0] & 0xffff0000u),
                              __builtin_bit_cast(float, a[1] << 16), __builtin_bit_cast(float, a[1] & 0xffff0000u)};
             }
@@ -907,18 +889,6 @@ struct DmaTile {
         return f;
     }
 };
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* base, long bytes_left) {
-    const long capped = bytes_left > 0xfffffff0L ? 0xfffffff0L : (bytes_left < 0 ? 0 : bytes_left);
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, (int)capped, 0x00020000);
-}
-
-// counted wait: at most N of this wave's LDS-DMA loads still in flight (loads retire in order)
-template <int N>
-__device__ __forceinline__ void wait_vmcnt() {
-    static_assert(N >= 0 && N < 64, "vmcnt immediate");
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
 
 // NBUF-deep ring of LDS tiles: NBUF-1 tiles are requested ahead; per k-tile ONE counted wait (only for the tile
 // about to be consumed -- later tiles stay in flight across the barrier) and ONE barrier.

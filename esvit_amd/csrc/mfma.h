@@ -69,3 +69,44 @@ __device__ __forceinline__ Frag<T> frag_ks(const T* lds, int LD, int r0, int k0,
     }
     return f;
 }
+
+// P V with P in registers (first used by window_attn_big.hip's second-generation forward).  Score tiles formed TRANSPOSED (S^T = K Q^T)
+// leave lane (c, g) with, for query c, the keys 16i + 4g + r -- for a 32-key k-step ks that is the 8 keys {32ks + 4g + e,
+// 32ks + 16 + 4g + e} of tiles lo = 2ks, hi = 2ks + 1.  An MFMA only needs A and B to agree on which key sits in which k-slot, so
+// those 8 values ARE an operand fragment of P V (frag_p_regs) if V's fragment is read from its natural [key][LD] image with the same
+// key permutation (frag_v_perm: channels d0 + c; bf16: two transpose reads 16 key rows apart).  P never goes through LDS.
+template <typename T>
+__device__ __forceinline__ Frag<T> frag_v_perm(const T* Vs, int LD, int d0, int ks, int c, int g) {
+    Frag<T> f;
+    if constexpr (sizeof(T) == 2) {
+        typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
+        const T* p0 = Vs + (32 * ks + 4 * g + (c >> 2)) * LD + d0 + 4 * (c & 3);
+        const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(p0));
+        const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(p0 + 16 * LD));
+        const s16x8 both = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
+        f.v = __builtin_bit_cast(bf16x8, both);
+    } else {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            f.v[e] = Vs[(32 * ks + 4 * g + e) * LD + d0 + c];
+            f.v[4 + e] = Vs[(32 * ks + 16 + 4 * g + e) * LD + d0 + c];
+        }
+    }
+    return f;
+}
+
+template <typename T>
+__device__ __forceinline__ Frag<T> frag_p_regs(const f32x4& lo, const f32x4& hi) {
+    Frag<T> f;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        if constexpr (sizeof(T) == 2) {
+            f.v[e] = (bf16)lo[e];
+            f.v[4 + e] = (bf16)hi[e];
+        } else {
+            f.v[e] = lo[e];
+            f.v[4 + e] = hi[e];
+        }
+    }
+    return f;
+}

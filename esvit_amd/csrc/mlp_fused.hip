@@ -46,8 +46,6 @@
 namespace {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int MLP_WAVES = 4;
 constexpr int MLP_ROWS = 32 * MLP_WAVES;  // token rows per workgroup
@@ -82,50 +80,12 @@ struct MlpCfg {
     }
 };
 
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t mk_rsrc(const void* base, long bytes) {
-    const long capped = bytes > 0xfffffff0L ? 0xfffffff0L : (bytes < 0 ? 0 : bytes);
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, (int)capped, 0x00020000);
-}
-
-template <int N>
-__device__ __forceinline__ void wait_vm() {
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-
-// Workgroup barrier of the chunk loops.  NOT __syncthreads(): its fence makes hipcc emit s_waitcnt vmcnt(0) in front of the
-// s_barrier, which drains the LDS-DMA of the chunk after next (and, in the backward, the hidden-tile stores to HBM) at every
-// chunk -- the loop would run at memory latency.  The data hazards are covered explicitly: the counted vmcnt before the barrier
-// (this wave's DMA pieces of the next chunk have landed), lgkmcnt(0) (this wave's LDS reads of the current chunk have returned).
-__device__ __forceinline__ void chunk_barrier() {
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-}
-
-__device__ __forceinline__ unsigned pack2(float a, float b) {
-    typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-    const bf16x2 v = {(bf16)a, (bf16)b};
-    return __builtin_bit_cast(unsigned, v);
-}
-
 // lanes n and n + 32 each hold two 4-channel groups (x: channels 8j' + 4h .., y: channels 8(j'+1) + 4h ..): exchange so that
 // the low lane holds channels 8j' .. 8j' + 7 and the high lane 8(j'+1) .. 8(j'+1) + 7 (v_permlane32_swap)
 __device__ __forceinline__ void pair_swap(unsigned& x, unsigned& y) {
     const u32x2 r = __builtin_amdgcn_permlane32_swap(x, y, false, false);
     x = r[0];
     y = r[1];
-}
-
-// exact erf-GELU and its derivative from ONE exponential: erf's exp(-u^2) with u = v / sqrt(2) is the Gaussian of GELU'
-__device__ __forceinline__ void gelu_both(float v, float& g, float& dg) {
-    const float av = fabsf(v) * 0.70710678118654752f;
-    const float t = __builtin_amdgcn_rcpf(1.f + 0.3275911f * av);
-    const float e = __expf(-0.5f * v * v);
-    const float poly = t * (0.254829592f + t * (-0.284496736f + t * (1.421413741f + t * (-1.453152027f + t * 1.061405429f))));
-    const float erfv = copysignf(1.f - poly * e, v);
-    const float cdf = 0.5f * (1.f + erfv);
-    g = v * cdf;
-    dg = cdf + v * 0.39894228040143268f * e;
 }
 
 // ------------------------------------------------------------------------------------------------------------------------
@@ -163,7 +123,7 @@ __device__ __forceinline__ void mlp_fused_fwd_body(
     const long rrow = row_ok ? row : (M - 1);  // out-of-range lanes compute on a valid row and store nothing
 
     // ---- weight chunk DMA ----
-    const __amdgpu_buffer_rsrc_t r1 = mk_rsrc(W1, (long)H4 * C * 2), r2 = mk_rsrc(W2, (long)C * H4 * 2);
+    const __amdgpu_buffer_rsrc_t r1 = make_rsrc(W1, (long)H4 * C * 2), r2 = make_rsrc(W2, (long)C * H4 * 2);
     int voff[Cfg::PPW];
 #pragma unroll
     for (int i = 0; i < Cfg::PPW; ++i) {
@@ -231,7 +191,7 @@ __device__ __forceinline__ void mlp_fused_fwd_body(
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc2[t][r] = 0.f;
 
-    wait_vm<0>();     // this wave's parts of chunks 0 and 1 have landed (and its LN loads are done)
+    wait_vmcnt<0>();  // this wave's parts of chunks 0 and 1 have landed (and its LN loads are done)
     __syncthreads();  // ... everybody else's too
 
     const int rho_n = (n & ~12) | ((n & 4) << 1) | ((n & 8) >> 1);
@@ -271,8 +231,8 @@ __device__ __forceinline__ void mlp_fused_fwd_body(
             }
         }
         // chunk q + 1 must have landed before the barrier; the DMA of chunk q + 2, issued after it, may stay in flight
-        if (more) wait_vm<Cfg::PPW>();
-        else wait_vm<0>();
+        if (more) wait_vmcnt<Cfg::PPW>();
+        else wait_vmcnt<0>();
         chunk_barrier();  // chunk q + 1 landed for every wave; every wave is done reading chunk q
         buf = buf == 2 ? 0 : buf + 1;
     }
@@ -328,8 +288,8 @@ __device__ __forceinline__ void mlp_fused_fwd_body(
                     float v[4];
 #pragma unroll
                     for (int i = 0; i < 4; ++i) v[i] = (acc2[mt][4 * j + i] - mean) * rstd * g[i] + b[i];
-                    w[jj][0] = pack2(v[0], v[1]);
-                    w[jj][1] = pack2(v[2], v[3]);
+                    w[jj][0] = esvit_pack2_bf16(v[0], v[1]);
+                    w[jj][1] = esvit_pack2_bf16(v[2], v[3]);
                 }
                 pair_swap(w[0][0], w[1][0]);
                 pair_swap(w[0][1], w[1][1]);

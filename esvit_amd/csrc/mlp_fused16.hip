@@ -59,7 +59,7 @@ __device__ __forceinline__ void fwd16_body(const float* __restrict__ x, const fl
     const bool ok = row < M;
     const long rrow = ok ? row : (M - 1);
 
-    const __amdgpu_buffer_rsrc_t r1 = mk_rsrc(W1p, (long)H4 * C * 2), r2 = mk_rsrc(W2, (long)C * H4 * 2), r3 = mk_rsrc(b1, (long)H4 * 4);
+    const __amdgpu_buffer_rsrc_t r1 = make_rsrc(W1p, (long)H4 * C * 2), r2 = make_rsrc(W2, (long)C * H4 * 2), r3 = make_rsrc(b1, (long)H4 * 4);
     int voff[PPW];
 #pragma unroll
     for (int i = 0; i < PPW; ++i) {
@@ -112,7 +112,7 @@ __device__ __forceinline__ void fwd16_body(const float* __restrict__ x, const fl
 #pragma unroll
     for (int t = 0; t < Cf::MT; ++t) acc2[t] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-    wait_vm<0>();
+    wait_vmcnt<0>();
     __syncthreads();
 
     int buf = 0;
@@ -150,10 +150,10 @@ __device__ __forceinline__ void fwd16_body(const float* __restrict__ x, const fl
             acc2[mt] = mfma16(a, hf, acc2[mt]);
         }
         if (more) {
-            if (full) wait_vm<PPW>();
-            else wait_vm<(PPW > 1 ? PPW - 1 : 0)>();
+            if (full) wait_vmcnt<PPW>();
+            else wait_vmcnt<(PPW > 1 ? PPW - 1 : 0)>();
         } else {
-            wait_vm<0>();
+            wait_vmcnt<0>();
         }
         chunk_barrier();
         buf = buf == 2 ? 0 : buf + 1;
@@ -229,8 +229,8 @@ __device__ __forceinline__ void bwd16_body(const float* __restrict__ x, const fl
     const long rrow = ok ? row : (M - 1);
     const bool wave_live = row0 < M;  // (a wave without a valid row issues no stores)
 
-    const __amdgpu_buffer_rsrc_t r1 = mk_rsrc(W1p, (long)H4 * C * 2), r2 = mk_rsrc(W2Tp, (long)H4 * C * 2), r3 = mk_rsrc(W1T, (long)C * H4 * 2),
-                                 r4 = mk_rsrc(b1, (long)H4 * 4);
+    const __amdgpu_buffer_rsrc_t r1 = make_rsrc(W1p, (long)H4 * C * 2), r2 = make_rsrc(W2Tp, (long)H4 * C * 2), r3 = make_rsrc(W1T, (long)C * H4 * 2),
+                                 r4 = make_rsrc(b1, (long)H4 * 4);
     int voff[PPW];
 #pragma unroll
     for (int i = 0; i < PPW; ++i) {
@@ -289,7 +289,7 @@ __device__ __forceinline__ void bwd16_body(const float* __restrict__ x, const fl
                 dyb[s][4 + e] = (bf16)(sm * gv[8 * s + 4 + e]);
             }
             // xhat out: channels 32s + 4g .. +3 and 32s + 16 + 4g .. +3 -> 8 consecutive channels per lane after the row swap
-            unsigned x0 = pack2(h[0], h[1]), x1 = pack2(h[2], h[3]), y0 = pack2(h[4], h[5]), y1 = pack2(h[6], h[7]);
+            unsigned x0 = esvit_pack2_bf16(h[0], h[1]), x1 = esvit_pack2_bf16(h[2], h[3]), y0 = esvit_pack2_bf16(h[4], h[5]), y1 = esvit_pack2_bf16(h[6], h[7]);
             row_swap(x0, y0);
             row_swap(x1, y1);
             const int ch = 32 * s + 16 * (g & 1) + 4 * (g & ~1);
@@ -301,7 +301,7 @@ __device__ __forceinline__ void bwd16_body(const float* __restrict__ x, const fl
 #pragma unroll
     for (int t = 0; t < Cf::MT; ++t) acc3[t] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-    wait_vm<0>();
+    wait_vmcnt<0>();
     __syncthreads();
 
     bf16* a1g_row = a1g + row * H4 + 8 * g;
@@ -353,13 +353,13 @@ __device__ __forceinline__ void bwd16_body(const float* __restrict__ x, const fl
         // counted the side-output stores as well (rounds 4-5) could be met with chunk q + 1 still on its way (profiles/r06_gemm_astat_probe.txt:
         // seen in a probe kernel; never here, the chunk has a whole iteration to land).  Same step time (47.36 vs 47.37 ms, same box).
         if constexpr (NBUF == 2) {
-            wait_vm<0>();
+            wait_vmcnt<0>();
         } else {
-            if (!wave_live) wait_vm<0>();
+            if (!wave_live) wait_vmcnt<0>();
             else if (more) {
-                if (full) wait_vm<PPW>();
-                else wait_vm<PPW - 1>();
-            } else wait_vm<0>();
+                if (full) wait_vmcnt<PPW>();
+                else wait_vmcnt<PPW - 1>();
+            } else wait_vmcnt<0>();
         }
         chunk_barrier();
         if constexpr (NBUF == 2) buf ^= 1;

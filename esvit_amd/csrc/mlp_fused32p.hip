@@ -53,7 +53,6 @@ __device__ long* g_p32_tl = nullptr;
 namespace {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
 
 constexpr int P32_WAVES = 4;
 constexpr int P32_ROWS = 32 * P32_WAVES;
@@ -95,11 +94,6 @@ struct P32Cfg {
         return ((32 * mt + chan(rho)) * 4 * C + 16 * (u & 1) + 8 * (u >> 1)) * 2;
     }
 };
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t p32_rsrc(const void* base, long bytes) {
-    const long capped = bytes > 0xfffffff0L ? 0xfffffff0L : (bytes < 0 ? 0 : bytes);
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, (int)capped, 0x00020000);
-}
 
 // y^T tile += A * B with the accumulator pinned to the AccVGPR half of the register file (192 of them: the allocator must not copy them)
 __device__ __forceinline__ void mma_acc32(const bf16x8& a, const bf16x8& b, f32x16& c) {
@@ -182,7 +176,7 @@ __device__ __forceinline__ void mlp32p_fwd_body(const P32Args& A) {
     const long rrow = row_ok ? row : (A.M - 1);  // out-of-range lanes compute on a valid row and store nothing
 
     // ---- weight chunk DMA ----
-    const __amdgpu_buffer_rsrc_t r1 = p32_rsrc(A.W1, (long)H4 * C * 2), r2 = p32_rsrc(A.W2, (long)C * H4 * 2), r3 = p32_rsrc(A.b1, (long)H4 * 4);
+    const __amdgpu_buffer_rsrc_t r1 = make_rsrc(A.W1, (long)H4 * C * 2), r2 = make_rsrc(A.W2, (long)C * H4 * 2), r3 = make_rsrc(A.b1, (long)H4 * 4);
     int vo1[Cf::PPW], vo2[Cf::PPW];
 #pragma unroll
     for (int i = 0; i < Cf::PPW; ++i) {
@@ -259,7 +253,7 @@ __device__ __forceinline__ void mlp32p_fwd_body(const P32Args& A) {
     }
 
     // side outputs (training pass): one descriptor per tensor, per-lane byte offset of this lane's 32 bytes of chunk 0 (out of range for rows past M)
-    const __amdgpu_buffer_rsrc_t ra1 = p32_rsrc(A.a1, SIDE ? A.M * H4 * 2 : 0), ra1g = p32_rsrc(A.a1g, SIDE ? A.M * H4 * 2 : 0);
+    const __amdgpu_buffer_rsrc_t ra1 = make_rsrc(A.a1, SIDE ? A.M * H4 * 2 : 0), ra1g = make_rsrc(A.a1g, SIDE ? A.M * H4 * 2 : 0);
     const unsigned side_off = row_ok ? (unsigned)(row * (H4 * 2) + 32 * hh) : 0x80000000u;  // (the tensors are below 2 GiB: the host checks)
 
     f32x16 acc[Cf::NT2];  // y^T: tile mt, register i <-> channel 32 mt + 16 hh + i of token n

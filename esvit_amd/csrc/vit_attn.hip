@@ -250,8 +250,6 @@ int grid_for(long total) {
 
 }  // namespace
 
-#define STREAM(s_) hipStream_t stream = reinterpret_cast<hipStream_t>(s_)
-
 extern "C" int esvit_heads_split(int dtype, const void* x, int B, int N, int Np, int nH, int hd, int parts, void* y, esvit_stream_t stream_) {
     STREAM(stream_);
     ESVIT_CHECK_ARG(x && y && B > 0 && N > 0 && Np >= N && nH > 0 && parts > 0, "esvit_heads_split: bad arguments");

@@ -69,43 +69,6 @@ __device__ __forceinline__ f32x4 load_frag4(const T* p) {
 // on a serial chain (slot map -> row loads -> LDS -> compute -> store) with one window per wave.  Here a wave owns one
 // head and a strided set of windows, requests the q, k, v rows of window it+1 (and the slot map of window it+2) while
 // it computes window `it`, synchronises only with itself, and stores 16-byte rows.  Same math, same LDS images.
-typedef unsigned int u32x4_f __attribute__((ext_vector_type(4)));
-
-// P V with P in registers (fourth-generation forward): operand helpers, see window_attn_big.hip for the derivation
-template <typename T>
-__device__ __forceinline__ Frag<T> frag_v_perm64(const T* Vs, int LD, int d0, int ks, int c, int g) {
-    Frag<T> f;
-    if constexpr (sizeof(T) == 2) {
-        typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
-        const T* p0 = Vs + (32 * ks + 4 * g + (c >> 2)) * LD + d0 + 4 * (c & 3);
-        const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(p0));
-        const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(p0 + 16 * LD));
-        const s16x8 both = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-        f.v = __builtin_bit_cast(bf16x8, both);
-    } else {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            f.v[e] = Vs[(32 * ks + 4 * g + e) * LD + d0 + c];
-            f.v[4 + e] = Vs[(32 * ks + 16 + 4 * g + e) * LD + d0 + c];
-        }
-    }
-    return f;
-}
-template <typename T>
-__device__ __forceinline__ Frag<T> frag_p_regs64(const f32x4& lo, const f32x4& hi) {
-    Frag<T> f;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-        if constexpr (sizeof(T) == 2) {
-            f.v[e] = (bf16)lo[e];
-            f.v[4 + e] = (bf16)hi[e];
-        } else {
-            f.v[e] = lo[e];
-            f.v[4 + e] = hi[e];
-        }
-    }
-    return f;
-}
 
 // Forward (the fourth generation; its predecessors are gone): a wave pair per (window, head), P kept in registers and V staged in its natural [key][d]
 // layout -- no P image, no 2-byte transposed V stores (16 per thread and window), one block barrier less per window.
@@ -119,14 +82,13 @@ __global__ __launch_bounds__(128, (HDIM == 32 ? 3 : 2)) void attn_fwd4_kernel(co
     constexpr int LDQ = Cfg::LDQ, VEC = Cfg::VEC, ES = sizeof(T);
     constexpr int VPR = HDIM / VEC, NV = NP * VPR / 128, LSTEP = 128 / VPR;
     constexpr int NS = 32 * VPR / 64, SSTEP = 64 / VPR;
-    constexpr int OOB = 0x7ffffff0;
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const int c = lane & 15, g = lane >> 4;
     T* base = reinterpret_cast<T*>(smem_raw);
     T* Qs = base;                      // [NP][LDQ]; wave w's own 32 query rows double as its output staging image
     T* Ks = base + Cfg::QK_ELEMS;      // [NP][LDQ]
-    T* Vs = base + 2 * Cfg::QK_ELEMS;  // [NP][LDQ], natural layout: P V reads it with transpose reads (frag_v_perm64)
+    T* Vs = base + 2 * Cfg::QK_ELEMS;  // [NP][LDQ], natural layout: P V reads it with transpose reads (mfma.h: frag_v_perm, P from registers)
 
     const long unit = xcd_contiguous_id(blockIdx.x, gridDim.x);  // the heads of a part share an XCD (and its L2)
     const bool unit_ok = unit < (long)parts * nH;
@@ -160,7 +122,7 @@ __global__ __launch_bounds__(128, (HDIM == 32 ? 3 : 2)) void attn_fwd4_kernel(co
         reg = (masked && act && lane < N) ? region_ids[(long)(bw % nW) * N + lane] : -1;
     };
     struct Win {
-        u32x4_f q[NV], k[NV], v[NV];
+        u32x4 q[NV], k[NV], v[NV];
         int ltok[NV];
         int mytok, myreg, bw;
         long tok_base;
@@ -176,7 +138,7 @@ __global__ __launch_bounds__(128, (HDIM == 32 ? 3 : 2)) void attn_fwd4_kernel(co
         for (int i = 0; i < NV; ++i) {
             const int tok = __shfl(mytok, lrow0 + LSTEP * i, 64);
             x.ltok[i] = tok;
-            const int vq = tok >= 0 ? tok * 3 * C * ES + dv * 16 : OOB;
+            const int vq = tok >= 0 ? tok * 3 * C * ES + dv * 16 : BUF_OOB;
             x.q[i] = __builtin_amdgcn_raw_buffer_load_b128(rq, vq, h * HDIM * ES, 0);
             x.k[i] = __builtin_amdgcn_raw_buffer_load_b128(rq, vq, (C + h * HDIM) * ES, 0);
             x.v[i] = __builtin_amdgcn_raw_buffer_load_b128(rq, vq, (2 * C + h * HDIM) * ES, 0);
@@ -300,10 +262,10 @@ __global__ __launch_bounds__(128, (HDIM == 32 ? 3 : 2)) void attn_fwd4_kernel(co
         for (int ks = 0; ks < 2; ++ks) {  // 64 keys = two 32-deep steps
             Frag<T> vf[DT];
 #pragma unroll
-            for (int dt = 0; dt < DT; ++dt) vf[dt] = frag_v_perm64<T>(Vs, LDQ, 16 * dt, ks, c, g);
+            for (int dt = 0; dt < DT; ++dt) vf[dt] = frag_v_perm<T>(Vs, LDQ, 16 * dt, ks, c, g);
 #pragma unroll
             for (int il = 0; il < 2; ++il) {
-                const Frag<T> pf = frag_p_regs64<T>(p[2 * ks][il], p[2 * ks + 1][il]);
+                const Frag<T> pf = frag_p_regs<T>(p[2 * ks][il], p[2 * ks + 1][il]);
 #pragma unroll
                 for (int dt = 0; dt < DT; ++dt) mma(vf[dt], pf, o[il][dt]);
             }
@@ -316,12 +278,12 @@ __global__ __launch_bounds__(128, (HDIM == 32 ? 3 : 2)) void attn_fwd4_kernel(co
             if constexpr (sizeof(T) == 2) {
 #pragma unroll
                 for (int dt = 0; dt < DT; dt += 2) {
-                    const esvit_u32x4 x = esvit_pack_tile_pair_bf16(o[il][dt], o[il][dt + 1]);
-                    buffer_store_b128(x, ro, ok ? tok * C * ES + (16 * dt + esvit_tile_pair_ch0(g)) * ES : OOB, h * HDIM * ES);
+                    const u32x4 x = esvit_pack_tile_pair_bf16(o[il][dt], o[il][dt + 1]);
+                    buffer_store_b128(x, ro, ok ? tok * C * ES + (16 * dt + esvit_tile_pair_ch0(g)) * ES : BUF_OOB, h * HDIM * ES);
                 }
             } else {
 #pragma unroll
-                for (int dt = 0; dt < DT; ++dt) buffer_store_b128(o[il][dt], ro, ok ? tok * C * ES + (16 * dt + 4 * g) * ES : OOB, h * HDIM * ES);
+                for (int dt = 0; dt < DT; ++dt) buffer_store_b128(o[il][dt], ro, ok ? tok * C * ES + (16 * dt + 4 * g) * ES : BUF_OOB, h * HDIM * ES);
             }
         }
         cur = nxt;
@@ -330,7 +292,6 @@ __global__ __launch_bounds__(128, (HDIM == 32 ? 3 : 2)) void attn_fwd4_kernel(co
     }
 }
 
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
 // -------------------------------------------------------------------------------------------------
 // Backward: a wave pair (one 128-thread workgroup) owns one head and a strided set of windows.  The rows of window it+1
@@ -359,7 +320,6 @@ __global__ __launch_bounds__(128, (HDIM == 32 ? 2 : 1)) void attn_bwd3_kernel(co
     constexpr int LSTEP = 128 / VPR;       // slot stride between a thread's load vectors
     constexpr int NS = 32 * VPR / 64;      // row vectors per lane per 32-row output tile (stores)
     constexpr int SSTEP = 64 / VPR;
-    constexpr int OOB = 0x7ffffff0;
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const int c = lane & 15, g = lane >> 4;
@@ -435,8 +395,8 @@ __global__ __launch_bounds__(128, (HDIM == 32 ? 2 : 1)) void attn_bwd3_kernel(co
         for (int i = 0; i < NV; ++i) {
             const int tok = __shfl(mytok, lrow0 + LSTEP * i, 64);
             x.ltok[i] = tok;
-            const int vq = tok >= 0 ? tok * 3 * C * ES + dv * 16 : OOB;
-            const int vo = tok >= 0 ? tok * C * ES + dv * 16 : OOB;
+            const int vq = tok >= 0 ? tok * 3 * C * ES + dv * 16 : BUF_OOB;
+            const int vo = tok >= 0 ? tok * C * ES + dv * 16 : BUF_OOB;
             x.q[i] = __builtin_amdgcn_raw_buffer_load_b128(rq, vq, h * HDIM * ES, 0);
             x.k[i] = __builtin_amdgcn_raw_buffer_load_b128(rq, vq, (C + h * HDIM) * ES, 0);
             x.v[i] = __builtin_amdgcn_raw_buffer_load_b128(rq, vq, (2 * C + h * HDIM) * ES, 0);
@@ -566,12 +526,12 @@ __global__ __launch_bounds__(128, (HDIM == 32 ? 2 : 1)) void attn_bwd3_kernel(co
                 if constexpr (sizeof(T) == 2) {
 #pragma unroll
                     for (int dt = 0; dt < DT; dt += 2) {
-                        const esvit_u32x4 x = esvit_pack_tile_pair_bf16(v[dt], v[dt + 1]);
-                        buffer_store_b128(x, rd, ok ? tok * 3 * C * ES + (16 * dt + esvit_tile_pair_ch0(g)) * ES : OOB, (col0 + h * HDIM) * ES);
+                        const u32x4 x = esvit_pack_tile_pair_bf16(v[dt], v[dt + 1]);
+                        buffer_store_b128(x, rd, ok ? tok * 3 * C * ES + (16 * dt + esvit_tile_pair_ch0(g)) * ES : BUF_OOB, (col0 + h * HDIM) * ES);
                     }
                 } else {
 #pragma unroll
-                    for (int dt = 0; dt < DT; ++dt) buffer_store_b128(v[dt], rd, ok ? tok * 3 * C * ES + (16 * dt + 4 * g) * ES : OOB, (col0 + h * HDIM) * ES);
+                    for (int dt = 0; dt < DT; ++dt) buffer_store_b128(v[dt], rd, ok ? tok * 3 * C * ES + (16 * dt + 4 * g) * ES : BUF_OOB, (col0 + h * HDIM) * ES);
                 }
                 if (padacc && active && t < N && tok < 0) {
 #pragma unroll
@@ -779,8 +739,6 @@ inline int bwd_parts(int Bw, int nH) {
 }
 
 }  // namespace
-
-#define STREAM(s_) hipStream_t stream = reinterpret_cast<hipStream_t>(s_)
 
 
 int esvit_big_relpos_bias_bwd(const float* dbias_ws, int parts, const int64_t* index, int N, int nH, int table_rows, float* dtable,

@@ -196,8 +196,8 @@ __device__ __forceinline__ void store_block_rows_t(const f32x4 (&acc)[2][HD / 16
         if constexpr (sizeof(T) == 2) {
 #pragma unroll
             for (int j = 0; j < DT; j += 2) {
-                const esvit_u32x4 x = esvit_pack_tile_pair_bf16(v[j], v[j + 1]);  // (every lane takes part in the exchange)
-                if (tok >= 0) *reinterpret_cast<esvit_u32x4*>(dst + (tok_base + tok) * row_stride + 16 * j + esvit_tile_pair_ch0(g)) = x;
+                const u32x4 x = esvit_pack_tile_pair_bf16(v[j], v[j + 1]);  // (every lane takes part in the exchange)
+                if (tok >= 0) *reinterpret_cast<u32x4*>(dst + (tok_base + tok) * row_stride + 16 * j + esvit_tile_pair_ch0(g)) = x;
             }
         } else {
 #pragma unroll
@@ -224,8 +224,8 @@ __device__ __forceinline__ void store_tile_rows_t(const f32x4 (&acc)[HD / 16], f
     if constexpr (sizeof(T) == 2) {
 #pragma unroll
         for (int j = 0; j < DT; j += 2) {
-            const esvit_u32x4 x = esvit_pack_tile_pair_bf16(acc[j] * mul, acc[j + 1] * mul);
-            if (tok >= 0) *reinterpret_cast<esvit_u32x4*>(dst + (tok_base + tok) * row_stride + 16 * j + esvit_tile_pair_ch0(g)) = x;
+            const u32x4 x = esvit_pack_tile_pair_bf16(acc[j] * mul, acc[j + 1] * mul);
+            if (tok >= 0) *reinterpret_cast<u32x4*>(dst + (tok_base + tok) * row_stride + 16 * j + esvit_tile_pair_ch0(g)) = x;
         }
     } else {
 #pragma unroll
@@ -239,49 +239,13 @@ __device__ __forceinline__ void store_tile_rows_t(const f32x4 (&acc)[HD / 16], f
 //   * P never goes through LDS.  The S^T tiles leave lane (c, g) with, for query c, the keys 16i + 4g + r -- for a 32-key
 //     chunk that is 8 keys {32ks + 4g + e, 32ks + 16 + 4g + e}.  An MFMA only needs A and B to agree on which key sits in
 //     which k-slot, so those 8 values ARE the A fragment of P V if V's B fragment is read with the same key permutation
-//     (frag_v_perm: two transpose reads 16 key rows apart).  That removes 56 LDS stores + 14 LDS fragment reads + a wave
+//     (mfma.h: frag_p_regs / frag_v_perm, two transpose reads 16 key rows apart).  That removes 56 LDS stores + 14 LDS fragment reads + a wave
 //     barrier per query block and, more importantly, the 59 KB of per-wave P images: the workgroup needs 53 KB instead of
 //     112 KB, so two (bf16) workgroups share a CU and one's softmax overlaps the other's MFMAs and loads.
 //   * K, V and the first Q block are requested together (one round trip), the Q block of the second pass is requested
 //     before the first pass computes, and the shift-mask labels of the keys are packed into 14 registers once per window
 //     instead of being re-read from LDS for every score tile.
 // -------------------------------------------------------------------------------------------------------------
-template <typename T>
-__device__ __forceinline__ Frag<T> frag_v_perm(const T* Vs, int LD, int d0, int ks, int c, int g) {
-    Frag<T> f;
-    if constexpr (sizeof(T) == 2) {
-        typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
-        const T* p0 = Vs + (32 * ks + 4 * g + (c >> 2)) * LD + d0 + 4 * (c & 3);
-        const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(p0));
-        const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(p0 + 16 * LD));
-        const s16x8 both = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-        f.v = __builtin_bit_cast(bf16x8, both);
-    } else {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            f.v[e] = Vs[(32 * ks + 4 * g + e) * LD + d0 + c];
-            f.v[4 + e] = Vs[(32 * ks + 16 + 4 * g + e) * LD + d0 + c];
-        }
-    }
-    return f;
-}
-
-template <typename T>
-__device__ __forceinline__ Frag<T> frag_p_regs(const f32x4& lo, const f32x4& hi) {
-    Frag<T> f;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-        if constexpr (sizeof(T) == 2) {
-            f.v[e] = (bf16)lo[e];
-            f.v[4 + e] = (bf16)hi[e];
-        } else {
-            f.v[e] = lo[e];
-            f.v[4 + e] = hi[e];
-        }
-    }
-    return f;
-}
-
 // forward, third variant (default): the second generation with ONE 16-query tile per wave and pass.  A workgroup is seven
 // waves, wave w takes query tiles w and w + 7 (no idle wave in the second pass, the 32-query blocks left one of four idle);
 // the score strip is 56 registers instead of 112, so the kernel fits four waves per SIMD and two workgroups (14 waves) share
@@ -820,8 +784,6 @@ inline int big_parts(int Bw, int nH) {
 
 }  // namespace
 
-#define STREAM(s_) hipStream_t stream = reinterpret_cast<hipStream_t>(s_)
-
 int esvit_big_frag_elems() { return NT * NT * 256; }
 int esvit_big_npb() { return NPB; }
 int esvit_big_parts(int Bw, int nH) { return big_parts(Bw, nH); }
@@ -878,7 +840,7 @@ static int big_bwd_launch(const void* qkv, const float* qkv_bias, const int32_t*
                           int nH, float scale, void* dqkv, float* dbias_ws, float* dpad_ws, hipStream_t stream) {
     using Cfg = BigCfg<T, HD>;
     const int parts = big_parts(Bw, nH);
-#ifdef ESVIT_BIG_BWD_FORK  // probe (tools/probe/ab_big_bwd_fork.sh): the dK / dV kernel on a second stream beside the dQ kernel (disjoint outputs)
+#ifdef ESVIT_BIG_BWD_FORK  // probe (its A/B script is gone; the measurement is profiles/r06_w14_dq_dkv_fork_ab.txt): the dK / dV kernel on a second stream beside the dQ kernel (disjoint outputs)
     static hipStream_t s2 = nullptr;
     static hipEvent_t ev_fork = nullptr, ev_join = nullptr;
     if (!s2) {

@@ -225,11 +225,11 @@ __device__ __forceinline__ void p8_epilogue_fast(const esvit_gemm_desc& p, f32x4
         }
     } else {  // P8_GELU_BWD
         const bf16* ap = reinterpret_cast<const bf16*>(p.aux) + row * p.ldaux + col;
-        u32x2_t a[4][2];
+        u32x2 a[4][2];
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-            a[i][0] = *reinterpret_cast<const u32x2_t*>(ap + 16 * i * p.ldaux);
-            a[i][1] = *reinterpret_cast<const u32x2_t*>(ap + 16 * i * p.ldaux + 16);
+            a[i][0] = *reinterpret_cast<const u32x2*>(ap + 16 * i * p.ldaux);
+            a[i][1] = *reinterpret_cast<const u32x2*>(ap + 16 * i * p.ldaux + 16);
         }
         bf16* cp = reinterpret_cast<bf16*>(p.C) + (long)z * p.strideC + row * p.ldc + wcol0;
         const bool quick = p.epilogue == ESVIT_EPI_QGELU_BWD;

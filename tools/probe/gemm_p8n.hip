@@ -272,7 +272,7 @@ __global__ __launch_bounds__(PN_NT, 1) void gemm_p8n_kernel(const esvit_gemm_des
     // ---- output addressing.  Every output / epilogue tensor goes through a buffer descriptor based at the item's first row (offsets
     // stay below 2^31; rows past M fall outside num_records and are dropped by the hardware) with a per-lane byte offset that is the
     // same for the whole kernel: row c of a row block, and either the lane's 8-column piece of a bf16 row (two column blocks exchanged
-    // between lane groups, pair_rows) or its 4 columns of block 0 (block 1 = + 16 columns) of an fp32 row.  Columns past N: the
+    // between lane groups, esvit_pack_tile_pair_bf16) or its 4 columns of block 0 (block 1 = + 16 columns) of an fp32 row.  Columns past N: the
     // per-lane offset is replaced by OOB.  The scalar offset carries the rest: wave row / column, unit.
     const long ldo = p.splitk > 1 ? (long)N : p.ldc;  // leading dimension of the output (elements)
     constexpr int ES = F32OUT ? 4 : 2;
@@ -335,7 +335,7 @@ __global__ __launch_bounds__(PN_NT, 1) void gemm_p8n_kernel(const esvit_gemm_des
             const unsigned vo = lane_off_bf16(vo_out, o.n0);
             if constexpr (EPI == PN_GELU) {
                 const unsigned sx = o.so_x + (unsigned)((QM * 128 + 16 * I) * p.ldaux * 2);
-                buffer_store_b128<ESVIT_P8N_STORE_AUX>(pair_rows(v[0], v[1]), o.rx, lane_off_bf16(vo_aux, o.n0), sx);
+                buffer_store_b128<ESVIT_P8N_STORE_AUX>(esvit_pack_tile_pair_bf16(v[0], v[1]), o.rx, lane_off_bf16(vo_aux, o.n0), sx);
             }
             if constexpr (EPI == PN_GELU || EPI == PN_GELU_NOAUX) {
                 const bool quick = p.epilogue == ESVIT_EPI_QGELU;
@@ -344,7 +344,7 @@ __global__ __launch_bounds__(PN_NT, 1) void gemm_p8n_kernel(const esvit_gemm_des
 #pragma unroll
                     for (int e = 0; e < 4; ++e) v[j][e] = quick ? qgelu_f(v[j][e]) : gelu_f(v[j][e]);
             }
-            buffer_store_b128<ESVIT_P8N_STORE_AUX>(pair_rows(v[0], v[1]), o.rc, vo, so);
+            buffer_store_b128<ESVIT_P8N_STORE_AUX>(esvit_pack_tile_pair_bf16(v[0], v[1]), o.rc, vo, so);
         }
     };
     // all eight units of a set at once (end of the item).  Kinds with inputs request the inputs of four units before the first of
@@ -383,7 +383,7 @@ __global__ __launch_bounds__(PN_NT, 1) void gemm_p8n_kernel(const esvit_gemm_des
             const bool quick = p.epilogue == ESVIT_EPI_QGELU_BWD;
             static_for<2>([&](auto hc) {
                 constexpr int QM = decltype(hc)::value;
-                u32x2_t a[4][2];
+                u32x2 a[4][2];
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {
                     const unsigned sx = o.so_x + (unsigned)((QM * 128 + 16 * i) * p.ldaux * 2);
@@ -401,7 +401,7 @@ __global__ __launch_bounds__(PN_NT, 1) void gemm_p8n_kernel(const esvit_gemm_des
                         for (int e = 0; e < 4; ++e) v[j][e] = acc[SET][QM][i][j][e] * p.alpha * (quick ? qgelu_grad_f(x[e]) : gelu_grad_f(x[e]));
                     }
                     const unsigned so = o.so_c + (unsigned)((QM * 128 + 16 * i) * ldo * 2);
-                    buffer_store_b128<ESVIT_P8N_STORE_AUX>(pair_rows(v[0], v[1]), o.rc, lane_off_bf16(vo_out, o.n0), so);
+                    buffer_store_b128<ESVIT_P8N_STORE_AUX>(esvit_pack_tile_pair_bf16(v[0], v[1]), o.rc, lane_off_bf16(vo_out, o.n0), so);
                 }
                 __builtin_amdgcn_sched_barrier(0);
             });

@@ -196,8 +196,8 @@ __device__ __forceinline__ void store_block_rows_t(const f32x4 (&acc)[2][HD / 16
         if constexpr (sizeof(T) == 2) {
 #pragma unroll
             for (int j = 0; j < DT; j += 2) {
-                const esvit_u32x4 x = esvit_pack_tile_pair_bf16(v[j], v[j + 1]);  // (every lane takes part in the exchange)
-                if (tok >= 0) *reinterpret_cast<esvit_u32x4*>(dst + (tok_base + tok) * row_stride + 16 * j + esvit_tile_pair_ch0(g)) = x;
+                const u32x4 x = esvit_pack_tile_pair_bf16(v[j], v[j + 1]);  // (every lane takes part in the exchange)
+                if (tok >= 0) *reinterpret_cast<u32x4*>(dst + (tok_base + tok) * row_stride + 16 * j + esvit_tile_pair_ch0(g)) = x;
             }
         } else {
 #pragma unroll
@@ -224,8 +224,8 @@ __device__ __forceinline__ void store_tile_rows_t(const f32x4 (&acc)[HD / 16], f
     if constexpr (sizeof(T) == 2) {
 #pragma unroll
         for (int j = 0; j < DT; j += 2) {
-            const esvit_u32x4 x = esvit_pack_tile_pair_bf16(acc[j] * mul, acc[j + 1] * mul);
-            if (tok >= 0) *reinterpret_cast<esvit_u32x4*>(dst + (tok_base + tok) * row_stride + 16 * j + esvit_tile_pair_ch0(g)) = x;
+            const u32x4 x = esvit_pack_tile_pair_bf16(acc[j] * mul, acc[j + 1] * mul);
+            if (tok >= 0) *reinterpret_cast<u32x4*>(dst + (tok_base + tok) * row_stride + 16 * j + esvit_tile_pair_ch0(g)) = x;
         }
     } else {
 #pragma unroll
@@ -246,42 +246,6 @@ __device__ __forceinline__ void store_tile_rows_t(const f32x4 (&acc)[HD / 16], f
 //     before the first pass computes, and the shift-mask labels of the keys are packed into 14 registers once per window
 //     instead of being re-read from LDS for every score tile.
 // -------------------------------------------------------------------------------------------------------------
-template <typename T>
-__device__ __forceinline__ Frag<T> frag_v_perm(const T* Vs, int LD, int d0, int ks, int c, int g) {
-    Frag<T> f;
-    if constexpr (sizeof(T) == 2) {
-        typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
-        const T* p0 = Vs + (32 * ks + 4 * g + (c >> 2)) * LD + d0 + 4 * (c & 3);
-        const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(p0));
-        const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(p0 + 16 * LD));
-        const s16x8 both = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-        f.v = __builtin_bit_cast(bf16x8, both);
-    } else {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            f.v[e] = Vs[(32 * ks + 4 * g + e) * LD + d0 + c];
-            f.v[4 + e] = Vs[(32 * ks + 16 + 4 * g + e) * LD + d0 + c];
-        }
-    }
-    return f;
-}
-
-template <typename T>
-__device__ __forceinline__ Frag<T> frag_p_regs(const f32x4& lo, const f32x4& hi) {
-    Frag<T> f;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-        if constexpr (sizeof(T) == 2) {
-            f.v[e] = (bf16)lo[e];
-            f.v[4 + e] = (bf16)hi[e];
-        } else {
-            f.v[e] = lo[e];
-            f.v[4 + e] = hi[e];
-        }
-    }
-    return f;
-}
-
 // forward, third variant (default): the second generation with ONE 16-query tile per wave and pass.  A workgroup is seven
 // waves, wave w takes query tiles w and w + 7 (no idle wave in the second pass, the 32-query blocks left one of four idle);
 // the score strip is 56 registers instead of 112, so the kernel fits four waves per SIMD and two workgroups (14 waves) share
@@ -892,8 +856,6 @@ inline int big_parts(int Bw, int nH) {
 }
 
 }  // namespace
-
-#define STREAM(s_) hipStream_t stream = reinterpret_cast<hipStream_t>(s_)
 
 int esvit_big_frag_elems() { return NT * NT * 256; }
 int esvit_big_npb() { return NPB; }
