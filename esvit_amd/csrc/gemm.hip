@@ -213,7 +213,7 @@ int validate(int dtype, esvit_gemm_desc& d) {
     if (d.batch < 1) d.batch = 1;
     if (d.splitk > 1) {
         ESVIT_CHECK_ARG(d.batch == 1 && d.partial && d.ldc == d.N, "esvit_gemm: split-K needs batch=1, a workspace and a dense C");
-        ESVIT_CHECK_ARG(!d.bias && !d.residual && !d.rowmap && d.epilogue == 0, "esvit_gemm: split-K has no fused epilogue");
+        ESVIT_CHECK_ARG(!d.bias && !d.residual && !d.rowmap && !d.rowscale && d.epilogue == 0, "esvit_gemm: split-K has no fused epilogue");
     } else {
         d.splitk = 1;
     }
@@ -223,6 +223,9 @@ int validate(int dtype, esvit_gemm_desc& d) {
     ESVIT_CHECK_ARG(d.epilogue >= 0 && d.epilogue <= ESVIT_EPI_QGELU_BWD, "esvit_gemm: bad epilogue %d", d.epilogue);
     if (d.colsum && d.splitk > 1) ESVIT_CHECK_ARG(d.colsum_partial != nullptr, "esvit_gemm: colsum with split-K needs colsum_partial");
     if (d.colsum) ESVIT_CHECK_ARG(d.batch == 1, "esvit_gemm: colsum is not batched");
+    // (the LDS-DMA loops accumulate it for a k-strided A only: in the other layouts nothing would write it.  The register-staged fp32 loop could,
+    // but one contract holds for both dtypes, and no caller asks for it there.)
+    if (d.colsum) ESVIT_CHECK_ARG(d.a_kstrided, "esvit_gemm: colsum (the fused bias gradient) exists for the weight-gradient layout only");
     if (d.colstat) ESVIT_CHECK_ARG(d.rowstat != nullptr, "esvit_gemm: colstat comes with rowstat");
     if (d.rowstat) {
         ESVIT_CHECK_ARG(dtype == ESVIT_BF16 && !d.a_kstrided && !d.b_kstrided && d.batch == 1 && d.splitk <= 1 && !d.out_f32 && d.epilogue == 0 &&

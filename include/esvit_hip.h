@@ -143,11 +143,12 @@ typedef struct {
     int64_t ldaux;
     int32_t epilogue; /* ESVIT_EPI_* */
     int32_t out_f32;  /* 1: C is fp32, 0: C has the activation dtype */
-    int32_t splitk;   /* >1: partial sums in `partial` then reduced into C (fp32, out_f32 must be 1) */
+    int32_t splitk;   /* >1: fp32 partial sums in `partial`, then reduced into C (fp32 with out_f32, else the activation dtype); slice z takes the k-tiles
+                       * [z, z + 1) * ceil(k-tiles / splitk) -- trailing slices may be empty; no fused epilogue, dense C (ldc == N), batch == 1 */
     float* partial;   /* workspace >= splitk*M*N floats */
     int32_t accumulate; /* split-K reduce: C += sum (1) or C = sum (0) */
     float alpha;
-    float* colsum;         /* optional, fp32 [M]: row sums of op(A) over K (= bias gradient when A = dY^T); fused via an all-ones B fragment */
+    float* colsum;         /* optional, fp32 [M]: alpha * row sums of op(A) over K (= bias gradient when A = dY^T); fused via an all-ones B fragment; k-strided A only */
     float* colsum_partial; /* workspace >= splitk*M floats when splitk > 1 */
     int32_t kernel;        /* ESVIT_GEMM_AUTO (0): chosen from the shape; otherwise force one main loop (tests / tuning) */
     /* optional softmax statistics of the OUTPUT rows (the logits of the DINO head, vision_transformer.py:418): for every row and
