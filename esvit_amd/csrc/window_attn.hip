@@ -782,7 +782,8 @@ int esvit_big_attn_fwd(int dtype, const void* qkv, const float* qkv_bias, const 
                        float* attn_out, hipStream_t stream);
 int esvit_big_attn_bwd(int dtype, const void* qkv, const float* qkv_bias, const int32_t* win2tok, int L, const void* dout,
                        const void* fout, const float* lse, const float* rel_table, int ws, float* bias_frag_ws, const int32_t* region_ids,
-                       int nW, int nB, int N, int nH, int hd, float scale, void* dqkv, float* dbias_ws, float* dpad_ws, hipStream_t stream);
+                       int nW, int nB, int N, int nH, int hd, float scale, void* dqkv, float* dbias_ws, float* dpad_ws, int split_db,
+                       hipStream_t stream);
 int esvit_big_relpos_bias_bwd(const float* dbias_ws, int parts, const int64_t* index, int N, int nH, int table_rows, float* dtable,
                               int accumulate, hipStream_t stream);
 
@@ -876,14 +877,22 @@ extern "C" int esvit_window_attn_bwd(int dtype, const void* qkv, const float* qk
     if (ws > 0 && (ws & ESVIT_ATTN_SLIDING_CHUNK))
         return esvit_chunk_attn_bwd(dtype, qkv, win2tok, L, dout, fwd_out, lse, ws & ~ESVIT_ATTN_SLIDING_CHUNK, bias_frag_ws, nW, nB, N, nH, hd, scale,
                                     dqkv, stream);
-    ESVIT_CHECK_ARG(qkv && qkv_bias && win2tok && dout && dqkv && dbias_ws && dpad_ws && nB > 0 && nW > 0 && nH > 0 && L > 0 &&
+    // (ESVIT_ATTN_SPLIT_DBIAS: the 224-slot kernels' bias gradient from its own kernel, esvit_hip.h)
+    const int split_db = ws > 0 && (ws & ESVIT_ATTN_SPLIT_DBIAS) ? 1 : 0;
+    if (split_db) ws &= ~ESVIT_ATTN_SPLIT_DBIAS;
+    ESVIT_CHECK_ARG(qkv && qkv_bias && win2tok && dout && dqkv && dpad_ws && nB > 0 && nW > 0 && nH > 0 && L > 0 &&
                         ws > 0 && N > 0 && (N == ws * ws || (N < ws * ws && N <= esvit_big_npb())),
                     "esvit_window_attn_bwd: bad args");
     ESVIT_CHECK_ARG(hd == HD || hd == 64, "esvit_window_attn_bwd: head_dim %d unsupported (32 or 64)", hd);
     ESVIT_CHECK_ARG(dtype == ESVIT_BF16 || dtype == ESVIT_F32, "esvit_window_attn_bwd: bad dtype");
+    // only the head_dim-64 instances of the 224-slot kernels can go without the slabs (their bias gradient is a kernel of its own, left
+    // out for a caller without a table); every other kernel writes them unconditionally
+    ESVIT_CHECK_ARG(dbias_ws || (N > NP && hd == 64),
+                    "esvit_window_attn_bwd: dbias_ws may be NULL only at head_dim 64 on windows of more than 64 tokens (%d tokens, head_dim %d)", N, hd);
+    ESVIT_CHECK_ARG(!split_db || N > NP, "esvit_window_attn_bwd: ESVIT_ATTN_SPLIT_DBIAS applies to windows of more than 64 tokens (got %d)", N);
     if (N > NP)
         return esvit_big_attn_bwd(dtype, qkv, qkv_bias, win2tok, L, dout, fwd_out, lse, rel_table, ws, bias_frag_ws, region_ids, nW, nB,
-                                  N, nH, hd, scale, dqkv, dbias_ws, dpad_ws, stream);
+                                  N, nH, hd, scale, dqkv, dbias_ws, dpad_ws, split_db, stream);
     ESVIT_CHECK_ARG(bias_frag_ws != nullptr, "esvit_window_attn_bwd: 7x7 windows need the bias_frag_ws scratch");
     if (rel_table) {  // NULL: bias_frag_ws still holds the fragment-order bias an earlier call of this step put there
         int rc = fill_bias_frag(rel_table, ws, N, nH, bias_frag_ws, stream);

@@ -538,6 +538,136 @@ __global__ __launch_bounds__(DQ4_WAVES * 64) void attn_big_bwd_dq4_kernel(
     }
 }
 
+// a * b rounded on its own, never contracted into a following sum: dS as dq4 forms it (there the product is also packed for the dQ
+// product, so it exists rounded), which keeps the bias-gradient kernel below bit-compatible with dq4's accumulation
+__device__ __forceinline__ f32x4 mul_rounded(f32x4 a, f32x4 b) {
+#pragma clang fp contract(off)
+    return a * b;
+}
+
+// Relative-position-bias gradient alone: the WANT_DB part of dq4 as a kernel of its own, for head_dim 64 (dq4 holds 200 registers there,
+// the 56 accumulators would spill) and, behind ESVIT_ATTN_SPLIT_DBIAS, for head_dim 32.  Same mapping as dq4 -- a wave per (part, head,
+// 16-query tile) walking the part's windows in the same order, K and V staged once per workgroup, delta from the same fragments -- and
+// the same slab layout, one writer per element, no atomics; a tile that never meets a live query writes its zeros.  Without the dQ
+// product nothing outlives a key tile but the accumulators: per key tile S^T = K (scale Q)^T + bias (+ mask), P = exp(S - lse),
+// dP^T = V dO^T, db += P o (dP - delta).  The price is that S and dP are computed a second time (dq4 and dkv2 each form them already).
+// gfx950, bf16 (hipcc -O3, -Rpass-analysis=kernel-resource-usage): 200 VGPRs at head_dim 64, 170 at head_dim 32, no scratch, no spill;
+// dynamic LDS as dq4, 126464 B at head_dim 64 and 73216 B at head_dim 32 (one workgroup per CU either way).
+template <typename T, int HD>
+__global__ __launch_bounds__(DQ4_WAVES * 64) void attn_big_bwd_dbias_kernel(
+    const T* __restrict__ qkv, const float* __restrict__ qkv_bias, const int* __restrict__ win2tok, int L, const T* __restrict__ dout,
+    const T* __restrict__ fout, const float* __restrict__ lse_in, const float* __restrict__ bias_frag, int ws,
+    const int* __restrict__ region_ids, int nW, int Bw, int N, int nH, float scale, int parts, float* __restrict__ dbias_ws) {
+    using Cfg = BigCfg<T, HD>;
+    constexpr int LDQ = Cfg::LDQ;
+    constexpr int KS = HD / 32;
+    constexpr int TILE = 16 * LDQ;  // one [16][LDQ] image
+    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+    const BigTables tb = carve_tables(smem_raw);
+    T* Ks = reinterpret_cast<T*>(smem_raw + Cfg::TABLE_BYTES);
+    T* Vs = Ks + Cfg::FULL;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int c = lane & 15, g = lane >> 4;
+    T* Qs = Vs + Cfg::FULL + wave * (3 * TILE);
+    T* Os = Qs + TILE;  // dO rows of this wave's queries
+    T* Fs = Os + TILE;  // forward output rows
+
+    const int unit = xcd_contiguous_id(blockIdx.x, gridDim.x);
+    const int grp = unit % DQ4_GROUPS;
+    const int ph = unit / DQ4_GROUPS;  // (part, h)
+    const int h = ph % nH, part = ph / nH;
+    const int qt = grp * DQ4_WAVES + wave;   // query tile of this wave
+    const bool wave_ok = qt < NT;
+    const int q0 = wave_ok ? 16 * qt : 0;
+    const int C = nH * HD;
+    const bool masked = region_ids != nullptr;
+    const T* src = qkv + h * HD;
+    const float* bias_h = bias_frag + (long)h * (NT * NT * 256);
+
+    f32x4 db[NT];
+#pragma unroll
+    for (int i = 0; i < NT; ++i) db[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+    const Vec16<T> padk = SlotStage<T, NPB, DQ4_WAVES * 64, HD>::pad_piece(qkv_bias + C + h * HD, threadIdx.x);
+    const Vec16<T> padv = SlotStage<T, NPB, DQ4_WAVES * 64, HD>::pad_piece(qkv_bias + 2 * C + h * HD, threadIdx.x);
+    const Vec16<T> padq = SlotStage<T, 16, 64, HD>::pad_piece(qkv_bias + h * HD, lane);
+    const int iters = (Bw + parts - 1) / parts;
+    for (int it = 0; it < iters; ++it) {
+        const int bw = part + it * parts;
+        const bool win_ok = bw < Bw;
+        const int bwc = win_ok ? bw : 0;
+        const long tok_base = (long)(bwc / nW) * L;
+        __syncthreads();  // previous window's reads are complete
+        load_window_tables(tb, win2tok, region_ids, bwc % nW, N, ws, win_ok);
+        __syncthreads();
+        const unsigned live = live_query_tiles(tb.tok, lane);  // (a window past the end has no live slot)
+        if (((live >> (grp * DQ4_WAVES)) & ((1u << DQ4_WAVES) - 1)) == 0) continue;  // whole workgroup: the table is shared
+        const bool tile_live = wave_ok && ((live >> qt) & 1);
+        float lq = 0.f;
+        {
+            SlotStage<T, NPB, DQ4_WAVES * 64, HD> sk, sv;
+            SlotStage<T, 16, 64, HD> sq, so, sf;
+            sk.load(src + C, 3L * C, tb.tok, tok_base, 0, N, &padk, threadIdx.x);
+            sv.load(src + 2 * C, 3L * C, tb.tok, tok_base, 0, N, &padv, threadIdx.x);
+            if (tile_live) {
+                sq.load(src, 3L * C, tb.tok, tok_base, q0, N, &padq, lane);
+                so.load(dout + h * HD, (long)C, tb.tok, tok_base, q0, N, nullptr, lane);
+                sf.load(fout + h * HD, (long)C, tb.tok, tok_base, q0, N, nullptr, lane);
+                lq = lse_in[((long)bwc * nH + h) * NPB + q0 + c];
+            }
+            sk.store(Ks, 1.f, threadIdx.x);
+            sv.store(Vs, 1.f, threadIdx.x);
+            if (tile_live) {
+                sq.store(Qs, scale, lane);
+                so.store(Os, 1.f, lane);
+                sf.store(Fs, 1.f, lane);
+            }
+        }
+        __syncthreads();
+        if (!tile_live) continue;  // (no workgroup barrier below this line)
+        Frag<T> qf[KS], of[KS];
+        const int rq = masked ? ((tb.pk[q0 + c] >> 16) & 0xff) : 0;
+        float d = 0.f;  // delta = sum_d dO[q][d] O[q][d], formed as dq4 forms it
+#pragma unroll
+        for (int ks = 0; ks < KS; ++ks) {
+            qf[ks] = frag_kc<T>(Qs, LDQ, 0, 32 * ks, c, g);
+            of[ks] = frag_kc<T>(Os, LDQ, 0, 32 * ks, c, g);
+            const Frag<T> ff = frag_kc<T>(Fs, LDQ, 0, 32 * ks, c, g);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) d += (float)of[ks].v[e] * (float)ff.v[e];
+        }
+        d += __shfl_xor(d, 16, 64);
+        d += __shfl_xor(d, 32, 64);
+#pragma unroll
+        for (int i = 0; i < NT; ++i) {
+            f32x4 b = *reinterpret_cast<const f32x4*>(bias_h + ((i * NT + (q0 >> 4)) * 64 + lane) * 4);
+            if (masked) {
+                const i32x4 pk4 = *reinterpret_cast<const i32x4*>(tb.pk + 16 * i + 4 * g);
+#pragma unroll
+                for (int r = 0; r < 4; ++r) b[r] += (((pk4[r] >> 16) & 0xff) != rq) ? -100.f : 0.f;
+            }
+            f32x4 dp = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int ks = 0; ks < KS; ++ks) {
+                mma(frag_kc<T>(Ks, LDQ, 16 * i, 32 * ks, c, g), qf[ks], b);
+                mma(frag_kc<T>(Vs, LDQ, 16 * i, 32 * ks, c, g), of[ks], dp);
+            }
+#pragma unroll
+            for (int r = 0; r < 4; ++r) b[r] = __expf(b[r] - lq);
+            db[i] += mul_rounded(b, dp - d);
+            // nothing but db[] outlives a key tile.  Pin each update where it stands: left alone, the compiler keeps S and dP of all
+            // fourteen tiles (112 registers) and does the exponentials and the sums at the end of the window, and spills
+            asm volatile("" : "+v"(db[i]));
+        }
+    }
+    if (wave_ok) {
+        // frag layout of the NPB x NPB bias gradient: ((ki*NT + qj)*64 + lane)*4 + r
+        float* wsp = dbias_ws + ((long)part * nH + h) * (NT * NT * 256);
+#pragma unroll
+        for (int i = 0; i < NT; ++i) *reinterpret_cast<f32x4*>(wsp + ((i * NT + qt) * 64 + lane) * 4) = db[i];
+    }
+}
+
 template <typename T, int HD>
 __global__ __launch_bounds__((BigCfg<T, HD>::WAVES * 64), ((sizeof(T) == 2 && HD == 32) ? 2 : 1)) void attn_big_bwd_dkv2_kernel(
     const T* __restrict__ qkv, const float* __restrict__ qkv_bias, const int* __restrict__ win2tok, int L, const T* __restrict__ dout,
@@ -837,7 +967,7 @@ int esvit_big_attn_fwd(int dtype, const void* qkv, const float* qkv_bias, const 
 template <typename T, int HD>
 static int big_bwd_launch(const void* qkv, const float* qkv_bias, const int32_t* win2tok, int L, const void* dout, const void* fout,
                           const float* lse, const float* rel_table, int ws, const int32_t* region_ids, int nW, int Bw, int N,
-                          int nH, float scale, void* dqkv, float* dbias_ws, float* dpad_ws, hipStream_t stream) {
+                          int nH, float scale, void* dqkv, float* dbias_ws, float* dpad_ws, bool split_db, hipStream_t stream) {
     using Cfg = BigCfg<T, HD>;
     const int parts = big_parts(Bw, nH);
 #ifdef ESVIT_BIG_BWD_FORK  // probe (its A/B script is gone; the measurement is profiles/r06_w14_dq_dkv_fork_ab.txt): the dK / dV kernel on a second stream beside the dQ kernel (disjoint outputs)
@@ -862,6 +992,18 @@ static int big_bwd_launch(const void* qkv, const float* qkv_bias, const int32_t*
                            (const T*)dout, (const T*)fout, lse, rel_table, ws, region_ids, nW, Bw, N, nH, scale, parts, (T*)dqkv, dbias_ws);
         ESVIT_CHECK_LAUNCH("window_attn_bwd(14x14, dQ)");
     }
+    // the bias gradient where dq4 does not produce it (head_dim 64; skipped when the caller has no table: dbias_ws = NULL), or, with
+    // ESVIT_ATTN_SPLIT_DBIAS, over dq4's own slabs (same stream: this kernel's values are the ones that stay)
+    if constexpr (sizeof(T) == 2) {
+        if (dbias_ws && (HD == 64 || split_db)) {
+            auto kern = attn_big_bwd_dbias_kernel<T, HD>;
+            const size_t lds = dq4_lds<T, HD>();
+            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+            hipLaunchKernelGGL(kern, dim3(parts * nH * DQ4_GROUPS), dim3(DQ4_WAVES * 64), lds, stream, (const T*)qkv, qkv_bias, win2tok, L,
+                               (const T*)dout, (const T*)fout, lse, rel_table, ws, region_ids, nW, Bw, N, nH, scale, parts, dbias_ws);
+            ESVIT_CHECK_LAUNCH("window_attn_bwd(14x14, dBias)");
+        }
+    }
     {
         auto kern = attn_big_bwd_dkv2_kernel<T, HD>;
         const size_t lds = dkv2_lds<T, HD>();
@@ -879,9 +1021,12 @@ static int big_bwd_launch(const void* qkv, const float* qkv_bias, const int32_t*
 
 int esvit_big_attn_bwd(int dtype, const void* qkv, const float* qkv_bias, const int32_t* win2tok, int L, const void* dout,
                        const void* fout, const float* lse, const float* rel_table_, int ws, float* bias_frag_ws, const int32_t* region_ids,
-                       int nW, int nB, int N, int nH, int hd, float scale, void* dqkv, float* dbias_ws, float* dpad_ws, hipStream_t stream) {
+                       int nW, int nB, int N, int nH, int hd, float scale, void* dqkv, float* dbias_ws, float* dpad_ws, int split_db,
+                       hipStream_t stream) {
     ESVIT_CHECK_ARG(N <= NPB, "window_attn: window %d too large", ws);
     ESVIT_CHECK_ARG(hd == 32 || (hd == 64 && dtype == ESVIT_BF16), "window_attn: %d tokens at head_dim %d: 32, or 64 in bf16", N, hd);
+    ESVIT_CHECK_ARG(dbias_ws || hd == 64, "esvit_window_attn_bwd: dbias_ws may be NULL only at head_dim 64 on windows of more than 64 tokens");
+    ESVIT_CHECK_ARG(!split_db || dtype == ESVIT_BF16, "esvit_window_attn_bwd: ESVIT_ATTN_SPLIT_DBIAS is a bf16 arrangement");
     ESVIT_CHECK_ARG(fout && lse, "esvit_window_attn_bwd: 14x14 windows need the forward output and log-sum-exp");
     ESVIT_CHECK_ARG(bias_frag_ws != nullptr, "esvit_window_attn_bwd: the bias_frag_ws scratch is required");
     {
@@ -892,12 +1037,12 @@ int esvit_big_attn_bwd(int dtype, const void* qkv, const float* qkv_bias, const 
     const int Bw = nB * nW;
     if (hd == 64)
         return big_bwd_launch<bf16, 64>(qkv, qkv_bias, win2tok, L, dout, fout, lse, rel_table, ws, region_ids, nW, Bw, N, nH, scale, dqkv, dbias_ws,
-                                        dpad_ws, stream);
+                                        dpad_ws, split_db != 0, stream);
     if (dtype == ESVIT_BF16)
         return big_bwd_launch<bf16, 32>(qkv, qkv_bias, win2tok, L, dout, fout, lse, rel_table, ws, region_ids, nW, Bw, N, nH, scale, dqkv, dbias_ws,
-                                        dpad_ws, stream);
+                                        dpad_ws, split_db != 0, stream);
     return big_bwd_launch<float, 32>(qkv, qkv_bias, win2tok, L, dout, fout, lse, rel_table, ws, region_ids, nW, Bw, N, nH, scale, dqkv, dbias_ws,
-                                     dpad_ws, stream);
+                                     dpad_ws, false, stream);
 }
 
 int esvit_i_relpos_fold(const float* dbias_ws, int parts, int nt, const int64_t* index, int N, int nH, float* dtable, hipStream_t stream);

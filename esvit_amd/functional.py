@@ -26,6 +26,13 @@ def ops_module():
     return ops
 
 
+def _no_dbias(o, N, hd):
+    """keyword of o.window_attn_bwd for a caller WITHOUT a relative-position table: on windows of more than 64 tokens at head_dim 64 the
+    bias gradient is a kernel of its own (window_attn_big.hip), which such a caller leaves out.  Passed only where it changes something
+    and to an ops module that knows it (the CPU restatement of the kernels computes the slabs in passing and has no such switch)"""
+    return {"want_dbias": False} if N > 64 and hd == 64 and getattr(o, "ATTN_BWD_OPTIONAL_DBIAS", False) else {}
+
+
 # ------------------------------------------------------------------------------------------------
 # static per-geometry tables (index maps, shift masks), cached per device
 # ------------------------------------------------------------------------------------------------
@@ -1290,7 +1297,8 @@ class CvtAttnFn(torch.autograd.Function):
         dao = _pad_tokens(o.linear_dgrad(dyb, Wproj), nB, H, W, Hp, Wp)
         geom = geometry(Hp, Wp, w, 0, x.device)
         regions = geometry(Hp, Wp, w, w // 2, x.device).region_ids if shift else None
-        dqkv, dbias_ws, _ = o.window_attn_bwd(qkv, pw_b, geom.win2tok, Hp * Wp, dao, ao, lse, table, w, regions, geom.nW, geom.N, nH, scale)
+        dqkv, dbias_ws, _ = o.window_attn_bwd(qkv, pw_b, geom.win2tok, Hp * Wp, dao, ao, lse, table, w, regions, geom.nW, geom.N, nH, scale,
+                                              **({} if has_table else _no_dbias(o, geom.N, C // nH)))
         dtable = o.relpos_bias_bwd(dbias_ws, index, geom.N, table.shape[0]) if has_table else None
         dWpw, dbpw = _side_run(lambda: o.linear_wgrad(dqkv, bnout, want_bias=True), dqkv, bnout)
         dbn = o.linear_dgrad(dqkv, Wpw)
@@ -1472,7 +1480,8 @@ def vit_attention_bwd(o, dao, att, bqkv, nB, N, nH, scale, dqkv_out=None):
         qkv, ao, frag = att[:3]
         lse = att[3] if len(att) == 4 else None
         win2tok, ws, _ = _vit_window(N, nH, qkv.device)
-        return o.window_attn_bwd(qkv, bqkv, win2tok, N, dao, ao, lse, None, ws, None, 1, N, nH, scale, dqkv_out=dqkv_out, bias_frag=frag)[0]
+        return o.window_attn_bwd(qkv, bqkv, win2tok, N, dao, ao, lse, None, ws, None, 1, N, nH, scale, dqkv_out=dqkv_out, bias_frag=frag,
+                                 **_no_dbias(o, N, qkv.shape[1] // 3 // nH))[0]
     dqkv = o.vit_attn_bwd(dao, att, nB, N, nH, scale)
     if dqkv_out is not None:
         dqkv_out.copy_(dqkv)

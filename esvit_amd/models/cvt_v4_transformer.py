@@ -59,9 +59,6 @@ class Attention(nn.Module):
         self.proj_out = nn.Conv2d(dim_out, dim_in, 1)
         self.rel_pos_embed = rel_pos_embed
         if rel_pos_embed:  # cvt_v4_transformer.py:141-163: the Swin index formula, one table row per relative offset
-            if window_size * window_size > 64 and dim_out // num_heads != 32:
-                raise NotImplementedError("relative-position tables on windows of more than 64 tokens need head_dim 32 (got %d)"
-                                          % (dim_out // num_heads))
             c = np.stack(np.meshgrid(np.arange(window_size), np.arange(window_size), indexing="ij")).reshape(2, -1)
             rel = (c[:, :, None] - c[:, None, :]).transpose(1, 2, 0) + (window_size - 1)
             self.register_buffer("rel_pos_idx", torch.from_numpy((rel[:, :, 0] * (2 * window_size - 1) + rel[:, :, 1]).astype(np.int64)))

@@ -772,9 +772,15 @@ def attn_dbias_slabs(N, windows, nH, device):
     return buf, out
 
 
+ATTN_BWD_OPTIONAL_DBIAS = True  # window_attn_bwd takes want_dbias (functional._no_dbias)
+ATTN_SPLIT_DBIAS = 0x10000000  # ESVIT_ATTN_SPLIT_DBIAS: OR'd into ws of esvit_window_attn_bwd, the separate bias-gradient kernel at head_dim 32 too
+
+
 def window_attn_bwd(qkv, qkv_bias, win2tok, L, dout, fwd_out, lse, rel_table, ws, region_ids, nW, N, nH, scale, dqkv_out=None, bias_frag=None,
-                    dbias_out=None):
-    """-> (dqkv act [nB*L, 3C], dbias_ws fp32 [parts, nH, frag], dpad_ws fp32 [rows, 2C]).  dbias_out: this call's slice of attn_dbias_slabs"""
+                    dbias_out=None, want_dbias=True):
+    """-> (dqkv act [nB*L, 3C], dbias_ws fp32 [parts, nH, frag], dpad_ws fp32 [rows, 2C]).  dbias_out: this call's slice of attn_dbias_slabs.
+    want_dbias=False (a caller without a table; windows of more than 64 tokens at head_dim 64 only, where the bias gradient is a kernel
+    of its own -- the library refuses it elsewhere): no slabs, None in their place.  ws may carry ATTN_SPLIT_DBIAS"""
     qkv, dout = _actc(qkv), _actc(dout)
     rows, C3 = qkv.shape
     Cc = C3 // 3
@@ -783,7 +789,10 @@ def window_attn_bwd(qkv, qkv_bias, win2tok, L, dout, fwd_out, lse, rel_table, ws
     dqkv = torch.empty_like(qkv) if dqkv_out is None else dqkv_out
     assert dqkv.shape == qkv.shape and dqkv.dtype == qkv.dtype and dqkv.is_contiguous()
     parts = query(Q_ATTN_BWD_PARTS, N, nB * nW, nH)
-    if dbias_out is None:
+    if not want_dbias:
+        assert dbias_out is None
+        dbias_ws = None
+    elif dbias_out is None:
         dbias_ws = torch.empty((parts, nH, attn_frag_elems(N)), dtype=torch.float32, device=qkv.device)
     else:
         dbias_ws = _f32c(dbias_out)

@@ -339,8 +339,16 @@ int esvit_attn_branch_fwd(int dtype, const float* x, const float* gamma, const f
  * against that 0).  One image's qkv rows (L * 3C activations) must fit a 2 GiB buffer
  * descriptor.
  * attn_out (optional, fp32 [nB*nW,nH,N,N]) receives the softmax (swin_transformer.py:146,152). 
- * N <= 64: head_dim 32 or 64.  64 < N <= 224: head_dim 32, or 64 in bf16 -- the head_dim-64 instances (whole ViT crops: one window per
- * image, N < ws * ws allowed, zero table) leave dbias_ws unwritten.
+ * N <= 64: head_dim 32 or 64.  64 < N <= 224: head_dim 32, or 64 in bf16 (whole ViT crops -- one window per image, N < ws * ws
+ * allowed, zero table -- and the 14x14 windows of the CvT / Swin configurations at head_dim 64).
+ *
+ * Bias gradient of the 224-slot kernels (64 < N <= 224).  At head_dim 32 the dQ kernel accumulates it beside dQ.  At head_dim 64 that
+ * kernel has no registers left for it and a kernel of its own writes the same slabs (it recomputes S and dP a second time): there, and
+ * only there, dbias_ws = NULL is accepted and skips that kernel -- the caller without a table (the ViTs, CvT without REL_POS_EMBED).
+ * For every other shape dbias_ws = NULL is ESVIT_ERR_ARG before any launch.
+ * ws | ESVIT_ATTN_SPLIT_DBIAS (esvit_window_attn_bwd only, 64 < N <= 224, bf16; ESVIT_ERR_ARG elsewhere): the separate bias-gradient
+ * kernel also at head_dim 32 -- the dQ kernel runs unchanged, then the separate kernel writes the slabs.  Not routed by the package: the
+ * arrangement "bias gradient out of the dQ kernel", kept available for tests and A/B measurements.
  *
  * Sliding-chunk mode (ws | ESVIT_ATTN_SLIDING_CHUNK; chunk_attn.hip): Vision Longformer's attention (layers/slidingchunk_2d.py
  * mode 0, layers/longformer2d.py) over one token grid per image, fused -- no tensor grows with L^2.  The tokens of an image are
@@ -370,13 +378,15 @@ int esvit_attn_branch_fwd(int dtype, const float* x, const float* gamma, const f
  */
 #define ESVIT_ATTN_SLIDING_CHUNK 0x40000000
 #define ESVIT_ATTN_GLOBAL 0x20000000
+#define ESVIT_ATTN_SPLIT_DBIAS 0x10000000
 int esvit_window_attn_fwd(int dtype, const void* qkv, const float* qkv_bias, const int32_t* win2tok, int L,
                           const float* rel_table, int ws, float* bias_frag_ws, const int32_t* region_ids, int nW, int nB,
                           int N, int nH, int hd, float scale, void* out, float* lse, float* attn_out,
                           esvit_stream_t stream);
 /* dout dtype [nB*L, C] -> dqkv dtype [nB*L, 3C] (every row written).  fwd_out / lse: the forward's outputs (needed for
  * 14x14 windows only).  Partials: dbias_ws fp32 [ESVIT_Q_ATTN_BWD_PARTS(N, nB*nW, nH), nH, frag]
- * (relative-position-bias gradient, reduced by esvit_relpos_bias_bwd) and dpad_ws fp32
+ * (relative-position-bias gradient, reduced by esvit_relpos_bias_bwd; every element written by exactly one wave, no atomics; NULL:
+ * see "Bias gradient of the 224-slot kernels" above) and dpad_ws fp32
  * [ESVIT_Q_ATTN_BWD_PAD_ROWS(N, nB*nW, nH | dtype << 32), 2C], ZERO-INITIALISED by the caller: sums of the dK / dV rows
  * of zero-pad slots, layout [k|v][nH][hd] -- gradients of qkv_bias[C:3C] (column-sum them into the bias gradient). */
 int esvit_window_attn_bwd(int dtype, const void* qkv, const float* qkv_bias, const int32_t* win2tok, int L,
