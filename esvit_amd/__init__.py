@@ -16,6 +16,7 @@ import torch  # noqa: E402
 
 from . import _lib  # noqa: F401  (raises if libesvit_hip.so is missing -- there is no fallback)
 from . import models, ops  # noqa: F401
+from . import analysis  # noqa: F401,E402  (attention entropy / rows / correspondence measurements)
 from .head import DINOHead  # noqa: F401
 from .loss import DDINOLoss, DINOLoss  # noqa: F401
 from .models import build_model  # noqa: F401

@@ -1,0 +1,173 @@
+"""Analysis of trained backbones (the reference's analyze_models.py): attention entropy, attention maps of chosen queries, thresholded
+attention masks, and the correspondence score between two views -- batched, on the device.
+
+For a VisionTransformer nothing here forms an attention matrix: the entropy of every softmax row and the probability rows of a few
+queries come from the statistics mode of the flash-attention kernels (csrc/flash_attn.hip, ops.global_attn_stats), on every
+block in one backbone pass.  The reference loops over images at batch size 1 because `forward_selfattention` returns [B, nH, N, N] per
+block.  Swin backbones keep their 7 x 7 window maps (they are small) and reduce them in torch.  Plotting, the two augmented views and
+the per-head ordering of the figures stay with the caller."""
+import math
+
+import torch
+
+from . import functional as Fn
+from .models.swin_transformer import SwinTransformer
+from .models.vision_transformer import VisionTransformer
+
+_LOG2E = 1.0 / math.log(2.0)
+_UNITS = {"bits": _LOG2E, "nats": 1.0}
+
+
+def _is_vit(model):
+    return isinstance(model, VisionTransformer)
+
+
+def _vit_block_stats(model, images, queries, blocks, want_rows):
+    """one backbone pass under no_grad; the statistics of the chosen blocks' attention on those blocks' inputs"""
+    depth = len(model.blocks)
+    blocks = list(range(depth)) if blocks is None else [int(b) % depth for b in blocks]
+    ents, rows = [], []
+    # (crops beyond the one-window kernels advance through the flash forward where it exists: the batched-GEMM route would form P)
+    with torch.no_grad(), Fn._long_attention("flash"):
+        x = model._tokens(images)
+        for i, blk in enumerate(model.blocks):
+            if i in blocks:
+                e, r = Fn.vit_block_attention_stats(x, blk.attn.num_heads, blk._params(), queries if want_rows else None)
+                ents.append(e)
+                rows.append(r)
+            if i < max(blocks):
+                x = blk(x, dp=None)
+    order = [sorted(set(blocks)).index(b) for b in blocks]  # (blocks were visited in ascending order)
+    return [ents[j] for j in order], [rows[j] for j in order]
+
+
+def _query_index(queries, N, device):
+    idx = torch.as_tensor(list(queries) if isinstance(queries, range) else queries).reshape(-1).long()
+    if idx.numel() and not (0 <= int(idx.min()) and int(idx.max()) < N):
+        raise ValueError("query indices must lie in [0, %d)" % N)
+    return idx.to(device)
+
+
+def attention_entropy(model, images, queries=None, unit="bits"):
+    """Shannon entropy of the attention distribution of every query token, block by block.
+
+    VisionTransformer: -> fp32 [depth, B, nH, N], or [depth, B, nH, len(queries)] for a list of query tokens (token 0 is the class
+    token).  One backbone pass without gradients; the entropy is accumulated beside the running softmax statistics, no N x N tensor
+    exists at any point.  SwinTransformer: -> a list with one tensor [B * nW, nH, ws^2] (or [..., len(queries)]) per block, from the
+    window maps of `forward_selfattention(images, n=2)`.  Any other backbone: TypeError.
+
+    unit: "bits" (the reference's log2) or "nats".  Convention 0 log 0 = 0: a probability that underflowed to zero contributes nothing.
+    The reference's `(-p * torch.log2(p)).sum(-1)` (analyze_models.py:116-135) evaluates 0 * -inf there and returns NaN for the row."""
+    if unit not in _UNITS:
+        raise ValueError("unit: bits or nats, not %r" % (unit,))
+    k = _UNITS[unit]
+    if _is_vit(model):
+        ents, _ = _vit_block_stats(model, images, None, None, False)
+        ent = torch.stack(ents)
+        if queries is not None:
+            ent = ent.index_select(3, _query_index(queries, ent.shape[3], ent.device))
+        return ent * k if k != 1.0 else ent
+    if isinstance(model, SwinTransformer):
+        with torch.no_grad():
+            maps = model.forward_selfattention(images, n=2)
+        out = []
+        for p in maps:
+            e = torch.special.entr(p.float()).sum(-1)
+            if queries is not None:
+                e = e.index_select(2, _query_index(queries, e.shape[2], e.device))
+            out.append(e * k if k != 1.0 else e)
+        return out
+    raise TypeError("attention_entropy: VisionTransformer and SwinTransformer backbones only, not %s (its attention is neither one global "
+                    "softmax per image nor Swin's window maps)" % type(model).__name__)
+
+
+def attention_rows(model, images, queries, blocks=None):
+    """the attention maps of the listed query tokens, what `attentions[0, :, query, :]` reads of `forward_selfattention`, for every
+    image and every chosen block: -> fp32 [len(blocks), B, nH, len(queries), N].  blocks: indices into model.blocks (default: the last
+    block).  VisionTransformer only."""
+    if not _is_vit(model):
+        raise TypeError("attention_rows: VisionTransformer backbones only, not %s" % type(model).__name__)
+    if queries is None or len(queries) == 0:
+        raise ValueError("attention_rows: at least one query token")
+    blocks = [len(model.blocks) - 1] if blocks is None else list(blocks)
+    _, rows = _vit_block_stats(model, images, queries, blocks, True)
+    return torch.stack(rows)
+
+
+def attention_mass_masks(rows, threshold=0.6):
+    """the thresholded masks of analyze_models.py:168-176 for any batch of attention rows [..., N]: sort each row ascending, normalise it
+    to sum 1, and keep the entries whose cumulative sum exceeds 1 - threshold (the largest entries, holding `threshold` of the mass)
+    -> bool, the shape of `rows`, in the rows' own order."""
+    val, idx = torch.sort(rows, dim=-1)
+    val = val / val.sum(-1, keepdim=True)
+    keep = torch.cumsum(val, dim=-1) > (1 - threshold)
+    return torch.zeros_like(keep).scatter_(-1, idx, keep)
+
+
+class AttentionEntropyMeter:
+    """per-(block, head) mean over images of the mean-over-queries attention entropy: the dataset-level figure of the reference
+    (analyze_models.py:805-829: batch 1, `queries=range(49)`, a running mean over images), for batches of any size.  Sums are kept on the
+    device in fp64; update() does not synchronise with the host."""
+
+    def __init__(self, unit="bits"):
+        self.unit = unit
+        self.total = None
+        self.images = 0
+
+    def update(self, model, images, queries=None):
+        ent = attention_entropy(model, images, queries, self.unit)
+        if isinstance(ent, list):  # Swin: a window is a sample of its block; the heads differ from stage to stage -> a list per block
+            per = [e.double().mean(-1).mean(0) * images.shape[0] for e in ent]
+            self.total = per if self.total is None else [a + b for a, b in zip(self.total, per)]
+        else:
+            per = ent.double().mean(-1).sum(1)  # [depth, nH]: summed over the images
+            self.total = per if self.total is None else self.total + per
+        self.images += images.shape[0]
+        return self
+
+    def update_from(self, model, loader, queries=None):
+        """a GpuEvalLoader or any iterable of (images, ...) batches"""
+        dev = next(model.parameters()).device
+        for batch in loader:
+            images = batch[0] if isinstance(batch, (tuple, list)) else batch
+            self.update(model, images.to(dev, non_blocking=True), queries)
+        return self
+
+    def compute(self):
+        """-> fp64 [depth, nH] (SwinTransformer: a list of [nH of the block] per block)"""
+        if self.total is None:
+            raise RuntimeError("AttentionEntropyMeter.compute: no update yet")
+        if isinstance(self.total, list):
+            return [t / self.images for t in self.total]
+        return self.total / self.images
+
+
+def correspondence_scores(fea1, fea2, grid_hw, cell, top=10, flipped=True):
+    """the correspondence measurement of analyze_models.py:302-354 for a batch of image pairs.  fea1, fea2 [B, T, C]: region tokens of
+    two views on a grid_hw = (rows, columns) grid, T = rows * columns (a class token is dropped by the caller); cell: the side of a grid
+    cell in pixels.  Every token of view 1 is matched to its most similar token of view 2 (cosine similarity; the first index on
+    ties); of the `top` matches with the highest similarity (stable descending order) the distance between the two cell centres
+    (row, column) * cell + cell / 2 is taken -- to the horizontally mirrored centre of view 1 when `flipped` -- and a match is correct
+    when that distance is 0.
+    -> (accuracy [B], distance_error [B], sims_sorted [B, T]); the reference's third return value is sims_sorted[:, min(top, T - 1)]."""
+    o = Fn.ops_module()
+    B, T, C = fea1.shape
+    gh, gw = grid_hw
+    assert fea2.shape == fea1.shape and gh * gw == T, (fea1.shape, fea2.shape, grid_hw)
+    z1 = o.l2norm_fwd(fea1.float().contiguous().view(B * T, C))[0].view(B, T, C)
+    z2 = o.l2norm_fwd(fea2.float().contiguous().view(B * T, C))[0].view(B, T, C)
+    ld = -(-T // 8) * 8
+    sim = o.batched_nt(z1, z2, ld)[:, :, :T]
+    best = sim.max(-1).values
+    ar = torch.arange(T, device=sim.device)
+    match = torch.where(sim == best.unsqueeze(-1), ar, T).min(-1).values  # the first index that holds the maximum
+    sims_sorted, order = torch.sort(best, dim=-1, descending=True, stable=True)
+    n = min(top, T)
+    src = order[:, :n]
+    dst = match.gather(1, src)
+    y1, x1 = (src // gw) * cell + cell / 2.0, (src % gw) * cell + cell / 2.0
+    y2, x2 = (dst // gw) * cell + cell / 2.0, (dst % gw) * cell + cell / 2.0
+    if flipped:
+        x1 = gw * cell - x1
+    dist = ((x1 - x2) ** 2 + (y1 - y2) ** 2).sqrt()
+    return (dist == 0).float().mean(-1), dist.mean(-1), sims_sorted

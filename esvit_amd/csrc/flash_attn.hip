@@ -18,13 +18,17 @@
 //             flash_bwd_dkv  per (image, head, key block), over the query blocks (Q, dO, lse, delta through the ring):
 //                            dV += P^T dO, dK += scale dS^T Q
 //             Every row of dqkv is written by exactly one workgroup: no atomics, two launches give identical bits.
+//   stats     ws = ESVIT_ATTN_GLOBAL | ESVIT_ATTN_STATS: the entropy of every softmax row (stats_entropy, the forward without V) and
+//             the fp32 probability rows of a few listed queries (stats_rows), for the attention analysis of esvit_amd/analysis.py.
 //
 // Q, K, V and dO enter the MFMAs as the bf16 values they are and the scale multiplies the fp32 scores (chunk_attn.hip's header records
 // what scaling Q in LDS cost).  P and dS are rounded to bf16 for their MFMAs; everything else is fp32.  Head dims 32 and 64.
 //
 // LDS (bf16 rows padded by 8 elements): forward Q + 2 x (K, V) = 5 [64][hd + 8] images, 25.6 KB (hd 32) / 46.1 KB (hd 64); backward
 // six images (+ 1 KB of lse / delta for dK dV): 30.7-31.7 / 55.3-56.3 KB -- two workgroups per CU and more at either head dim.
-// VGPRs (tools/kernel_regs.sh flash_attn), no scratch, no spills:  hd 32: fwd 76, dq 78, dkv 108;  hd 64: fwd 120, dq 110, dkv 156.
+// The statistics kernels hold Q + 2 x K (15.4 / 27.6 KB) and 2 x K + 512 B of per-wave maxima and sums (10.8 / 18.9 KB), statically.
+// VGPRs (tools/kernel_regs.sh flash_attn), no scratch, no spills:  hd 32: fwd 76, dq 78, dkv 108, entropy 60, rows 76;
+// hd 64: fwd 120, dq 110, dkv 156, entropy 72, rows 88.
 #include "common.h"
 #include "mfma.h"
 #include "../../include/esvit_hip.h"
@@ -436,6 +440,208 @@ __global__ __launch_bounds__(NTHR) void flash_bwd_dkv_kernel(const bf16* __restr
     store_tile_rows<HD>(av, 1.f, rows, N, 3 * C, 2 * C + u.h * HD, tok, g);
 }
 
+// -------------------------------------------------------------------------------------------------------------
+// attention statistics (ws = ESVIT_ATTN_GLOBAL | ESVIT_ATTN_STATS): what an attention analysis reads, without P and without V
+// -------------------------------------------------------------------------------------------------------------
+// entropy of every softmax row, in nats: the forward's work map and K ring, Q and K only.  Beside the running max m and sum l a query
+// carries u = sum_k e^(s_k - m) (s_k - m); when the max moves to m' (alpha = e^(m - m')) every old term e^(s - m)(s - m) becomes
+// alpha e^(s - m) ((s - m) + (m - m')), i.e. u <- alpha (u + (m - m') l).  H = ln l - u / l: l >= 1 (the maximum's own term is e^0) and
+// u <= 0, both terms are >= 0 and nothing cancels.  A key slot >= N has e = 0 and adds an exact (signed) zero to l and u.
+// ent: row 0 of the image-head's [rows][N] slab (row_stride = rows * N floats per (image, head)).
+template <int HD>
+__global__ __launch_bounds__(NTHR) void stats_entropy_kernel(const bf16* __restrict__ qkv, int N, int nH, int nblk, float scale,
+                                                             long slab, float* __restrict__ ent, float* __restrict__ lse_out) {
+    using Cfg = FCfg<HD>;
+    constexpr int LDQ = Cfg::LDQ, KS = Cfg::KS, IMG = Cfg::IMG;
+    __shared__ __attribute__((aligned(16))) bf16 Qs[IMG];
+    __shared__ __attribute__((aligned(16))) bf16 Kr[2 * IMG];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int c = lane & 15, g = lane >> 4;
+
+    const Unit u = unit_of(blockIdx.x, nblk, nH);
+    const int C = nH * HD;
+    const bf16* src = qkv + (long)u.b * N * 3 * C + u.h * HD;
+    const int q0 = u.blk * BLKT;
+    {
+        RowStage<HD> sq, sk;
+        sq.load(src, 3L * C, q0, N, tid);
+        sk.load(src + C, 3L * C, 0, N, tid);
+        sq.store(Qs, tid);
+        sk.store(Kr, tid);
+    }
+    __syncthreads();
+    const bool live = q0 + 16 * wave < N;
+
+    Frag<bf16> qf[KS];
+#pragma unroll
+    for (int ks = 0; ks < KS; ++ks) qf[ks] = frag_kc<bf16>(Qs, LDQ, 16 * wave, 32 * ks, c, g);
+    float m = -3.0e38f, l = 0.f, uu = 0.f;  // of query slot 16 wave + c (the same in the four lanes g of a column)
+
+#pragma unroll 1
+    for (int kb = 0; kb < nblk; ++kb) {
+        const bool more = kb + 1 < nblk;
+        RowStage<HD> sk;
+        if (more) sk.load(src + C, 3L * C, (kb + 1) * BLKT, N, tid);
+        const bf16* Ks = Kr + (kb & 1) * IMG;
+        if (live) {
+            f32x4 p[NT16];
+            float mb = -3.0e38f;
+#pragma unroll
+            for (int i = 0; i < NT16; ++i) {
+                f32x4 s = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                for (int ks = 0; ks < KS; ++ks) mma(frag_kc<bf16>(Ks, LDQ, 16 * i, 32 * ks, c, g), qf[ks], s);
+                const int key0 = kb * BLKT + 16 * i + 4 * g;
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    s[r] = key0 + r < N ? s[r] * scale : -1.0e30f;
+                    mb = fmaxf(mb, s[r]);
+                }
+                p[i] = s;
+            }
+            mb = fmaxf(mb, __shfl_xor(mb, 16, 64));
+            mb = fmaxf(mb, __shfl_xor(mb, 32, 64));
+            const float mn = fmaxf(m, mb);
+            const float alpha = __expf(m - mn);  // (first block: 0 on l = u = 0, and (m - mn) l = -0)
+            float sum = 0.f, usum = 0.f;
+#pragma unroll
+            for (int i = 0; i < NT16; ++i)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const float d = p[i][r] - mn;
+                    const float e = __expf(d);  // a slot >= N: exp(-1e30) = 0, 0 * -1e30 = -0
+                    sum += e;
+                    usum += e * d;
+                }
+            sum += __shfl_xor(sum, 16, 64);
+            sum += __shfl_xor(sum, 32, 64);
+            usum += __shfl_xor(usum, 16, 64);
+            usum += __shfl_xor(usum, 32, 64);
+            uu = alpha * (uu + (m - mn) * l) + usum;
+            l = l * alpha + sum;
+            m = mn;
+        }
+        if (more) sk.store(Kr + ((kb + 1) & 1) * IMG, tid);
+        __syncthreads();
+    }
+    const int qt = q0 + 16 * wave + c;
+    if (!live || g != 0 || qt >= N) return;
+    const float ll = __logf(l);
+    ent[(long)u.z * slab + qt] = ll - uu / l;
+    if (lse_out) lse_out[(long)u.z * N + qt] = m + ll;
+}
+
+// probability rows of nq listed queries (the same list for every image and head): one workgroup per (image, head, 16 listed queries),
+// whose Q rows are gathered straight into the operand fragment; the four waves take one 16-key tile each of every 64-key block of the
+// K ring.  Two sweeps over K: the first for the row maximum and sum (online per wave, then combined across the waves through LDS), the
+// second recomputes the scores and writes p = e^(s - m) / l.  Scores are formed as S = Q K^T (acc[r] = query 4g + r, key c), so that a
+// store instruction writes 16 consecutive floats of a row.  rows: row 1 of the (image, head) slab; row j of the list is slab row 1 + j.
+// An index outside [0, N) reads as a zero query row (never out of bounds; the callers validate the list).
+template <int HD>
+__global__ __launch_bounds__(NTHR) void stats_rows_kernel(const bf16* __restrict__ qkv, const int32_t* __restrict__ qidx, int nq, int ntile,
+                                                          int N, int nH, int nblk, float scale, long slab, float* __restrict__ rows) {
+    // the second sweep has to rebuild the first sweep's scaled scores bit for bit (the maximum's own term is e^0 = 1 exactly, a one-token
+    // image gives p = 1): s * scale - m must not become one fused multiply-add, which would subtract m from the UNROUNDED product
+#pragma clang fp contract(off)
+    using Cfg = FCfg<HD>;
+    constexpr int LDQ = Cfg::LDQ, KS = Cfg::KS, IMG = Cfg::IMG;
+    __shared__ __attribute__((aligned(16))) bf16 Kr[2 * IMG];
+    __shared__ float red[2][WAVES][16];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int c = lane & 15, g = lane >> 4;
+
+    const Unit u = unit_of(blockIdx.x, ntile, nH);
+    const int C = nH * HD;
+    const bf16* src = qkv + (long)u.b * N * 3 * C + u.h * HD;
+    Frag<bf16> qf[KS];
+    {
+        const int j = 16 * u.blk + c;
+        const int t = j < nq ? qidx[j] : -1;
+#pragma unroll
+        for (int ks = 0; ks < KS; ++ks) {
+            qf[ks].v = __builtin_bit_cast(bf16x8, u32x4{0u, 0u, 0u, 0u});
+            if (t >= 0 && t < N) qf[ks].v = *reinterpret_cast<const bf16x8*>(src + (long)t * 3 * C + 32 * ks + 8 * g);
+        }
+    }
+    {
+        RowStage<HD> sk;
+        sk.load(src + C, 3L * C, 0, N, tid);
+        sk.store(Kr, tid);
+    }
+    __syncthreads();
+
+    float m[4], l[4], inv[4];  // of the listed queries 16 tile + 4g + r
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        m[r] = -3.0e38f;
+        l[r] = 0.f;
+        inv[r] = 0.f;
+    }
+    float* out[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const int j = 16 * u.blk + 4 * g + r;
+        out[r] = j < nq ? rows + (long)u.z * slab + (long)j * N : nullptr;
+    }
+
+#pragma unroll 1
+    for (int step = 0; step < 2 * nblk; ++step) {
+        const bool second = step >= nblk;
+        const int kb = second ? step - nblk : step;
+        const bool more = step + 1 < 2 * nblk;
+        const int nkb = kb + 1 < nblk ? kb + 1 : 0;  // (the second sweep starts over at block 0)
+        RowStage<HD> sk;
+        if (more) sk.load(src + C, 3L * C, nkb * BLKT, N, tid);
+        const bf16* Ks = Kr + (step & 1) * IMG;
+        if (step == nblk) {  // the partial (m, l) of the four waves, written before the barrier that ended the first sweep
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                float mm = -3.0e38f;
+#pragma unroll
+                for (int w = 0; w < WAVES; ++w) mm = fmaxf(mm, red[0][w][4 * g + r]);
+                float ls = 0.f;
+#pragma unroll
+                for (int w = 0; w < WAVES; ++w) ls += red[1][w][4 * g + r] * __expf(red[0][w][4 * g + r] - mm);
+                m[r] = mm;
+                inv[r] = 1.f / ls;  // (ls >= 1: the wave that holds the maximum adds e^0)
+            }
+        }
+        f32x4 s = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int ks = 0; ks < KS; ++ks) mma(qf[ks], frag_kc<bf16>(Ks, LDQ, 16 * wave, 32 * ks, c, g), s);
+        const int key = kb * BLKT + 16 * wave + c;
+        const bool valid = key < N;
+        if (!second) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const float sr = valid ? s[r] * scale : -1.0e30f;
+                float mb = sr;
+#pragma unroll
+                for (int x = 1; x < 16; x <<= 1) mb = fmaxf(mb, __shfl_xor(mb, x, 64));
+                const float mn = fmaxf(m[r], mb);
+                float e = valid ? __expf(sr - mn) : 0.f;
+#pragma unroll
+                for (int x = 1; x < 16; x <<= 1) e += __shfl_xor(e, x, 64);
+                l[r] = l[r] * __expf(m[r] - mn) + e;
+                m[r] = mn;
+            }
+            if (step == nblk - 1 && c == 0) {
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    red[0][wave][4 * g + r] = m[r];
+                    red[1][wave][4 * g + r] = l[r];
+                }
+            }
+        } else if (valid) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+                if (out[r]) out[r][key] = __expf(s[r] * scale - m[r]) * inv[r];
+        }
+        if (more) sk.store(Kr + ((step + 1) & 1) * IMG, tid);
+        __syncthreads();
+    }
+}
+
 template <int HD>
 constexpr size_t lds_bytes(int images, bool stats) {
     return (size_t)images * FCfg<HD>::IMG * 2 + (stats ? 4 * BLKT * 4 : 0);
@@ -484,20 +690,58 @@ int bwd_launch(const bf16* qkv, const bf16* dout, const bf16* fout, const float*
     return ESVIT_OK;
 }
 
-// argument checks shared by the two entries; no HIP call before they pass
-int check_mode(const char* who, int dtype, int L, int ws, int nW, int nB, int N, int nH, int hd) {
+template <int HD>
+int stats_launch(const bf16* qkv, const int32_t* qidx, int nq, int N, int nB, int nH, float scale, float* attn_out, float* lse,
+                 hipStream_t stream) {
+    const int nblk = blocks_of(N);
+    const long slab = (long)(1 + nq) * N;
+    hipLaunchKernelGGL(stats_entropy_kernel<HD>, dim3(nB * nH * nblk), dim3(NTHR), 0, stream, qkv, N, nH, nblk, scale, slab, attn_out, lse);
+    ESVIT_CHECK_LAUNCH("window_attn_fwd(global, stats: entropy)");
+    if (nq > 0) {
+        const int ntile = (nq + 15) / 16;
+        hipLaunchKernelGGL(stats_rows_kernel<HD>, dim3(nB * nH * ntile), dim3(NTHR), 0, stream, qkv, qidx, nq, ntile, N, nH, nblk, scale, slab,
+                           attn_out + N);
+        ESVIT_CHECK_LAUNCH("window_attn_fwd(global, stats: rows)");
+    }
+    return ESVIT_OK;
+}
+
+// argument checks shared by the entries; no HIP call before they pass.  stats: the statistics mode (forward only), nW = 1 + listed queries
+int check_mode(const char* who, int dtype, int L, int ws, int nW, int nB, int N, int nH, int hd, bool stats = false) {
     ESVIT_CHECK_ARG(!(ws & ESVIT_ATTN_SLIDING_CHUNK), "%s: both mode flags at once (ESVIT_ATTN_GLOBAL | ESVIT_ATTN_SLIDING_CHUNK)", who);
-    ESVIT_CHECK_ARG(ws == ESVIT_ATTN_GLOBAL, "%s (global): ws carries the mode flag alone, not 0x%x", who, (unsigned)ws);
+    ESVIT_CHECK_ARG(stats || !(ws & ESVIT_ATTN_STATS), "%s (global): ESVIT_ATTN_STATS is a mode of esvit_window_attn_fwd only", who);
+    ESVIT_CHECK_ARG(ws == (stats ? ESVIT_ATTN_GLOBAL | ESVIT_ATTN_STATS : ESVIT_ATTN_GLOBAL), "%s (global): ws carries the mode flag%s alone, not 0x%x",
+                    who, stats ? "s" : "", (unsigned)ws);
     ESVIT_CHECK_ARG(dtype == ESVIT_BF16, "%s (global): bf16 only (the fp32 parity mode keeps the batched-GEMM route)", who);
     ESVIT_CHECK_ARG(hd == 32 || hd == 64, "%s (global): head_dim %d unsupported (32 or 64)", who, hd);
     ESVIT_CHECK_ARG(L >= 1, "%s (global): L=%d, at least one token per image", who, L);
-    ESVIT_CHECK_ARG(nW == 1 && N == L && nB > 0 && nH > 0, "%s (global): bad geometry L=%d nW=%d N=%d nB=%d nH=%d (nW = 1, N = L)", who, L, nW, N, nB, nH);
+    if (stats)
+        ESVIT_CHECK_ARG(nW >= 1 && N == L && nB > 0 && nH > 0,
+                        "%s (global, stats): bad geometry L=%d nW=%d N=%d nB=%d nH=%d (nW = 1 + listed queries >= 1, N = L)", who, L, nW, N, nB, nH);
+    else
+        ESVIT_CHECK_ARG(nW == 1 && N == L && nB > 0 && nH > 0, "%s (global): bad geometry L=%d nW=%d N=%d nB=%d nH=%d (nW = 1, N = L)", who, L, nW, N, nB, nH);
     ESVIT_CHECK_ARG((long)L * 3 * nH * hd * 2 < 0x7fff0000L, "%s (global): one image's qkv rows must fit a 2 GiB buffer descriptor", who);
     ESVIT_CHECK_ARG((long)nB * nH * blocks_of(L) < 0x7fffffffL, "%s (global): too many (image, head, block) units for one grid", who);
     return ESVIT_OK;
 }
 
 }  // namespace
+
+// the statistics mode of the forward entry (ws = ESVIT_ATTN_GLOBAL | ESVIT_ATTN_STATS, include/esvit_hip.h)
+int esvit_flash_attn_stats(int dtype, const void* qkv, const int32_t* queries, int L, int ws, int nW, int nB, int N, int nH, int hd, float scale,
+                           const void* out, float* lse, float* attn_out, bool unused_are_null, hipStream_t stream) {
+    const char* who = "esvit_window_attn_fwd";
+    const int rc = check_mode(who, dtype, L, ws, nW, nB, N, nH, hd, true);
+    if (rc != ESVIT_OK) return rc;
+    const int nq = nW - 1;
+    ESVIT_CHECK_ARG(!out, "%s (global, stats): out must be NULL (the mode reads q and k only and writes no attention output)", who);
+    ESVIT_CHECK_ARG(attn_out, "%s (global, stats): attn_out (fp32 [nB, nH, nW, L]) is required", who);
+    ESVIT_CHECK_ARG(qkv && (queries || nq == 0), "%s (global, stats): qkv is required, and win2tok (the query list) for nW - 1 = %d queries", who, nq);
+    ESVIT_CHECK_ARG(unused_are_null, "%s (global, stats): qkv_bias, rel_table, region_ids and bias_frag_ws are not used, pass NULL", who);
+    ESVIT_CHECK_ARG((long)nB * nH * ((nq + 15) / 16) < 0x7fffffffL, "%s (global, stats): too many (image, head, query tile) units for one grid", who);
+    if (hd == 32) return stats_launch<32>((const bf16*)qkv, queries, nq, L, nB, nH, scale, attn_out, lse, stream);
+    return stats_launch<64>((const bf16*)qkv, queries, nq, L, nB, nH, scale, attn_out, lse, stream);
+}
 
 // esvit_query(ESVIT_Q_GLOBAL_ATTN_WS, nB * nH, L, backward): floats of the scratch the mode takes through bias_frag_ws (delta)
 int64_t esvit_i_global_attn_ws(int64_t Z, int64_t L, int64_t backward) {

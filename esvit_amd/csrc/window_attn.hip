@@ -798,6 +798,8 @@ int esvit_flash_attn_fwd(int dtype, const void* qkv, int L, int ws, int nW, int 
                          float* attn_out, hipStream_t stream);
 int esvit_flash_attn_bwd(int dtype, const void* qkv, int L, const void* dout, const void* fwd_out, const float* lse, int ws, float* scratch,
                          int nW, int nB, int N, int nH, int hd, float scale, void* dqkv, hipStream_t stream);
+int esvit_flash_attn_stats(int dtype, const void* qkv, const int32_t* queries, int L, int ws, int nW, int nB, int N, int nH, int hd, float scale,
+                           const void* out, float* lse, float* attn_out, bool unused_are_null, hipStream_t stream);
 
 // answers of esvit_query (lib.cpp)
 int esvit_i_attn_frag_elems(int N) { return N <= NP ? FRAG_ELEMS : (N <= esvit_big_npb() ? esvit_big_frag_elems() : -1); }
@@ -822,6 +824,11 @@ extern "C" int esvit_window_attn_fwd(int dtype, const void* qkv, const float* qk
                                      const float* rel_table, int ws, float* bias_frag_ws, const int32_t* region_ids, int nW, int nB, int N,
                                      int nH, int hd, float scale, void* out, float* lse, float* attn_out, esvit_stream_t s_) {
     STREAM(s_);
+    ESVIT_CHECK_ARG(!(ws > 0 && (ws & ESVIT_ATTN_STATS)) || (ws & ESVIT_ATTN_GLOBAL),
+                    "esvit_window_attn_fwd: ESVIT_ATTN_STATS is valid only together with ESVIT_ATTN_GLOBAL (ws = 0x%x)", (unsigned)ws);
+    if (ws > 0 && (ws & ESVIT_ATTN_GLOBAL) && (ws & ESVIT_ATTN_STATS) && !(ws & ESVIT_ATTN_SLIDING_CHUNK))  // entropy and listed rows of P
+        return esvit_flash_attn_stats(dtype, qkv, win2tok, L, ws, nW, nB, N, nH, hd, scale, out, lse, attn_out,
+                                      !qkv_bias && !rel_table && !region_ids && !bias_frag_ws, stream);
     if (ws > 0 && (ws & ESVIT_ATTN_GLOBAL))  // flash attention over whole crops of any length: one "window" of L tokens per image (esvit_hip.h)
         return esvit_flash_attn_fwd(dtype, qkv, L, ws, nW, nB, N, nH, hd, scale, out, lse, attn_out, stream);
     if (ws > 0 && (ws & ESVIT_ATTN_SLIDING_CHUNK))  // Vision Longformer's sliding-chunk attention: nW x N is the token grid (esvit_hip.h)
@@ -872,6 +879,8 @@ extern "C" int esvit_window_attn_bwd(int dtype, const void* qkv, const float* qk
                                      const int32_t* region_ids, int nW, int nB, int N, int nH, int hd, float scale, void* dqkv,
                                      float* dbias_ws, float* dpad_ws, esvit_stream_t s_) {
     STREAM(s_);
+    ESVIT_CHECK_ARG(!(ws > 0 && (ws & ESVIT_ATTN_STATS)) || (ws & ESVIT_ATTN_GLOBAL),
+                    "esvit_window_attn_bwd: ESVIT_ATTN_STATS is valid only together with ESVIT_ATTN_GLOBAL, in esvit_window_attn_fwd (ws = 0x%x)", (unsigned)ws);
     if (ws > 0 && (ws & ESVIT_ATTN_GLOBAL))
         return esvit_flash_attn_bwd(dtype, qkv, L, dout, fwd_out, lse, ws, bias_frag_ws, nW, nB, N, nH, hd, scale, dqkv, stream);
     if (ws > 0 && (ws & ESVIT_ATTN_SLIDING_CHUNK))

@@ -1583,6 +1583,73 @@ def vit_block_attention(x, nH, prm_list):
     return p.reshape(nB, nH, p.shape[-2], p.shape[-1])[:, :, :N, :N].float()
 
 
+def _vit_stats_route(o, hd, dtype):
+    """do the attention statistics take the kernels of flash_attn.hip (ops.global_attn_stats)?  For every N (37 and 197 tokens
+    included: one kernel serves all crops) when the ops module has the entry and supports the shape; an ops module without it (the CPU
+    restatement, oracle/ops_ref.py) or an unsupported shape (fp32 parity mode, other head dims) reduces P of the batched-GEMM route."""
+    if not hasattr(o, "global_attn_stats"):
+        return False
+    sup = getattr(o, "global_attn_stats_supported", None)
+    return sup is not None and bool(sup(dtype, hd))
+
+
+class _long_attention:
+    """with _long_attention("flash"): ... -- VIT_LONG_ATTENTION for the duration of a block of code (the analysis pass of
+    esvit_amd/analysis.py asks for the flash forward, so that no N x N tensor exists while it advances through the blocks either)"""
+
+    def __init__(self, route):
+        assert route in ("gemm", "flash")
+        self.route = route
+
+    def __enter__(self):
+        global VIT_LONG_ATTENTION
+        self.old, VIT_LONG_ATTENTION = VIT_LONG_ATTENTION, self.route
+
+    def __exit__(self, *exc):
+        global VIT_LONG_ATTENTION
+        VIT_LONG_ATTENTION = self.old
+
+
+_STATS_SLICE_ELEMS = 1 << 26  # fall-back route: at most this many probabilities (256 MB in fp32) at a time
+
+
+def vit_attention_stats(o, qkv, nB, N, nH, scale, queries=None):
+    """what an attention analysis reads of a block's softmax(scale q k^T), qkv [nB * N, 3C] -> (entropy fp32 [nB, nH, N] in nats with
+    0 log 0 = 0, rows fp32 [nB, nH, nq, N] of the listed query tokens or None).  The kernels of flash_attn.hip never form P; the
+    fall-back forms P of o.vit_attn_fwd for a slice of the batch at a time and reduces it in torch."""
+    hd = qkv.shape[1] // 3 // nH
+    if _vit_stats_route(o, hd, qkv.dtype):
+        ent, rows, _ = o.global_attn_stats(qkv, nB, N, nH, scale, queries=queries)
+        return ent, rows
+    idx = None
+    if queries is not None:
+        idx = torch.as_tensor(queries, device=qkv.device).reshape(-1).long()
+        if idx.numel() and not (0 <= int(idx.min()) and int(idx.max()) < N):
+            raise ValueError("vit_attention_stats: query indices must lie in [0, %d)" % N)
+    step = max(1, _STATS_SLICE_ELEMS // (nH * N * N))
+    ents, rows = [], []
+    for b0 in range(0, nB, step):
+        nb = min(step, nB - b0)
+        _, att = o.vit_attn_fwd(qkv[b0 * N:(b0 + nb) * N], nb, N, nH, scale)
+        p = att[-1]
+        p = p.reshape(nb, nH, p.shape[-2], p.shape[-1])[:, :, :N, :N].float()
+        ents.append(torch.special.entr(p).sum(-1))
+        if idx is not None:
+            rows.append(p.index_select(2, idx))
+    return torch.cat(ents), (torch.cat(rows) if idx is not None else None)
+
+
+def vit_block_attention_stats(x, nH, prm_list, queries=None):
+    """vit_attention_stats of a block's attention on its input x fp32 [nB, N, C] (LayerNorm and the qkv projection are recomputed, as
+    vit_block_attention does)"""
+    o = ops_module()
+    g1, b1, Wqkv_p, bqkv = prm_list[:4]
+    nB, N, C = x.shape
+    xw = o.layernorm_fwd(x.contiguous().view(nB * N, C), g1, b1, LN_EPS)[0]
+    qkv = o.linear_fwd(xw, _weight(Wqkv_p), bqkv)
+    return vit_attention_stats(o, qkv, nB, N, nH, (C // nH) ** -0.5, queries)
+
+
 # ------------------------------------------------------------------------------------------------
 # Vision Longformer (models/vision_longformer.py:406-770): an AttnBlock followed by its MlpBlock is one autograd node, like a ViT
 # block.  'full' stages project with one qkv Linear (vision_longformer.py:36-118); 'longformerhand' stages (layers/longformer2d.py)

@@ -1287,6 +1287,52 @@ def global_attn_bwd(dout, saved, B, N, nH, scale, dqkv=None):
     return dqkv
 
 
+# ---- attention statistics (csrc/flash_attn.hip): entropy of every softmax row and a few rows of P, without P ------------------------
+ATTN_STATS = 0x08000000  # ESVIT_ATTN_STATS: OR'd into ATTN_GLOBAL, selects the statistics mode of esvit_window_attn_fwd
+
+
+def global_attn_stats_supported(dtype, hd):
+    """the statistics kernels exist for this shape: bf16, head_dim 32 / 64 (any number of tokens)"""
+    return dtype == torch.bfloat16 and hd in (32, 64)
+
+
+def _stats_queries(queries, N, device):
+    """a list / range / int tensor of token indices -> int32 device tensor, every index checked against [0, N) here: the library
+    cannot read the array"""
+    if queries is None:
+        return None
+    if torch.is_tensor(queries):
+        q = queries.reshape(-1)
+        assert not q.dtype.is_floating_point and q.dtype != torch.bool, "queries: integer token indices"
+        if q.numel():
+            lo, hi = int(q.min()), int(q.max())
+            if lo < 0 or hi >= N:
+                raise ValueError("global_attn_stats: query indices must lie in [0, %d), got %d .. %d" % (N, lo, hi))
+        return q.to(device=device, dtype=torch.int32).contiguous()
+    idx = [int(i) for i in queries]
+    bad = [i for i in idx if not 0 <= i < N]
+    if bad:
+        raise ValueError("global_attn_stats: query indices must lie in [0, %d), got %r" % (N, bad[:8]))
+    return torch.tensor(idx, dtype=torch.int32, device=device)
+
+
+def global_attn_stats(qkv, B, N, nH, scale, queries=None, want_lse=False):
+    """what an attention analysis reads of softmax(scale q k^T), without the score tensor: qkv [B * N, 3C] ->
+    (entropy fp32 [B, nH, N] in nats, rows fp32 [B, nH, nq, N] of the listed queries or None, lse fp32 [B, nH, N] or None).
+    queries: a list or an integer tensor of token indices in [0, N), the same for every image and head; duplicates allowed."""
+    qkv = _actc(qkv)
+    Cc = qkv.shape[1] // 3
+    assert qkv.shape[0] == B * N
+    qidx = _stats_queries(queries, N, qkv.device)
+    nq = 0 if qidx is None else qidx.numel()
+    both = torch.empty((B, nH, 1 + nq, N), dtype=torch.float32, device=qkv.device)
+    lse = torch.empty((B, nH, N), dtype=torch.float32, device=qkv.device) if want_lse else None
+    check(lib.esvit_window_attn_fwd(_code(qkv.dtype), _p(qkv), None, _p(qidx) if nq else None, N, None, ATTN_GLOBAL | ATTN_STATS, None, None,
+                                    1 + nq, B, N, nH, Cc // nH, float(scale), None, _p(lse) if want_lse else None, _p(both), _stream()),
+          "window_attn_fwd(global, stats)")
+    return both[:, :, 0], (both[:, :, 1:] if queries is not None else None), lse
+
+
 # ---- fused sliding-chunk attention (csrc/chunk_attn.hip): the scores stay on the chip, nothing grows with N^2 --------------------
 ATTN_SLIDING_CHUNK = 0x40000000  # ESVIT_ATTN_SLIDING_CHUNK: OR'd into ws, selects the sliding-chunk mode of esvit_window_attn_fwd / _bwd
 CHUNK_W = 7                      # the chunk side the kernels are built for (every yaml of the reference)

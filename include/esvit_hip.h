@@ -375,9 +375,27 @@ int esvit_attn_branch_fwd(int dtype, const float* x, const float* gamma, const f
  *   scale        multiplies the fp32 scores (q enters the product as the bf16 it is)
  *   win2tok, qkv_bias, rel_table, region_ids, attn_out, dbias_ws, dpad_ws: not used, pass NULL
  * Every row of out / dqkv is written by exactly one workgroup; no atomics: two launches give identical bits.
+ *
+ * Statistics of the global mode (ws = ESVIT_ATTN_GLOBAL | ESVIT_ATTN_STATS, esvit_window_attn_fwd only; flash_attn.hip): what an
+ * attention analysis reads -- the entropy of every query's softmax row and the probability rows of a few listed queries -- from q and k
+ * alone: no v, no out, no tensor that grows with L^2.  Scores and probabilities are fp32 (the scores are not rounded to bf16 before the
+ * softmax, as the batched-GEMM route does).  The flag is valid only together with ESVIT_ATTN_GLOBAL: alone, with a window side, in
+ * esvit_window_attn_bwd or together with ESVIT_ATTN_SLIDING_CHUNK it is ESVIT_ERR_ARG before any launch.  The arguments mean:
+ *   L            tokens per image, >= 1;  N = L;  nW = 1 + nq, nq >= 0 the number of listed queries
+ *   win2tok      int32 [nq] on the device: token indices in [0, L) of the listed queries, the same for every image and head; duplicates
+ *                allowed; NULL when nq = 0.  The library cannot read the array: the caller checks the range (an index outside it yields
+ *                the row of a zero query, nothing is read or written out of bounds)
+ *   attn_out     fp32 [nB, nH, 1 + nq, L] (required): row 0 = entropy of every query, H = ln l - sum_k e^(s_k - m) (s_k - m) / l in nats
+ *                (m, l: maximum and sum of e^(s_k - m) of the row), accumulated online; rows 1 .. nq = softmax_k(scale q k) over all L keys
+ *                for the listed queries, from a normaliser of their own
+ *   lse          fp32 [nB, nH, L] or NULL: m + ln l of every query
+ *   hd, dtype, scale: as in the global mode
+ *   out must be NULL;  qkv_bias, rel_table, region_ids, bias_frag_ws: not used, pass NULL
+ * Every element has one writer; no atomics: two launches give identical bits.
  */
 #define ESVIT_ATTN_SLIDING_CHUNK 0x40000000
 #define ESVIT_ATTN_GLOBAL 0x20000000
+#define ESVIT_ATTN_STATS 0x08000000
 #define ESVIT_ATTN_SPLIT_DBIAS 0x10000000
 int esvit_window_attn_fwd(int dtype, const void* qkv, const float* qkv_bias, const int32_t* win2tok, int L,
                           const float* rel_table, int ws, float* bias_frag_ws, const int32_t* region_ids, int nW, int nB,
