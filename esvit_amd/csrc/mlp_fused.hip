@@ -384,6 +384,11 @@ int esvit_i_mlp16_bwd(const float* x, const float* gy, const float* rs_mlp, cons
                       const void* W1p, const void* W2Tp, const void* W1T, const float* b1, long M, int C, float* gx, void* gxa, void* xhat,
                       void* a1g, void* da1, hipStream_t stream);
 
+// weight gradients on the chip (mlp_fused_dw.hip): bf16, C = 96
+int esvit_i_mlp_dw_bwd(const float* x, const float* gy, const float* rs_mlp, const float* rs_out, const float* gamma, const float* beta, float eps,
+                       const void* W1p, const void* W2Tp, const float* b1, long M, float* gx, void* gxa, float* dW2, float* G, float* db1, float* db2,
+                       float* ws, hipStream_t stream);
+
 #define AL16(p_) (((uintptr_t)(p_) % 16) == 0)
 
 extern "C" int esvit_mlp_fused_fwd(int dtype, const float* x, const float* gamma, const float* beta, float eps, const void* W1,
@@ -423,9 +428,19 @@ extern "C" int esvit_mlp_fused_fwd_train(int dtype, const float* x, const float*
 extern "C" int esvit_mlp_fused_bwd(int dtype, const float* x, const float* gy, const float* rowscale_mlp, const float* rowscale_out,
                                    const float* gamma, const float* beta, float eps, const void* W1, const void* W2T, const void* W1T,
                                    const float* b1, int64_t M, int C, float* gx, void* gx_act, void* xhat, void* a1g, void* da1,
-                                   esvit_stream_t s_) {
+                                   esvit_stream_t s_, float* dW2, float* G, float* db1, float* db2, float* partials_ws) {
     hipStream_t stream = reinterpret_cast<hipStream_t>(s_);
     ESVIT_CHECK_ARG(esvit_i_mlp_fused_supported(dtype, C) & 2, "esvit_mlp_fused_bwd: bf16 activations and C in {96, 128, 192, 256} only (C=%d)", C);
+    const int ndw = (dW2 != nullptr) + (G != nullptr) + (db1 != nullptr) + (db2 != nullptr) + (partials_ws != nullptr);
+    ESVIT_CHECK_ARG(ndw == 0 || ndw == 5, "esvit_mlp_fused_bwd: dW2, G, db1, db2 and partials_ws come together (%d of 5 given)", ndw);
+    if (ndw == 5) {
+        ESVIT_CHECK_ARG(C == 96, "esvit_mlp_fused_bwd: the on-chip weight gradients exist at C = 96 only (C=%d)", C);
+        ESVIT_CHECK_ARG(x && gy && gamma && beta && W1 && W2T && b1 && gx && gx_act && M > 0, "esvit_mlp_fused_bwd: null pointer / empty input");
+        ESVIT_CHECK_ARG(AL16(x) && AL16(gy) && AL16(gx) && AL16(gx_act) && AL16(W1) && AL16(W2T) && AL16(gamma) && AL16(beta) && AL16(b1) && AL16(dW2) &&
+                            AL16(G) && AL16(partials_ws),
+                        "esvit_mlp_fused_bwd: operands must be 16-byte aligned");
+        return esvit_i_mlp_dw_bwd(x, gy, rowscale_mlp, rowscale_out, gamma, beta, eps, W1, W2T, b1, M, gx, gx_act, dW2, G, db1, db2, partials_ws, stream);
+    }
     ESVIT_CHECK_ARG(x && gy && gamma && beta && W1 && W2T && W1T && b1 && gx && gx_act && xhat && a1g && da1 && M > 0,
                     "esvit_mlp_fused_bwd: null pointer / empty input");
     ESVIT_CHECK_ARG(AL16(x) && AL16(gy) && AL16(gx) && AL16(gx_act) && AL16(xhat) && AL16(a1g) && AL16(da1) && AL16(W1) && AL16(W2T) &&

@@ -208,9 +208,28 @@ def _mlp_fused_train(W1, C):
     return MLP_FUSED_TRAIN and ops_module().mlp_fused_supported(W1.dtype, C, backward=True)
 
 
+# stage 0 (bf16, C = 96): the same kernel also accumulates dW2, db2, G and db1 on the chip, so GELU(A), dA and xhat are never written
+# and the two weight-gradient GEMMs with their split-K reduces disappear (esvit_mlp_fused_bwd's trailing arguments).  "0": A-B runs.
+MLP_DW_ONCHIP = os.environ.get("ESVIT_MLP_DW_ONCHIP", "1") != "0"
+
+
+def _mlp_dw_onchip(o, W1, C):
+    return MLP_DW_ONCHIP and hasattr(o, "mlp_fused_bwd_dw") and o.mlp_fused_dw_supported(W1.dtype, C)
+
+
 def _mlp_branch_bwd(o, x1, gy, dyb, g2, b2, W1, bfc1, params, dp_mlp, dp_out):
     """-> (gx1 fp32, gx1 act copy (scaled by dp_out), dg2, db2, dW1, dbfc1, dW2, dbfc2); dyb: cast(dp_mlp * gy) [M, C] act"""
     g2_p, b2_p, W1_p, bfc1_p, W2_p, bfc2_p = params
+    if _mlp_dw_onchip(o, W1, x1.shape[1]):
+        ln2 = _ln_sinks(g2_p, b2_p)
+        wsink, bsink = P.grad_out(W1_p), P.grad_out(bfc1_p)
+        w2sink, b2sink = P.grad_out(W2_p), P.grad_out(bfc2_p)
+        gx1, dyw, dW2, dbfc2, G, dbfc1 = o.mlp_fused_bwd_dw(x1, gy, g2, b2, LN_EPS, _mlp_w(W1_p, "MLP_W1_BWD"), _mlp_w(W2_p, "MLP_W2T_BWD"),
+                                                            _mlp_w(W1_p, "MLP_W1T_BWD"), bfc1, rowscale_mlp=dp_mlp, rowscale_out=dp_out,
+                                                            out=(w2sink, wsink), db_out=(b2sink, bsink))
+        # the fold is a leaf of the chain like the GEMMs it used to follow: same side stream, same join
+        dW1, dg2, db2 = _side_run(lambda: o.ln_fold_finish(G, dbfc1, W1_p.detach(), g2, b2, gb_out=ln2), G, dbfc1)
+        return gx1, dyw, _alias(dg2, ln2), _alias(db2, ln2), _alias(dW1, wsink), _alias(dbfc1, bsink), _alias(dW2, w2sink), _alias(dbfc2, b2sink)
     gx1, dyw, xhat, a1g, da1 = o.mlp_fused_bwd(x1, gy, g2, b2, LN_EPS, _mlp_w(W1_p, "MLP_W1_BWD"), _mlp_w(W2_p, "MLP_W2T_BWD"), _mlp_w(W1_p, "MLP_W1T_BWD"), bfc1,
                                                rowscale_mlp=dp_mlp, rowscale_out=dp_out)
     ln2 = _ln_sinks(g2_p, b2_p)
@@ -306,7 +325,8 @@ class SwinBlockFn(torch.autograd.Function):
         gy = gy.contiguous().view(M, C)
         Wqkv_p, Wproj_p, W1_p, W2_p = ctx.wparams
         # ---- MLP branch ----
-        dyb = o.gather_cast(gy, M, rowscale=dp2, rows_per_sample=L)
+        onchip = ctx.fused_mlp and _mlp_dw_onchip(o, W1, C)  # (the kernel scales and casts gy itself: no activation-dtype copy is read)
+        dyb = None if onchip else o.gather_cast(gy, M, rowscale=dp2, rows_per_sample=L)
         if ctx.fused_mlp:
             rs2 = None if dp2 is None else dp2.repeat_interleave(L)
             rs1 = None if dp1 is None else dp1.repeat_interleave(L)
@@ -465,7 +485,10 @@ class SwinBlockMultiFn(torch.autograd.Function):
         Wqkv_p, Wproj_p, W1_p, W2_p = ctx.wparams
         g1_p, b1_p, table_p, bqkv_p, bproj_p, g2_p, b2_p, bfc1_p, bfc2_p = ctx.sparams
         # ---- MLP branch ----
-        dyb = gysh.contiguous() if gysh is not None else o.gather_cast(gy, M, rowscale=dp2, rows_per_sample=1)
+        if gysh is not None:
+            dyb = gysh.contiguous()
+        else:
+            dyb = None if (ctx.fused_mlp and _mlp_dw_onchip(o, W1, C)) else o.gather_cast(gy, M, rowscale=dp2, rows_per_sample=1)
         if ctx.fused_mlp:
             gx1, dyw, dg2, db2, dW1, dbfc1, dW2, dbfc2 = _mlp_branch_bwd(o, x1, gy, dyb, g2, b2, W1, bfc1,
                                                                           (g2_p, b2_p, W1_p, bfc1_p, W2_p, bfc2_p), dp2, dp1)

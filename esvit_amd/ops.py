@@ -84,7 +84,8 @@ def relative_position_index(ws):
 # esvit_query questions (include/esvit_hip.h)
 (Q_ATTN_FRAG_ELEMS, Q_ATTN_LSE_ELEMS, Q_ATTN_BWD_PARTS, Q_ATTN_BWD_PAD_ROWS, Q_LN_BWD_BLOCKS, Q_COLSUM_BLOCKS, Q_COL_REDUCE_BLOCKS,
  Q_UPDATE_CHUNK_ELEMS, Q_MLP_FUSED, Q_AUG_MAX_BOX, Q_JPEG_WORKSPACE, Q_RESIZE_FITS, Q_CHUNK_ATTN_WS, Q_TOPK_WS, Q_PROBE_CE_REG_ROW,
- Q_GLOBAL_ATTN_WS) = range(1, 17)
+ Q_GLOBAL_ATTN_WS, Q_MLP_DW_WS) = range(1, 18)
+MLP_DW_PARTIAL_FLOATS = 74208  # ESVIT_MLP_DW_PARTIAL_FLOATS
 
 
 def query(what, a=0, b=0, c=0):
@@ -475,8 +476,49 @@ def mlp_fused_bwd(x, gy, gamma, beta, eps, W1, W2T, W1T, b1, *, rowscale_mlp=Non
     a1g = torch.empty((M, 4 * Cc), dtype=dt, device=x.device)
     da1 = torch.empty((M, 4 * Cc), dtype=dt, device=x.device)
     check(lib.esvit_mlp_fused_bwd(_code(dt), _p(x), _p(gy), _p(rowscale_mlp), _p(rowscale_out), _p(_f32c(gamma)), _p(_f32c(beta)), eps, _p(W1),
-                                  _p(W2T), _p(W1T), _p(_f32c(b1)), M, Cc, _p(gx), _p(gxa), _p(xhat), _p(a1g), _p(da1), _stream()), "mlp_fused_bwd")
+                                  _p(W2T), _p(W1T), _p(_f32c(b1)), M, Cc, _p(gx), _p(gxa), _p(xhat), _p(a1g), _p(da1), _stream(),
+                                  None, None, None, None, None), "mlp_fused_bwd")
     return gx, gxa, xhat, a1g, da1
+
+
+def mlp_fused_dw_supported(dt, Cc):
+    """esvit_mlp_fused_bwd can accumulate the branch's weight gradients on the chip at this dtype and width (bf16, C = 96)"""
+    return query(Q_MLP_DW_WS, _code(dt), int(Cc), 1) > 0
+
+
+def mlp_fused_dw_grid(dt, Cc, M):
+    """workgroups (= partials, = the summation order) of the on-chip weight-gradient mode for M rows on the current device"""
+    return query(Q_MLP_DW_WS, _code(dt), int(Cc), int(M)) // (4 * MLP_DW_PARTIAL_FLOATS)
+
+
+def mlp_fused_bwd_dw(x, gy, gamma, beta, eps, W1, W2T, W1T, b1, *, rowscale_mlp=None, rowscale_out=None, out=None, db_out=None):
+    """mlp_fused_bwd with the weight gradients accumulated on the chip: nothing hidden-sized is written ->
+    (gx fp32 [M, C], gx_act act [M, C], dW2 fp32 [C, 4C], db2 fp32 [C], G fp32 [4C, C] = dA^T xhat, db1 fp32 [4C]); G and db1 go on to
+    ln_fold_finish.  out = (dW2, G), db_out = (db2, db1): the fp32 tensors to write them to (gradient-bucket slots), each or any None"""
+    x, gy, W1, W2T, W1T = _f32c(x), _f32c(gy), _actc(W1), _actc(W2T), _actc(W1T)
+    M, Cc = x.shape
+    assert gy.shape == x.shape and W1.shape == (4 * Cc, Cc) and W2T.shape == (4 * Cc, Cc) and W1T.shape == (Cc, 4 * Cc)
+    dt = W1.dtype
+    dev = x.device
+    dW2, G = out if out is not None else (None, None)
+    db2, db1 = db_out if db_out is not None else (None, None)
+    dW2 = dW2 if dW2 is not None else torch.empty((Cc, 4 * Cc), dtype=torch.float32, device=dev)
+    G = G if G is not None else torch.empty((4 * Cc, Cc), dtype=torch.float32, device=dev)
+    db2 = db2 if db2 is not None else torch.empty((Cc,), dtype=torch.float32, device=dev)
+    db1 = db1 if db1 is not None else torch.empty((4 * Cc,), dtype=torch.float32, device=dev)
+    assert dW2.shape == (Cc, 4 * Cc) and G.shape == (4 * Cc, Cc) and db2.shape == (Cc,) and db1.shape == (4 * Cc,)
+    for t in (dW2, G, db2, db1):
+        _f32c(t)
+    nbytes = query(Q_MLP_DW_WS, _code(dt), Cc, M)
+    if nbytes <= 0:
+        raise RuntimeError("mlp_fused_bwd_dw: no on-chip weight-gradient mode at dtype %s, C = %d" % (dt, Cc))
+    ws = workspace(nbytes // 4, dev)
+    gx = torch.empty_like(x)
+    gxa = torch.empty((M, Cc), dtype=dt, device=dev)
+    check(lib.esvit_mlp_fused_bwd(_code(dt), _p(x), _p(gy), _p(rowscale_mlp), _p(rowscale_out), _p(_f32c(gamma)), _p(_f32c(beta)), eps, _p(W1),
+                                  _p(W2T), _p(W1T), _p(_f32c(b1)), M, Cc, _p(gx), _p(gxa), None, None, None, _stream(),
+                                  _p(dW2), _p(G), _p(db1), _p(db2), _p(ws)), "mlp_fused_bwd(dw)")
+    return gx, gxa, dW2, db2, G, db1
 
 
 def ln_fold_finish(G, db, W, gamma, beta, *, gb_out=None):

@@ -58,6 +58,9 @@ const char* esvit_last_error(void);
  *                                              per row); longer rows take one workgroup per row and three sweeps
  *   ESVIT_Q_GLOBAL_ATTN_WS (nB*nH, L, backward) floats of the scratch the global mode of esvit_window_attn_fwd (backward = 0: none) /
  *                                              esvit_window_attn_bwd (backward = 1) takes through bias_frag_ws; linear in L
+ *   ESVIT_Q_MLP_DW_WS (dtype, C, M)            BYTES of partials_ws of esvit_mlp_fused_bwd's on-chip weight-gradient mode for M rows: one partial of
+ *                                              ESVIT_MLP_DW_PARTIAL_FLOATS floats per workgroup of the launch (one per CU, at most one per 64 rows);
+ *                                              0 where the mode does not exist (anything but bf16, C = 96)
  * Unknown `what` returns ESVIT_ERR_ARG. */
 #define ESVIT_Q_ATTN_FRAG_ELEMS 1
 #define ESVIT_Q_ATTN_LSE_ELEMS 2
@@ -75,6 +78,8 @@ const char* esvit_last_error(void);
 #define ESVIT_Q_TOPK_WS 14
 #define ESVIT_Q_PROBE_CE_REG_ROW 15
 #define ESVIT_Q_GLOBAL_ATTN_WS 16
+#define ESVIT_Q_MLP_DW_WS 17
+#define ESVIT_MLP_DW_PARTIAL_FLOATS 74208 /* dW2 96 x 384 + G 384 x 96 + db1 384 + db2 96 */
 int64_t esvit_query(int what, int64_t a, int64_t b, int64_t c);
 
 /* ---- host-side integer index maps (bit-exact vs reference) -------------
@@ -205,6 +210,14 @@ int esvit_gemm_select(int dtype, const esvit_gemm_desc* d, int* tile_m, int* til
  *     gx      fp32 [M, C]   dL/dx = gy + LN'(dH)                 gx_act  act [M, C]  cast(rowscale_out[row] * gx) (NULL scale = 1)
  *     xhat    act [M, C]    (x - mean) rstd                      a1g     act [M, 4C] GELU(A)          da1  act [M, 4C]  dA
  *   The weight gradients are two esvit_gemm calls: dW2 = (rowscale gy)^T a1g, and G = da1^T xhat, db1 = colsum(da1) followed by
+ *   esvit_ln_fold_finish.
+ *   Weight gradients on the chip (trailing arguments dW2, G, db1, db2, partials_ws; bf16 and C = 96 only): with all five given the
+ *   same call also returns   dW2 fp32 [C, 4C] = (rowscale gy)^T GELU(A),   db2 fp32 [C] = colsum(rowscale gy),
+ *   G fp32 [4C, C] = dA^T xhat,   db1 fp32 [4C] = colsum(dA)   (overwritten; G and db1 go on to esvit_ln_fold_finish), accumulated in
+ *   registers by persistent workgroups and summed from per-workgroup partials in index order by a second launch of the same call (no
+ *   atomics: identical launches give identical bits).  partials_ws: esvit_query(ESVIT_Q_MLP_DW_WS, dtype, C, M) bytes, 16-byte aligned,
+ *   contents need not be initialised.  xhat, a1g and da1 are not written in this mode and may be NULL; W1T is not read.  All five
+ *   NULL: the mode above, unchanged.  Any other combination, or the five given at another dtype / C: ESVIT_ERR_ARG before any launch.
  * esvit_ln_fold_finish: LayerNorm folded out of a weight gradient.  With LN(x) = xhat o gamma + beta and G = dY^T xhat [J, C],
  *   db = colsum(dY) [J], W the fp32 master [J, C]:  dW = G o gamma + db (x) beta (written over G),
  *   dgamma[c] (+)= sum_j W[j, c] G[j, c],  dbeta[c] (+)= sum_j db[j] W[j, c]   (swin_transformer.py:331 autograd).
@@ -224,7 +237,7 @@ int esvit_mlp_fused_fwd_train(int dtype, const float* x, const float* gamma, con
 int esvit_mlp_fused_bwd(int dtype, const float* x, const float* gy, const float* rowscale_mlp, const float* rowscale_out,
                         const float* gamma, const float* beta, float eps, const void* W1, const void* W2T, const void* W1T,
                         const float* b1, int64_t M, int C, float* gx, void* gx_act, void* xhat, void* a1g, void* da1,
-                        esvit_stream_t stream);
+                        esvit_stream_t stream, float* dW2, float* G, float* db1, float* db2, float* partials_ws);
 int esvit_ln_fold_finish(float* G, const float* db, const float* W, const float* gamma, const float* beta, int J, int C,
                          float* dgamma, float* dbeta, int accumulate, esvit_stream_t stream);
 /* The weight copies the fused kernels stream, produced from the fp32 masters (fc1.weight [4C, C], fc2.weight [C, 4C]); fc2.weight

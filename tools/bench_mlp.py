@@ -1,5 +1,6 @@
 """fused MLP forward (esvit_mlp_fused_fwd) vs the unfused LayerNorm -> fc1 -> fc2 sequence on the stage-0 / stage-1 row counts
-of one Swin-T W7 step (run on the MI355X): python tools/bench_mlp.py [--batch 128]"""
+of one Swin-T W7 step (run on the MI355X): python tools/bench_mlp.py [--batch 128] [--bwd-only]
+--bwd-only: the backward legs alone -- kernel, kernel + two weight-gradient GEMMs + fold, and (C = 96) the on-chip weight-gradient mode + fold"""
 import argparse, json, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -24,7 +25,9 @@ def timeit(fn, iters=10, warm=2):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=128)
-    B = ap.parse_args().batch
+    ap.add_argument("--bwd-only", action="store_true")
+    args = ap.parse_args()
+    B = args.batch
     dt = torch.bfloat16
     for C, rows_s, rows_t in ((96, B * (2 * 3136 + 8 * 576), B * 2 * 3136), (192, B * (2 * 784 + 8 * 144), B * 2 * 784)):
         # ---- training branch: forward + backward, fused (recompute) vs the unfused sequence of the same step ----
@@ -60,7 +63,20 @@ def main():
             dW2, dbb = ops.linear_wgrad(dyb, a1g_, want_bias=True)
             G, dbb1 = ops.linear_wgrad(da1_, xhat, want_bias=True)
             return ops.ln_fold_finish(G, dbb1, W1f, g, b)
+        def fus_bwd_dw():  # weight gradients accumulated by the data-gradient kernel itself: kernel + partial reduce + fold
+            gx, gxa, dW2, db2, G, dbb1 = ops.mlp_fused_bwd_dw(x, gy, g, b, 1e-6, K1, W2T, W1T, b1)
+            return ops.ln_fold_finish(G, dbb1, W1f, g, b)
         res = dict(C=C, rows=M, who="student")
+        if args.bwd_only:
+            for name, fn in (("fused_bwd_kernel", fus_bwd_kernel), ("fused_bwd_all", fus_bwd)) + ((("fused_bwd_dw_all", fus_bwd_dw),) if ops.mlp_fused_dw_supported(dt, C) else ()):
+                res[name + "_us"] = round(timeit(fn, iters=20, warm=3) * 1e6, 1)
+            if "fused_bwd_dw_all_us" in res:
+                res["dw_speedup"] = round(res["fused_bwd_all_us"] / res["fused_bwd_dw_all_us"], 2)
+                res["fused_bwd_dw_GBs"] = round(M * C * 14 / res["fused_bwd_dw_all_us"] / 1e3)
+            print(json.dumps(res), flush=True)
+            continue
+        if ops.mlp_fused_dw_supported(dt, C):
+            res["fused_bwd_dw_all_us"] = round(timeit(fus_bwd_dw) * 1e6, 1)
         for name, fn in (("unfused_fwd", unf_fwd), ("fused_fwd", lambda: ops.mlp_fused_fwd(x, g, b, 1e-6, K1f, b1, W2, b2)),
                          ("fused_fwd_nextnorm", lambda: ops.mlp_fused_fwd(x, g, b, 1e-6, K1f, b1, W2, b2, next_norm=(g, b))),
                          ("unfused_bwd", unf_bwd), ("fused_bwd_kernel", fus_bwd_kernel), ("fused_bwd_all", fus_bwd)):
