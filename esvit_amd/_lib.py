@@ -58,6 +58,22 @@ class JpegDesc(C.Structure):
     ]
 
 
+class GridGroup(C.Structure):
+    """esvit_grid_group: one resolution group of a grouped launch (a negative batch / row count -G turns the first pointer argument of
+    esvit_pad_crop_tokens / esvit_dwconv3x3 / esvit_col_sums2 / esvit_col_affine2 into a host array of G of these)"""
+    _fields_ = [
+        ("p0", vp), ("p1", vp), ("out", vp),
+        ("a1", vp), ("a2", vp), ("a3", vp),
+        ("nB", i32), ("H", i32), ("W", i32),
+        ("Hd", i32), ("Wd", i32),
+        ("C", i32), ("dtype", i32),
+        ("reserved", i32),
+    ]
+
+
+MAX_GRID_GROUPS = 4
+
+
 # name -> (restype, argtypes); every symbol declared in include/esvit_hip.h
 SIGNATURES = {
     "esvit_version": (C.c_int, []),

@@ -175,9 +175,12 @@ __device__ __forceinline__ void store4c(bf16* p, f32x4 v) {
     *reinterpret_cast<bf16x4*>(p) = bf16x4{(bf16)v[0], (bf16)v[1], (bf16)v[2], (bf16)v[3]};
 }
 
+// The bodies of the kernels that have a grouped mode (include/esvit_hip.h) take the block's index and the block count of ITS range
+// (bid, nblk): the plain kernels pass blockIdx.x / gridDim.x, the grouped ones the position inside the group's slice of the grid --
+// the same instructions on the same elements in the same order either way.
 template <typename T>
-__global__ __launch_bounds__(256) void dwconv3x3_kernel(const T* __restrict__ x, const float* __restrict__ w, int flip, int nB, int H, int W, int C,
-                                                        T* __restrict__ y) {
+__device__ __forceinline__ void dwconv3x3_body(const T* __restrict__ x, const float* __restrict__ w, int flip, int nB, int H, int W, int C,
+                                               T* __restrict__ y, long bid, long nblk) {
     const int c = threadIdx.x * 4, PY = blockDim.y;
     f32x4 wt[9];  // wt[t][e] = tap t of channel c+e
 #pragma unroll
@@ -187,7 +190,7 @@ __global__ __launch_bounds__(256) void dwconv3x3_kernel(const T* __restrict__ x,
         for (int e = 0; e < 4; ++e) wt[t][e] = w[(c + e) * 9 + ts];
     }
     const long P = (long)nB * H * W;
-    for (long p = (long)blockIdx.x * PY + threadIdx.y; p < P; p += (long)gridDim.x * PY) {
+    for (long p = bid * PY + threadIdx.y; p < P; p += nblk * PY) {
         const int ix = (int)(p % W), iy = (int)((p / W) % H);
         const long b = p / ((long)W * H);
         f32x4 acc = {0.f, 0.f, 0.f, 0.f};
@@ -204,6 +207,12 @@ __global__ __launch_bounds__(256) void dwconv3x3_kernel(const T* __restrict__ x,
         }
         store4c(y + p * C + c, acc);
     }
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void dwconv3x3_kernel(const T* __restrict__ x, const float* __restrict__ w, int flip, int nB, int H, int W, int C,
+                                                        T* __restrict__ y) {
+    dwconv3x3_body<T>(x, w, flip, nB, H, W, C, y, blockIdx.x, gridDim.x);
 }
 
 // ws[blk][(c+e)*9 + t] = sum over the block's positions of x(shifted by tap t) * dy
@@ -261,8 +270,8 @@ __device__ __forceinline__ void dw_load_row(const bf16* __restrict__ row, int ix
     }
 }
 
-__global__ __launch_bounds__(256) void dwconv3x3_strip_kernel(const bf16* __restrict__ x, const float* __restrict__ w, int flip, int nB, int H, int W,
-                                                              int C, bf16* __restrict__ y) {
+__device__ __forceinline__ void dwconv3x3_strip_body(const bf16* __restrict__ x, const float* __restrict__ w, int flip, int nB, int H, int W, int C,
+                                                     bf16* __restrict__ y, long bid, long nblk) {
     const int c = threadIdx.x * 8, PY = blockDim.y;
     // the 72 taps of this thread's eight channels are contiguous in w [C][9]: eighteen 16-byte loads
     float wraw[72];
@@ -279,7 +288,7 @@ __global__ __launch_bounds__(256) void dwconv3x3_strip_kernel(const bf16* __rest
         for (int e = 0; e < 8; ++e) wt[t][e] = flip ? wraw[e * 9 + 8 - t] : wraw[e * 9 + t];
     const int strips_w = (W + DW_SW - 1) / DW_SW;
     const long S = (long)nB * H * strips_w;
-    for (long s = (long)blockIdx.x * PY + threadIdx.y; s < S; s += (long)gridDim.x * PY) {
+    for (long s = bid * PY + threadIdx.y; s < S; s += nblk * PY) {
         const int ix0 = (int)(s % strips_w) * DW_SW;
         const long t = s / strips_w;
         const int iy = (int)(t % H);
@@ -311,6 +320,11 @@ __global__ __launch_bounds__(256) void dwconv3x3_strip_kernel(const bf16* __rest
             st16<bf16>(y + ((b * H + iy) * (long)W + ix0 + o) * C + c, ov);
         }
     }
+}
+
+__global__ __launch_bounds__(256) void dwconv3x3_strip_kernel(const bf16* __restrict__ x, const float* __restrict__ w, int flip, int nB, int H, int W,
+                                                              int C, bf16* __restrict__ y) {
+    dwconv3x3_strip_body(x, w, flip, nB, H, W, C, y, blockIdx.x, gridDim.x);
 }
 
 // ws[blk][(c+e)*9 + t]: the same partial layout as dwconv3x3_wgrad_kernel
@@ -366,13 +380,13 @@ __global__ __launch_bounds__(256) void dwconv3x3_wgrad_strip_kernel(const bf16* 
 
 // ws[blk][0..C) = sum_r a[r][c],  ws[blk][C..2C) = sum_r a[r][c] * b[r][c]
 template <typename T>
-__global__ __launch_bounds__(256) void col_sums2_kernel(const T* __restrict__ a, const T* __restrict__ b, long rows, int C,
-                                                        float* __restrict__ ws) {
+__device__ __forceinline__ void col_sums2_body(const T* __restrict__ a, const T* __restrict__ b, long rows, int C, float* __restrict__ ws, long bid,
+                                               long nblk) {
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     f32x4* sm = reinterpret_cast<f32x4*>(smem_raw);  // [PY][C4][2]
     const int c4 = threadIdx.x, c = c4 * 4, PY = blockDim.y, C4 = blockDim.x;
     f32x4 s1 = {0.f, 0.f, 0.f, 0.f}, s2 = {0.f, 0.f, 0.f, 0.f};
-    for (long r = (long)blockIdx.x * PY + threadIdx.y; r < rows; r += (long)gridDim.x * PY) {
+    for (long r = bid * PY + threadIdx.y; r < rows; r += nblk * PY) {
         const f32x4 av = load4c(a + r * C + c);
         s1 += av;
         s2 += av * load4c(b + r * C + c);
@@ -385,9 +399,15 @@ __global__ __launch_bounds__(256) void col_sums2_kernel(const T* __restrict__ a,
             s1 += sm[(yy * C4 + c4) * 2 + 0];
             s2 += sm[(yy * C4 + c4) * 2 + 1];
         }
-        store4c(ws + (long)blockIdx.x * 2 * C + c, s1);
-        store4c(ws + (long)blockIdx.x * 2 * C + C + c, s2);
+        store4c(ws + bid * 2 * C + c, s1);
+        store4c(ws + bid * 2 * C + C + c, s2);
     }
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void col_sums2_kernel(const T* __restrict__ a, const T* __restrict__ b, long rows, int C,
+                                                        float* __restrict__ ws) {
+    col_sums2_body<T>(a, b, rows, C, ws, blockIdx.x, gridDim.x);
 }
 
 // The same sums for C > 1024 (more channel lanes than a workgroup has threads; the DINO head's BatchNorm at hidden_dim = 2048): the
@@ -411,9 +431,9 @@ __global__ __launch_bounds__(256) void col_sums2_wide_kernel(const T* __restrict
 // ACT 0: y = a1 x1 + a2 x2 + a3;  1: y = GELU(a1 x1 + a3);  2: y = x2 * GELU'(a1 x1 + a3);  3: y = max(a1 x1 + a3, 0);
 // 4: y = x2 where a1 x1 + a3 > 0, else 0  (BatchNorm + ReLU of the residual stem and its backward)
 template <typename T, int ACT>
-__global__ void col_affine2_kernel(const T* __restrict__ x1, const T* __restrict__ x2, long n, int C, const float* __restrict__ a1,
-                                   const float* __restrict__ a2, const float* __restrict__ a3, T* __restrict__ y) {
-    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
+__device__ __forceinline__ void col_affine2_body(const T* __restrict__ x1, const T* __restrict__ x2, long n, int C, const float* __restrict__ a1,
+                                                 const float* __restrict__ a2, const float* __restrict__ a3, T* __restrict__ y, long bid, long nblk) {
+    for (long i = bid * blockDim.x + threadIdx.x; i < n; i += nblk * blockDim.x) {
         const int c = (int)(i % C);
         float v = a1[c] * to_f32(x1[i]) + a3[c];
         if constexpr (ACT == 0) {
@@ -429,6 +449,12 @@ __global__ void col_affine2_kernel(const T* __restrict__ x1, const T* __restrict
         }
         y[i] = from_f32<T>(v);
     }
+}
+
+template <typename T, int ACT>
+__global__ void col_affine2_kernel(const T* __restrict__ x1, const T* __restrict__ x2, long n, int C, const float* __restrict__ a1,
+                                   const float* __restrict__ a2, const float* __restrict__ a3, T* __restrict__ y) {
+    col_affine2_body<T, ACT>(x1, x2, n, C, a1, a2, a3, y, blockIdx.x, gridDim.x);
 }
 
 // BatchNorm2d coefficient arithmetic on [C]-sized vectors (one launch instead of ~15 tiny elementwise launches per layer).
@@ -487,11 +513,12 @@ __global__ void bn_bwd_coeffs_kernel(const float* __restrict__ red, float n, con
 
 // dst[b, y, x, :] = src[b, y, x, :] if (y < Hs && x < Ws) else 0, for y < Hd, x < Wd: zero-pads (Hd > Hs) or crops (Hd < Hs) a token grid
 template <typename T>
-__global__ void pad_crop_kernel(const T* __restrict__ src, int nB, int Hs, int Ws, int Hd, int Wd, int C, T* __restrict__ dst) {
+__device__ __forceinline__ void pad_crop_body(const T* __restrict__ src, int nB, int Hs, int Ws, int Hd, int Wd, int C, T* __restrict__ dst, long bid,
+                                              long nblk) {
     constexpr int VEC = ElemTraits<T>::VEC;
     const int CV = C / VEC;
     const long total = (long)nB * Hd * Wd * CV;
-    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+    for (long i = bid * blockDim.x + threadIdx.x; i < total; i += nblk * blockDim.x) {
         const int cv = (int)(i % CV);
         const long p = i / CV;
         const int x = (int)(p % Wd), y = (int)((p / Wd) % Hd);
@@ -500,6 +527,100 @@ __global__ void pad_crop_kernel(const T* __restrict__ src, int nB, int Hs, int W
         if (y < Hs && x < Ws) v = ld16<T>(src + ((b * Hs + y) * Ws + x) * C + cv * VEC);
         st16<T>(dst + p * C + cv * VEC, v);
     }
+}
+
+template <typename T>
+__global__ void pad_crop_kernel(const T* __restrict__ src, int nB, int Hs, int Ws, int Hd, int Wd, int C, T* __restrict__ dst) {
+    pad_crop_body<T>(src, nB, Hs, Ws, Hd, Wd, C, dst, blockIdx.x, gridDim.x);
+}
+
+// ---- grouped mode (include/esvit_hip.h): up to four grids of different geometry in one launch.  The records travel in the kernel's argument
+// block; group g owns the blocks [blk0[g], blk0[g + 1]) of the grid, as many as the plain call on that group would launch, and runs the plain
+// body on them.  A block finds its group with three compares of a uniform value (unused groups start at INT_MAX).
+struct GroupArgs {
+    const void* p0[ESVIT_MAX_GRID_GROUPS];
+    const void* p1[ESVIT_MAX_GRID_GROUPS];
+    void* out[ESVIT_MAX_GRID_GROUPS];
+    const float* a1[ESVIT_MAX_GRID_GROUPS];
+    const float* a2[ESVIT_MAX_GRID_GROUPS];
+    const float* a3[ESVIT_MAX_GRID_GROUPS];
+    long rows[ESVIT_MAX_GRID_GROUPS];  // nB * H * W
+    int nB[ESVIT_MAX_GRID_GROUPS], H[ESVIT_MAX_GRID_GROUPS], W[ESVIT_MAX_GRID_GROUPS], Hd[ESVIT_MAX_GRID_GROUPS], Wd[ESVIT_MAX_GRID_GROUPS];
+    int blk0[ESVIT_MAX_GRID_GROUPS + 1];  // blk0[G] = the grid; blk0[g > G] = INT_MAX
+};
+
+__device__ __forceinline__ int group_of(const GroupArgs& ga) {
+    const int b = blockIdx.x;
+    return (b >= ga.blk0[1]) + (b >= ga.blk0[2]) + (b >= ga.blk0[3]);
+}
+
+template <typename T>
+__global__ void pad_crop_grouped_kernel(const GroupArgs ga, int C) {
+    const int g = group_of(ga);
+    pad_crop_body<T>(reinterpret_cast<const T*>(ga.p0[g]), ga.nB[g], ga.H[g], ga.W[g], ga.Hd[g], ga.Wd[g], C, reinterpret_cast<T*>(ga.out[g]),
+                     blockIdx.x - ga.blk0[g], ga.blk0[g + 1] - ga.blk0[g]);
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void dwconv3x3_grouped_kernel(const GroupArgs ga, const float* __restrict__ w, int flip, int C) {
+    const int g = group_of(ga);
+    dwconv3x3_body<T>(reinterpret_cast<const T*>(ga.p0[g]), w, flip, ga.nB[g], ga.H[g], ga.W[g], C, reinterpret_cast<T*>(ga.out[g]),
+                      blockIdx.x - ga.blk0[g], ga.blk0[g + 1] - ga.blk0[g]);
+}
+
+__global__ __launch_bounds__(256) void dwconv3x3_strip_grouped_kernel(const GroupArgs ga, const float* __restrict__ w, int flip, int C) {
+    const int g = group_of(ga);
+    dwconv3x3_strip_body(reinterpret_cast<const bf16*>(ga.p0[g]), w, flip, ga.nB[g], ga.H[g], ga.W[g], C, reinterpret_cast<bf16*>(ga.out[g]),
+                         blockIdx.x - ga.blk0[g], ga.blk0[g + 1] - ga.blk0[g]);
+}
+
+// group g's partials: ws[(blk0[g] + local block)][2C] -- the groups' partial tables one after the other
+template <typename T>
+__global__ __launch_bounds__(256) void col_sums2_grouped_kernel(const GroupArgs ga, int C, float* __restrict__ ws) {
+    const int g = group_of(ga);
+    col_sums2_body<T>(reinterpret_cast<const T*>(ga.p0[g]), reinterpret_cast<const T*>(ga.p1[g]), ga.rows[g], C, ws + (long)ga.blk0[g] * 2 * C,
+                      blockIdx.x - ga.blk0[g], ga.blk0[g + 1] - ga.blk0[g]);
+}
+
+// Stage 2 of the grouped sums: blockIdx.y = group.  The arithmetic of esvit_partial_reduce (elementwise.hip: partial_reduce_kernel<32> from
+// 256 partial rows on, <8> below) restated with the slice count as a value, so that every group gets the bits of its own plain call: four
+// strided partial sums per slice combined as (s0 + s1) + (s2 + s3), then the slices in order.
+__global__ __launch_bounds__(1024) void col_sums2_finish_grouped_kernel(const float* __restrict__ ws, const GroupArgs ga, int ncols,
+                                                                         float* __restrict__ out) {
+    __shared__ float sm[32][33];
+    const int g = blockIdx.y;
+    const int nblk = ga.blk0[g + 1] - ga.blk0[g];
+    const int SL = nblk >= 256 ? 32 : 8;
+    const float* w = ws + (long)ga.blk0[g] * ncols;
+    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
+    const int c = blockIdx.x * 32 + tx;
+    float s = 0.f;
+    if (c < ncols && ty < SL) {
+        float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
+        int b = ty;
+        for (; b + 3 * SL < nblk; b += 4 * SL) {
+            s0 += w[(long)b * ncols + c];
+            s1 += w[(long)(b + SL) * ncols + c];
+            s2 += w[(long)(b + 2 * SL) * ncols + c];
+            s3 += w[(long)(b + 3 * SL) * ncols + c];
+        }
+        for (; b < nblk; b += SL) s0 += w[(long)b * ncols + c];
+        s = (s0 + s1) + (s2 + s3);
+    }
+    sm[ty][tx] = s;
+    __syncthreads();
+    if (ty == 0 && c < ncols) {
+        float t = 0.f;
+        for (int k = 0; k < SL; ++k) t += sm[k][tx];
+        out[(long)g * ncols + c] = t;
+    }
+}
+
+template <typename T, int ACT>
+__global__ void col_affine2_grouped_kernel(const GroupArgs ga, int C) {
+    const int g = group_of(ga);
+    col_affine2_body<T, ACT>(reinterpret_cast<const T*>(ga.p0[g]), reinterpret_cast<const T*>(ga.p1[g]), ga.rows[g] * C, C, ga.a1[g], ga.a2[g], ga.a3[g],
+                             reinterpret_cast<T*>(ga.out[g]), blockIdx.x - ga.blk0[g], ga.blk0[g + 1] - ga.blk0[g]);
 }
 
 inline int grid_for(long n, int threads = 256, int cap = 8192) {
@@ -526,6 +647,142 @@ inline int reduce_blocks(long rows) {
 // load4c / store4c move four channels at once: 8 bytes of bf16, 16 of fp32
 inline int chan_align(int dtype) { return dtype == ESVIT_BF16 ? 8 : 16; }
 inline bool chan_aligned(int dtype, const void* p) { return (uintptr_t)p % chan_align(dtype) == 0; }
+
+// ---- grouped mode, host side.  `what`: the entry's name for the messages.  Checks the record array and what all records share; the geometry
+// and pointer checks of each entry follow in the entry (the plain call's own conditions, per record).
+#define ESVIT_GROUP_PROLOGUE(what, recs_, negcount, dtype, C)                                                                            \
+    const esvit_grid_group* recs = reinterpret_cast<const esvit_grid_group*>(recs_);                                                    \
+    const long G = -(long)(negcount);                                                                                                    \
+    ESVIT_CHECK_ARG(G >= 1 && G <= ESVIT_MAX_GRID_GROUPS, what ": grouped mode takes 1..%d groups, not %ld", ESVIT_MAX_GRID_GROUPS, G);  \
+    ESVIT_CHECK_ARG(recs != nullptr, what ": grouped mode without a record array");                                                     \
+    ESVIT_CHECK_ARG(dtype == ESVIT_BF16 || dtype == ESVIT_F32, what ": bad dtype");                                                      \
+    for (int g = 0; g < (int)G; ++g) {                                                                                                   \
+        ESVIT_CHECK_ARG(recs[g].C == C, what ": group %d has C=%d, the call C=%d (one width per grouped launch)", g, recs[g].C, C);      \
+        ESVIT_CHECK_ARG(recs[g].dtype == dtype, what ": group %d has dtype %d, the call %d (one dtype per grouped launch)", g,           \
+                        recs[g].dtype, dtype);                                                                                           \
+        ESVIT_CHECK_ARG(recs[g].nB > 0 && recs[g].H > 0 && recs[g].W > 0, what ": group %d: bad grid (nB=%d H=%d W=%d)", g, recs[g].nB, \
+                        recs[g].H, recs[g].W);                                                                                           \
+    }
+
+static void group_fill(GroupArgs& ga, const esvit_grid_group* recs, int G, const int* nblk) {
+    int at = 0;
+    for (int g = 0; g < ESVIT_MAX_GRID_GROUPS; ++g) {
+        const esvit_grid_group& r = recs[g < G ? g : 0];  // (unused slots repeat group 0: never selected, never a wild pointer)
+        ga.p0[g] = r.p0, ga.p1[g] = r.p1, ga.out[g] = r.out, ga.a1[g] = r.a1, ga.a2[g] = r.a2, ga.a3[g] = r.a3;
+        ga.nB[g] = r.nB, ga.H[g] = r.H, ga.W[g] = r.W, ga.Hd[g] = r.Hd, ga.Wd[g] = r.Wd;
+        ga.rows[g] = (long)r.nB * r.H * r.W;
+        ga.blk0[g] = g < G ? at : 0x7fffffff;
+        if (g < G) at += nblk[g];
+    }
+    ga.blk0[G] = at;
+    for (int g = G + 1; g <= ESVIT_MAX_GRID_GROUPS; ++g) ga.blk0[g] = 0x7fffffff;
+}
+
+static int dwconv3x3_grouped(int dtype, const void* recs_, const float* w, int flip, int negG, int C, hipStream_t stream) {
+    ESVIT_GROUP_PROLOGUE("esvit_dwconv3x3", recs_, negG, dtype, C);
+    ESVIT_CHECK_ARG(w && C > 0 && C % 4 == 0, "esvit_dwconv3x3: bad args (C=%d)", C);
+    const bool strip_c = dtype == ESVIT_BF16 && C % 8 == 0 && C / 8 <= 256 && ((uintptr_t)w % 16 == 0);
+    int nstrip = 0;
+    for (int g = 0; g < (int)G; ++g) {
+        ESVIT_CHECK_ARG(recs[g].p0 && recs[g].out, "esvit_dwconv3x3: group %d: null x / y", g);
+        nstrip += strip_c && ((uintptr_t)recs[g].p0 % 16 == 0) && ((uintptr_t)recs[g].out % 16 == 0);
+    }
+    ESVIT_CHECK_ARG(nstrip == 0 || nstrip == (int)G, "esvit_dwconv3x3: %d of %ld groups are 16-byte aligned: a grouped launch runs one kernel", nstrip, G);
+    const bool strip = nstrip > 0;
+    ESVIT_CHECK_ARG(strip || C / 4 <= 256, "esvit_dwconv3x3: C=%d too wide", C);
+    for (int g = 0; g < (int)G; ++g)
+        ESVIT_CHECK_ARG(strip || (chan_aligned(dtype, recs[g].p0) && chan_aligned(dtype, recs[g].out)),
+                        "esvit_dwconv3x3: group %d: x, y must be aligned to four channels (%d bytes)", g, chan_align(dtype));
+    GroupArgs ga;
+    int nblk[ESVIT_MAX_GRID_GROUPS];
+    if (strip) {
+        const int cvn = C / 8;
+        const dim3 blk(cvn, 256 / cvn > 0 ? 256 / cvn : 1);
+        for (int g = 0; g < (int)G; ++g)
+            nblk[g] = grid_for((long)recs[g].nB * recs[g].H * ((recs[g].W + DW_SW - 1) / DW_SW), (int)blk.y, 2048);
+        group_fill(ga, recs, (int)G, nblk);
+        hipLaunchKernelGGL(dwconv3x3_strip_grouped_kernel, dim3(ga.blk0[G]), blk, 0, stream, ga, w, flip, C);
+        ESVIT_CHECK_LAUNCH("dwconv3x3(strip, grouped)");
+        return ESVIT_OK;
+    }
+    const dim3 block = chan_block(C);
+    for (int g = 0; g < (int)G; ++g) nblk[g] = grid_for((long)recs[g].nB * recs[g].H * recs[g].W, (int)block.y, 4096);
+    group_fill(ga, recs, (int)G, nblk);
+    if (dtype == ESVIT_BF16) hipLaunchKernelGGL(dwconv3x3_grouped_kernel<bf16>, dim3(ga.blk0[G]), block, 0, stream, ga, w, flip, C);
+    else hipLaunchKernelGGL(dwconv3x3_grouped_kernel<float>, dim3(ga.blk0[G]), block, 0, stream, ga, w, flip, C);
+    ESVIT_CHECK_LAUNCH("dwconv3x3(grouped)");
+    return ESVIT_OK;
+}
+
+static int col_sums2_grouped(int dtype, const void* recs_, long negG, int C, float* out, float* ws, hipStream_t stream) {
+    ESVIT_GROUP_PROLOGUE("esvit_col_sums2", recs_, negG, dtype, C);
+    ESVIT_CHECK_ARG(out && ws && C > 0 && C % 4 == 0, "esvit_col_sums2: bad args (C=%d)", C);
+    ESVIT_CHECK_ARG(C / 4 <= 256, "esvit_col_sums2: grouped mode takes C <= 1024, not %d", C);
+    ESVIT_CHECK_ARG((uintptr_t)ws % 16 == 0, "esvit_col_sums2: ws must be aligned to 16 bytes");
+    GroupArgs ga;
+    int nblk[ESVIT_MAX_GRID_GROUPS];
+    for (int g = 0; g < (int)G; ++g) {
+        ESVIT_CHECK_ARG(recs[g].p0 && recs[g].p1, "esvit_col_sums2: group %d: null a / b", g);
+        ESVIT_CHECK_ARG(chan_aligned(dtype, recs[g].p0) && chan_aligned(dtype, recs[g].p1),
+                        "esvit_col_sums2: group %d: a, b must be aligned to four channels (%d bytes)", g, chan_align(dtype));
+        nblk[g] = reduce_blocks((long)recs[g].nB * recs[g].H * recs[g].W);
+    }
+    group_fill(ga, recs, (int)G, nblk);
+    const dim3 block = chan_block(C);
+    const size_t lds = (size_t)block.x * block.y * 2 * sizeof(f32x4);
+    if (dtype == ESVIT_BF16) hipLaunchKernelGGL(col_sums2_grouped_kernel<bf16>, dim3(ga.blk0[G]), block, lds, stream, ga, C, ws);
+    else hipLaunchKernelGGL(col_sums2_grouped_kernel<float>, dim3(ga.blk0[G]), block, lds, stream, ga, C, ws);
+    ESVIT_CHECK_LAUNCH("col_sums2(grouped)");
+    hipLaunchKernelGGL(col_sums2_finish_grouped_kernel, dim3(ceil_div(2 * C, 32), (unsigned)G), dim3(1024), 0, stream, ws, ga, 2 * C, out);
+    ESVIT_CHECK_LAUNCH("col_sums2(grouped finish)");
+    return ESVIT_OK;
+}
+
+template <typename T>
+static void launch_col_affine2_grouped(int act, const GroupArgs& ga, int grid, int C, hipStream_t stream) {
+    if (act == 1) hipLaunchKernelGGL((col_affine2_grouped_kernel<T, 1>), dim3(grid), dim3(256), 0, stream, ga, C);
+    else if (act == 2) hipLaunchKernelGGL((col_affine2_grouped_kernel<T, 2>), dim3(grid), dim3(256), 0, stream, ga, C);
+    else if (act == 3) hipLaunchKernelGGL((col_affine2_grouped_kernel<T, 3>), dim3(grid), dim3(256), 0, stream, ga, C);
+    else if (act == 4) hipLaunchKernelGGL((col_affine2_grouped_kernel<T, 4>), dim3(grid), dim3(256), 0, stream, ga, C);
+    else hipLaunchKernelGGL((col_affine2_grouped_kernel<T, 0>), dim3(grid), dim3(256), 0, stream, ga, C);
+}
+
+static int col_affine2_grouped(int dtype, const void* recs_, long negG, int C, int act, hipStream_t stream) {
+    ESVIT_GROUP_PROLOGUE("esvit_col_affine2", recs_, negG, dtype, C);
+    ESVIT_CHECK_ARG(C > 0 && act >= 0 && act <= 4, "esvit_col_affine2: bad args");
+    GroupArgs ga;
+    int nblk[ESVIT_MAX_GRID_GROUPS];
+    for (int g = 0; g < (int)G; ++g) {
+        const esvit_grid_group& r = recs[g];
+        ESVIT_CHECK_ARG(r.p0 && r.a1 && r.a3 && r.out, "esvit_col_affine2: group %d: null x1 / a1 / a3 / y", g);
+        ESVIT_CHECK_ARG(act == 0 ? (!r.p1 || r.a2) : ((act == 1 || act == 3) ? !r.p1 : r.p1 != nullptr),
+                        "esvit_col_affine2: group %d: x2 / a2 do not fit act=%d", g, act);
+        nblk[g] = grid_for((long)r.nB * r.H * r.W * C);
+    }
+    group_fill(ga, recs, (int)G, nblk);
+    if (dtype == ESVIT_BF16) launch_col_affine2_grouped<bf16>(act, ga, ga.blk0[G], C, stream);
+    else launch_col_affine2_grouped<float>(act, ga, ga.blk0[G], C, stream);
+    ESVIT_CHECK_LAUNCH("col_affine2(grouped)");
+    return ESVIT_OK;
+}
+
+static int pad_crop_grouped(int dtype, const void* recs_, int negG, int C, hipStream_t stream) {
+    ESVIT_GROUP_PROLOGUE("esvit_pad_crop_tokens", recs_, negG, dtype, C);
+    ESVIT_CHECK_ARG(C > 0 && C % (dtype == ESVIT_BF16 ? 8 : 4) == 0, "esvit_pad_crop_tokens: C=%d must be a multiple of the 16-byte vector", C);
+    GroupArgs ga;
+    int nblk[ESVIT_MAX_GRID_GROUPS];
+    for (int g = 0; g < (int)G; ++g) {
+        const esvit_grid_group& r = recs[g];
+        ESVIT_CHECK_ARG(r.p0 && r.out && r.Hd > 0 && r.Wd > 0, "esvit_pad_crop_tokens: group %d: bad args", g);
+        ESVIT_CHECK_ARG((uintptr_t)r.p0 % 16 == 0 && (uintptr_t)r.out % 16 == 0, "esvit_pad_crop_tokens: group %d: src, dst must be aligned to 16 bytes", g);
+        nblk[g] = grid_for((long)r.nB * r.Hd * r.Wd * (C / (dtype == ESVIT_BF16 ? 8 : 4)));
+    }
+    group_fill(ga, recs, (int)G, nblk);
+    if (dtype == ESVIT_BF16) hipLaunchKernelGGL(pad_crop_grouped_kernel<bf16>, dim3(ga.blk0[G]), dim3(256), 0, stream, ga, C);
+    else hipLaunchKernelGGL(pad_crop_grouped_kernel<float>, dim3(ga.blk0[G]), dim3(256), 0, stream, ga, C);
+    ESVIT_CHECK_LAUNCH("pad_crop_tokens(grouped)");
+    return ESVIT_OK;
+}
 
 }  // namespace
 
@@ -584,6 +841,7 @@ extern "C" int esvit_conv_col2im(int dtype, const void* dcols, int nB, int H, in
 
 extern "C" int esvit_dwconv3x3(int dtype, const void* x, const float* w, int flip, int nB, int H, int W, int C, void* y, esvit_stream_t s_) {
     STREAM(s_);
+    if (nB < 0) return dwconv3x3_grouped(dtype, x, w, flip, nB, C, stream);
     ESVIT_CHECK_ARG(x && w && y && nB > 0 && H > 0 && W > 0 && C > 0 && C % 4 == 0, "esvit_dwconv3x3: bad args (C=%d)", C);
     ESVIT_CHECK_ARG(dtype == ESVIT_BF16 || dtype == ESVIT_F32, "esvit_dwconv3x3: bad dtype");
     const bool strip = dtype == ESVIT_BF16 && C % 8 == 0 && C / 8 <= 256 && ((uintptr_t)x % 16 == 0) && ((uintptr_t)y % 16 == 0) && ((uintptr_t)w % 16 == 0);
@@ -649,6 +907,7 @@ extern "C" int esvit_dwconv3x3_wgrad(int dtype, const void* x, const void* dy, i
 
 extern "C" int esvit_col_sums2(int dtype, const void* a, const void* b, int64_t rows, int C, float* out, float* ws, esvit_stream_t s_) {
     STREAM(s_);
+    if (rows < 0) return col_sums2_grouped(dtype, a, (long)rows, C, out, ws, stream);
     ESVIT_CHECK_ARG(a && b && out && ws && rows > 0 && C > 0, "esvit_col_sums2: bad args");
     ESVIT_CHECK_ARG(dtype == ESVIT_BF16 || dtype == ESVIT_F32, "esvit_col_sums2: bad dtype");
     ESVIT_CHECK_ARG(C % 4 == 0, "esvit_col_sums2: bad C=%d", C);
@@ -694,6 +953,7 @@ static void launch_col_affine2(int act, const void* x1, const void* x2, long n, 
 extern "C" int esvit_col_affine2(int dtype, const void* x1, const void* x2, int64_t rows, int C, const float* a1, const float* a2,
                                  const float* a3, int act, void* y, esvit_stream_t s_) {
     STREAM(s_);
+    if (rows < 0) return col_affine2_grouped(dtype, x1, (long)rows, C, act, stream);
     ESVIT_CHECK_ARG(x1 && a1 && a3 && y && rows > 0 && C > 0 && act >= 0 && act <= 4, "esvit_col_affine2: bad args");
     ESVIT_CHECK_ARG(act == 0 ? (!x2 || a2) : ((act == 1 || act == 3) ? !x2 : x2 != nullptr), "esvit_col_affine2: x2 / a2 do not fit act=%d", act);
     ESVIT_CHECK_ARG(dtype == ESVIT_BF16 || dtype == ESVIT_F32, "esvit_col_affine2: bad dtype");
@@ -741,6 +1001,7 @@ extern "C" int esvit_bn_bwd_coeffs(const float* red, float n, const float* gamma
 
 extern "C" int esvit_pad_crop_tokens(int dtype, const void* src, int nB, int Hs, int Ws, int Hd, int Wd, int C, void* dst, esvit_stream_t s_) {
     STREAM(s_);
+    if (nB < 0) return pad_crop_grouped(dtype, src, nB, C, stream);
     ESVIT_CHECK_ARG(src && dst && nB > 0 && Hs > 0 && Ws > 0 && Hd > 0 && Wd > 0 && C > 0, "esvit_pad_crop_tokens: bad args");
     ESVIT_CHECK_ARG(dtype == ESVIT_BF16 || dtype == ESVIT_F32, "esvit_pad_crop_tokens: bad dtype");
     ESVIT_CHECK_ARG(C % (dtype == ESVIT_BF16 ? 8 : 4) == 0, "esvit_pad_crop_tokens: C=%d must be a multiple of the 16-byte vector", C);

@@ -11,6 +11,7 @@ Stages (reference lines):
   TokenMeanFn      swin_transformer.py:688-689
   DinoHeadFn       vision_transformer.py:414-418
   ConvEmbedFn, CvtAttnFn, CvtFfnFn   cvt_v4_transformer.py:349-382, 108-220 (+75-105), 62-72  (BASELINE config 5)
+  ConvEmbedMultiFn, CvtAttnMultiFn, CvtFfnMultiFn   the same over the token rows of several resolution groups (cvt_v4_transformer.py:625-628)
 """
 import os
 
@@ -1388,6 +1389,324 @@ class CvtFfnFn(torch.autograd.Function):
         gx, dg2, db2 = o.layernorm_bwd(dh, x.view(M, C), mean, rstd, g2, g_in=gy)
         _side_join()
         return gx.view(nB, L, C), None, dg2, db2, dW1.view(Hd, C, 1, 1), dbf1, dW2.view(C, Hd, 1, 1), dbf2
+
+
+# ---- ragged multi-crop CvT: every resolution group of a step through ONE set of LayerNorm / GEMM launches -----------------------------
+# LayerNorm, the 1x1 convolutions (GEMMs) and the residual adds are row-wise, so the token rows of all groups run through them together
+# and every parameter receives ONE gradient contribution, written into its bucket slot.  What depends on the grid runs per group: the
+# zero-pad / crop around the windows, the depthwise 3x3, the window attention -- and BatchNorm, which keeps the reference's semantics: the
+# reference calls the backbone once per group (cvt_v4_transformer.py:625-628), so each group is normalised with ITS OWN batch statistics
+# and the running statistics take one momentum update per group, IN GROUP ORDER.  The pad / crop, depthwise and BatchNorm kernels of all
+# groups are one launch each where the ops module has the grouped entries (include/esvit_hip.h, "GROUPED MODE"); an ops module without
+# them (the CPU restatement) runs the plain calls group by group.
+CVT_MAX_GROUPS = 4  # ESVIT_MAX_GRID_GROUPS
+
+
+def _g_pad_crop(o, srcs, geos, outs):
+    """pad_crop_tokens per group (geos: (nB, Hs, Ws, Hd, Wd)) into `outs`"""
+    if not srcs:
+        return
+    if hasattr(o, "pad_crop_tokens_grouped"):
+        o.pad_crop_tokens_grouped(srcs, geos, outs=outs)
+        return
+    for s, g, d in zip(srcs, geos, outs):
+        d.copy_(o.pad_crop_tokens(s, *g))
+
+
+def _g_dwconv(o, xs, w9, geos, flip, outs):
+    if hasattr(o, "dwconv3x3_grouped"):
+        o.dwconv3x3_grouped(xs, w9, geos, flip=flip, outs=outs)
+        return
+    for x, (nB, H, W), d in zip(xs, geos, outs):
+        d.copy_(o.dwconv3x3(x, w9, nB, H, W, flip=flip))
+
+
+def _g_col_sums2(o, a_list, b_list):
+    """-> fp32 [G, 2, C], row g with the bits of col_sums2(a_list[g], b_list[g])"""
+    if hasattr(o, "col_sums2_grouped"):
+        return o.col_sums2_grouped(a_list, b_list)
+    return torch.stack([o.col_sums2(a, b) for a, b in zip(a_list, b_list)], 0)
+
+
+def _g_col_affine2(o, x1s, a1s, a3s, x2s, a2s, outs):
+    if hasattr(o, "col_affine2_grouped"):
+        o.col_affine2_grouped(x1s, a1s, a3s, x2s, a2s, outs=outs)
+        return
+    for i, (x1, d) in enumerate(zip(x1s, outs)):
+        d.copy_(o.col_affine2(x1, a1s[i], a3s[i], None if x2s is None else x2s[i], None if a2s is None else a2s[i]))
+
+
+def _cvt_group_geometry(segs, window, has_table, shift):
+    """segs: (row0, nB, H, W) -> per group (row0, row1, pad0, pad1, nB, H, W, Hp, Wp, w); the refusals of CvtAttnFn.forward, per group"""
+    out, p0 = [], 0
+    for (r0, nB, H, W) in segs:
+        w = min(window, H, W)
+        if (has_table or shift) and w != window:
+            raise RuntimeError("CvT relative-position bias / shift mask on a %dx%d map: smaller than the %dx%d window" % (H, W, window, window))
+        if shift and (H % w or W % w):
+            raise RuntimeError("CvT shift mask on a %dx%d map: not a multiple of the %dx%d window" % (H, W, window, window))
+        Hp, Wp = -(-H // w) * w, -(-W // w) * w
+        out.append((r0, r0 + nB * H * W, p0, p0 + nB * Hp * Wp, nB, H, W, Hp, Wp, w))
+        p0 += nB * Hp * Wp
+    return out
+
+
+class CvtAttnMultiFn(torch.autograd.Function):
+    """CvtAttnFn over the token rows of several resolution groups.  X fp32 [M, C] (group after group), segs: tuple of (row0, nB, H, W),
+    dp_rows: None or the per-row DropPath scale [M].  A group whose grid needs no padding is never copied: its depthwise convolution reads
+    the LayerNorm output in place and its attention writes into the rows of the projection's operand."""
+
+    @staticmethod
+    def forward(ctx, X, segs, nH, window, dp_rows, bn_state, g1, b1, dw_w, bn_g, bn_b, pw_Wp, pw_b, proj_Wp, proj_b, table_p=None, index=None,
+                shift=False):
+        o = ops_module()
+        X = X.contiguous()
+        M, C = X.shape
+        geo = _cvt_group_geometry(segs, window, table_p is not None, shift)
+        G, Mp, dev = len(geo), geo[-1][3], X.device
+        xn, _, mean1, rstd1 = o.layernorm_fwd(X, g1, b1, CVT_LN_EPS)
+        dt = xn.dtype
+        padded = [i for i, q in enumerate(geo) if (q[7], q[8]) != (q[5], q[6])]
+        xps = [xn[q[0]:q[1]] for q in geo]
+        for i in padded:
+            xps[i] = torch.empty((geo[i][3] - geo[i][2], C), dtype=dt, device=dev)
+        _g_pad_crop(o, [xn[geo[i][0]:geo[i][1]] for i in padded], [(geo[i][4], geo[i][5], geo[i][6], geo[i][7], geo[i][8]) for i in padded],
+                    [xps[i] for i in padded])
+        dw9 = dw_w.detach().reshape(C, 9).contiguous()
+        d = torch.empty((Mp, C), dtype=dt, device=dev)
+        ds = [d[q[2]:q[3]] for q in geo]
+        pgeo = [(q[4], q[7], q[8]) for q in geo]
+        _g_dwconv(o, xps, dw9, pgeo, False, ds)
+        eval_bn = bool(bn_state.get("eval"))
+        gam, bet = bn_g.detach().contiguous(), bn_b.detach().contiguous()
+        if eval_bn:  # the running statistics for every group: one coefficient vector
+            ns = [float(q[3] - q[2]) for q in geo]
+            coefs = [o.bn_eval_coeffs(bn_state["eval_mean"], bn_state["eval_var"], gam, bet, BN_EPS)] * G
+        else:        # every group with its own batch statistics; ONE all-reduce of the stacked sums; running statistics in group order
+            sums = _g_col_sums2(o, ds, ds)
+            world = _allreduce_stats(sums, bn_state.get("group"))
+            ns = [float((q[3] - q[2]) * world) for q in geo]
+            coefs = [o.bn_fwd_coeffs(sums[i], ns[i], gam, bet, BN_EPS, BN_MOMENTUM, bn_state.get("running_mean"), bn_state.get("running_var"))
+                     for i in range(G)]
+            if bn_state.get("num_batches_tracked") is not None:
+                bn_state["num_batches_tracked"].add_(G)
+        bnout = torch.empty_like(d)
+        _g_col_affine2(o, ds, [c[0] for c in coefs], [c[1] for c in coefs], None, None, [bnout[q[2]:q[3]] for q in geo])
+        Wpw, Wproj = _weight(pw_Wp, (3 * C, C)), _weight(proj_Wp, (C, C))
+        qkv = o.linear_fwd(bnout, Wpw, pw_b)
+        scale = float(C) ** -0.5
+        aoc = torch.empty((M, C), dtype=qkv.dtype, device=dev)
+        aos, lses, tables = [], [], []
+        for i, (r0, r1, p0, p1, nB, H, W, Hp, Wp, w) in enumerate(geo):
+            geom = geometry(Hp, Wp, w, 0, dev)
+            table = _zero_table(w, nH, dev) if table_p is None else table_p.detach()
+            regions = geometry(Hp, Wp, w, w // 2, dev).region_ids if shift else None
+            ao, lse = o.window_attn_fwd(qkv[p0:p1], pw_b, geom.win2tok, Hp * Wp, table, w, regions, geom.nW, geom.N, nH, scale,
+                                        out=None if i in padded else aoc[r0:r1])
+            aos.append(ao)
+            lses.append(lse)
+            tables.append(table)
+        _g_pad_crop(o, [aos[i] for i in padded], [(geo[i][4], geo[i][7], geo[i][8], geo[i][5], geo[i][6]) for i in padded],
+                    [aoc[geo[i][0]:geo[i][1]] for i in padded])
+        x1 = o.linear_fwd(aoc, Wproj, proj_b, residual=X, rowscale=dp_rows, rows_per_sample=1, out_f32=True)
+        ctx.geo, ctx.padded, ctx.meta = geo, padded, (nH, scale, dp_rows, bn_state.get("group"), eval_bn, table_p is not None, shift)
+        ctx.ns, ctx.has_lse = ns, [l is not None for l in lses]
+        ctx.params = (g1, b1, pw_Wp, pw_b, proj_Wp, proj_b, table_p)
+        ucoefs = coefs[:1] if eval_bn else coefs
+        ctx.ncoef = len(ucoefs)
+        ctx.save_for_backward(X, mean1, rstd1, g1, dw9, d, gam, bnout, Wpw, pw_b, qkv, aoc, Wproj, index, *xps, *aos, *tables, *ucoefs,
+                              *[l for l in lses if l is not None])
+        return x1
+
+    @staticmethod
+    def backward(ctx, gy):
+        o = ops_module()
+        t = ctx.saved_tensors
+        X, mean1, rstd1, g1, dw9, d, gam, bnout, Wpw, pw_b, qkv, aoc, Wproj, index = t[:14]
+        geo, padded = ctx.geo, ctx.padded
+        G = len(geo)
+        xps, aos, tables = t[14:14 + G], t[14 + G:14 + 2 * G], t[14 + 2 * G:14 + 3 * G]
+        coefs = list(t[14 + 3 * G:14 + 3 * G + ctx.ncoef])
+        rest = list(t[14 + 3 * G + ctx.ncoef:])
+        lses = [rest.pop(0) if h else None for h in ctx.has_lse]
+        nH, scale, dp_rows, group, eval_bn, has_table, shift = ctx.meta
+        if eval_bn:
+            coefs = coefs * G
+        g1_p, b1_p, pw_Wp, pw_b_p, proj_Wp, proj_b_p, table_p = ctx.params
+        M, C = X.shape
+        Mp, dev = geo[-1][3], X.device
+        gy = gy.contiguous()
+        dyb = o.gather_cast(gy, M, rowscale=dp_rows, rows_per_sample=1)
+        dWproj, dbproj = _side_run(lambda: _wgrad(dyb, aoc, proj_Wp, (C, C), want_bias=True, bias_param=proj_b_p), dyb, aoc)
+        daoc = o.linear_dgrad(dyb, Wproj)
+        daos = [daoc[q[0]:q[1]] for q in geo]
+        for i in padded:
+            daos[i] = torch.empty((geo[i][3] - geo[i][2], C), dtype=daoc.dtype, device=dev)
+        _g_pad_crop(o, [daoc[geo[i][0]:geo[i][1]] for i in padded], [(geo[i][4], geo[i][5], geo[i][6], geo[i][7], geo[i][8]) for i in padded],
+                    [daos[i] for i in padded])
+        dqkv = torch.empty_like(qkv)
+        dtable, tsink = None, P.grad_out(table_p) if has_table else None
+        for i, (r0, r1, p0, p1, nB, H, W, Hp, Wp, w) in enumerate(geo):
+            geom = geometry(Hp, Wp, w, 0, dev)
+            regions = geometry(Hp, Wp, w, w // 2, dev).region_ids if shift else None
+            _, dbias_ws, _ = o.window_attn_bwd(qkv[p0:p1], pw_b, geom.win2tok, Hp * Wp, daos[i], aos[i], lses[i], tables[i], w, regions, geom.nW, geom.N,
+                                               nH, scale, dqkv_out=dqkv[p0:p1], **({} if has_table else _no_dbias(o, geom.N, C // nH)))
+            if has_table:  # the first group writes the table gradient (its bucket slot when there is one), later groups add to it
+                if i == 0:
+                    dtable = o.relpos_bias_bwd(dbias_ws, index, geom.N, tables[i].shape[0], out=tsink, accumulate=False if tsink is not None else None)
+                else:
+                    o.relpos_bias_bwd(dbias_ws, index, geom.N, tables[i].shape[0], out=dtable, accumulate=True)
+        if has_table:
+            dtable = _alias(dtable, tsink)
+        dWpw, dbpw = _side_run(lambda: _wgrad(dqkv, bnout, pw_Wp, (3 * C, C), want_bias=True, bias_param=pw_b_p), dqkv, bnout)
+        dbn = o.linear_dgrad(dqkv, Wpw)
+        # BatchNorm backward per group (CvtAttnFn.backward); d gamma / d beta: the sum of the groups' local reductions
+        ds, dbns = [d[q[2]:q[3]] for q in geo], [dbn[q[2]:q[3]] for q in geo]
+        sums = _g_col_sums2(o, dbns, ds)
+        red = torch.stack([o.bn_bwd_local(sums[i], coefs[i]) for i in range(G)], 0)  # [G, 2, C]
+        dgb = red.sum(0)
+        if eval_bn:
+            abcs = [o.bn_bwd_coeffs(None, ctx.ns[i], gam, coefs[i]) for i in range(G)]
+        else:
+            _allreduce_stats(red, group)  # ONE all-reduce for all groups
+            abcs = [o.bn_bwd_coeffs(red[i], ctx.ns[i], gam, coefs[i]) for i in range(G)]
+        dd = torch.empty_like(d)
+        dds = [dd[q[2]:q[3]] for q in geo]
+        _g_col_affine2(o, dbns, [a[0] for a in abcs], [a[2] for a in abcs], ds, [a[1] for a in abcs], dds)
+        pgeo = [(q[4], q[7], q[8]) for q in geo]
+
+        def dw_wgrad():
+            acc = o.dwconv3x3_wgrad(xps[0], dds[0], *pgeo[0])
+            for i in range(1, G):
+                acc = acc.add_(o.dwconv3x3_wgrad(xps[i], dds[i], *pgeo[i]))
+            return acc
+
+        ddw = _side_run(dw_wgrad, dd, *xps).view(C, 1, 3, 3)
+        dxn = torch.empty((M, C), dtype=dd.dtype, device=dev)
+        dxps = [dxn[q[0]:q[1]] for q in geo]
+        for i in padded:
+            dxps[i] = torch.empty((geo[i][3] - geo[i][2], C), dtype=dd.dtype, device=dev)
+        _g_dwconv(o, dds, dw9, pgeo, True, dxps)
+        _g_pad_crop(o, [dxps[i] for i in padded], [(geo[i][4], geo[i][7], geo[i][8], geo[i][5], geo[i][6]) for i in padded],
+                    [dxn[geo[i][0]:geo[i][1]] for i in padded])
+        ln1 = _ln_sinks(g1_p, b1_p)
+        gx, dg1, db1 = o.layernorm_bwd(dxn, X, mean1, rstd1, g1, g_in=gy, gb_out=ln1)
+        _side_join()
+        return (gx, None, None, None, None, None, _alias(dg1, ln1), _alias(db1, ln1), ddw, dgb[1], dgb[0], dWpw.view(3 * C, C, 1, 1), dbpw,
+                dWproj.view(C, C, 1, 1), dbproj, dtable, None, None)
+
+
+class CvtFfnMultiFn(torch.autograd.Function):
+    """CvtFfnFn over the token rows of all groups: X fp32 [M, C]; dp_rows: None or the per-row DropPath scale [M]"""
+
+    @staticmethod
+    def forward(ctx, X, dp_rows, g2, b2, W1p, bf1, W2p, bf2):
+        o = ops_module()
+        X = X.contiguous()
+        M, C = X.shape
+        Hd = W1p.shape[0]
+        W1, W2 = _weight(W1p, (Hd, C)), _weight(W2p, (C, Hd))
+        h, _, mean, rstd = o.layernorm_fwd(X, g2, b2, CVT_LN_EPS)
+        a1g, a1 = o.linear_fwd(h, W1, bf1, gelu=True, want_preact=True, quick=True)
+        y = o.linear_fwd(a1g, W2, bf2, residual=X, rowscale=dp_rows, rows_per_sample=1, out_f32=True)
+        ctx.dp_rows = dp_rows
+        ctx.params = (g2, b2, W1p, bf1, W2p, bf2)
+        ctx.save_for_backward(X, mean, rstd, g2, h, a1, a1g, W1, W2)
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        o = ops_module()
+        X, mean, rstd, g2, h, a1, a1g, W1, W2 = ctx.saved_tensors
+        g2_p, b2_p, W1p, bf1_p, W2p, bf2_p = ctx.params
+        M, C = X.shape
+        Hd = W1.shape[0]
+        gy = gy.contiguous()
+        dyb = o.gather_cast(gy, M, rowscale=ctx.dp_rows, rows_per_sample=1)
+        dW2, dbf2 = _side_run(lambda: _wgrad(dyb, a1g, W2p, (C, Hd), want_bias=True, bias_param=bf2_p), dyb, a1g)
+        da1 = o.linear_dgrad(dyb, W2, gelu_preact=a1, quick=True)
+        dW1, dbf1 = _side_run(lambda: _wgrad(da1, h, W1p, (Hd, C), want_bias=True, bias_param=bf1_p), da1, h)
+        dh = o.linear_dgrad(da1, W1)
+        ln2 = _ln_sinks(g2_p, b2_p)
+        gx, dg2, db2 = o.layernorm_bwd(dh, X, mean, rstd, g2, g_in=gy, gb_out=ln2)
+        _side_join()
+        return gx, None, _alias(dg2, ln2), _alias(db2, ln2), dW1.view(Hd, C, 1, 1), dbf1, dW2.view(C, Hd, 1, 1), dbf2
+
+
+def cvt_block_multi(X, segs, nH, window, dp_rows, bn_state, attn_prm, ffn_prm, table_p=None, index=None, shift=False):
+    """one CvT block (attention + feed-forward) over the token rows of several resolution groups; X fp32 [M, C].
+    attn_prm = (norm.w, norm.b, dw.w, bn.w, bn.b, pw.w, pw.b, proj.w, proj.b), ffn_prm = (norm.w, norm.b, fc1.w, fc1.b, fc2.w, fc2.b);
+    dp_rows: None or (attention branch [M], feed-forward branch [M])"""
+    dp1, dp2 = (None, None) if dp_rows is None else dp_rows
+    X = CvtAttnMultiFn.apply(X, segs, nH, window, dp1, bn_state, *attn_prm, table_p, index, shift)
+    return CvtFfnMultiFn.apply(X, dp2, *ffn_prm)
+
+
+class ConvEmbedMultiFn(torch.autograd.Function):
+    """ConvEmbed of several resolution groups: im2col per piece into ONE column matrix, one projection GEMM + LayerNorm over all rows (one
+    gradient contribution per parameter), col2im per group.  geo = (nchw, Cin, k, stride, pad, pieces), pieces: (nB, H, W) per piece.
+    nchw: srcs = the fp32 image batches, one per piece (read where they lie); else srcs = (X,) fp32 token rows [M, Cin], piece after piece.
+    -> fp32 token rows [sum nB Ho Wo, E]"""
+
+    @staticmethod
+    def forward(ctx, geo, Wp, bp, g, b, *srcs):
+        o = ops_module()
+        nchw, Cin, k, stride, pad, pieces = geo
+        outs = [(nB, o.conv_out_size(H, k, stride, pad), o.conv_out_size(W, k, stride, pad)) for (nB, H, W) in pieces]
+        rows = [nB * Ho * Wo for (nB, Ho, Wo) in outs]
+        Wk = _conv_weight_matrix(Wp)
+        cols = torch.empty((sum(rows), Wk.shape[1]), dtype=Wk.dtype, device=srcs[0].device)
+        if not nchw:
+            X = srcs[0].contiguous()
+            xa = o.gather_cast(X, X.shape[0])
+        r0 = q0 = 0
+        for i, (nB, H, W) in enumerate(pieces):
+            src = srcs[i].contiguous() if nchw else xa[q0:q0 + nB * H * W]
+            if getattr(o, "IM2COL_OUT", False):
+                o.conv_im2col(src, nchw, nB, H, W, Cin, k, stride, pad, out=cols[r0:r0 + rows[i]])
+            else:
+                cols[r0:r0 + rows[i]].copy_(o.conv_im2col(src, nchw, nB, H, W, Cin, k, stride, pad))
+            r0 += rows[i]
+            q0 += nB * H * W
+        y = o.linear_fwd(cols, Wk, bp, out_f32=True)
+        t, _, mean, rstd = o.layernorm_fwd(y, g, b, CVT_LN_EPS, dtype=torch.float32)
+        ctx.geo, ctx.rows, ctx.nsrc = geo, rows, len(srcs)
+        ctx.params = (Wp, bp, g, b)
+        ctx.save_for_backward(cols, Wk, y, mean, rstd, g)
+        return t
+
+    @staticmethod
+    def backward(ctx, gt):
+        o = ops_module()
+        cols, Wk, y, mean, rstd, g = ctx.saved_tensors
+        nchw, Cin, k, stride, pad, pieces = ctx.geo
+        Wp, bp_p, g_p, b_p = ctx.params
+        E = y.shape[1]
+        ln = _ln_sinks(g_p, b_p)
+        dy, dg, db = o.layernorm_bwd(gt.contiguous(), y, mean, rstd, g, gb_out=ln)
+        dyb = o.gather_cast(dy, dy.shape[0])
+        bsink = P.grad_out(bp_p)
+        dWk, dbp = _side_run(lambda: o.linear_wgrad(dyb, cols, want_bias=True, db_out=bsink), dyb, cols)
+        dX = None
+        if not nchw and ctx.needs_input_grad[5]:
+            dcols = o.linear_dgrad(dyb, Wk)
+            dX = torch.empty((sum(nB * H * W for (nB, H, W) in pieces), Cin), dtype=torch.float32, device=dcols.device)
+            r0 = q0 = 0
+            for i, (nB, H, W) in enumerate(pieces):
+                dst = dX[q0:q0 + nB * H * W]
+                if getattr(o, "IM2COL_OUT", False):
+                    o.conv_col2im(dcols[r0:r0 + ctx.rows[i]], nB, H, W, Cin, k, stride, pad, out=dst)
+                else:
+                    dst.copy_(o.conv_col2im(dcols[r0:r0 + ctx.rows[i]], nB, H, W, Cin, k, stride, pad))
+                r0 += ctx.rows[i]
+                q0 += nB * H * W
+        _side_join()
+        # the GEMM's column order is (ky, kx, c): the parameter's layout is one permuting copy away, written into its bucket slot if there is one
+        K = k * k * Cin
+        wsink = P.grad_out(Wp)
+        src = dWk[:, :K].reshape(E, k, k, Cin).permute(0, 3, 1, 2)
+        dWp = _alias(wsink.copy_(src), wsink) if wsink is not None else src.contiguous()
+        return (None, dWp, _alias(dbp, bsink), _alias(dg, ln), _alias(db, ln)) + ((dX,) if not nchw else (None,) * ctx.nsrc)
 
 
 # ------------------------------------------------------------------------------------------------

@@ -14,6 +14,7 @@ Conv 3x3 -> BatchNorm -> ReLU units instead of the first ConvEmbed).  Both need 
 one window wide, as in the reference (its bias / mask shapes do not fit a shrunken window).  Train mode uses batch statistics
 (synchronised over the ranks), eval mode the running statistics, as ``nn.BatchNorm2d`` / ``SyncBatchNorm`` do.
 """
+import os
 from functools import partial
 
 import numpy as np
@@ -135,6 +136,38 @@ class Transformer(nn.Module):
         return x
 
 
+    def forward_tokens_multi(self, X, segs):
+        """the ragged multi-crop route: X fp32 [M, C], the token rows of all resolution groups; segs: tuple of (row0, nB, H, W).  One
+        DropPath draw over the samples of all groups (the random stream differs from the per-group schedule's, as on the other ragged
+        routes), expanded to rows"""
+        f = self.drop_path_factors(sum(nB for (_, nB, _, _) in segs), X.device)
+        rows = None
+        if f is not None:
+            at, parts = 0, []
+            for (_, nB, H, W) in segs:
+                parts.append(f[:, :, at:at + nB].repeat_interleave(H * W, dim=2))
+                at += nB
+            rows = torch.cat(parts, dim=2).contiguous()  # [depth, 2, M]
+        for li, (attn, ff, drop_path) in enumerate(self.layers):
+            dp = None
+            if rows is not None and isinstance(drop_path, DropPath) and drop_path.drop_prob:
+                dp = (rows[li, 0], rows[li, 1])
+            a, bn = attn.fn, attn.fn.qkv.bn
+            bn_state = {"group": self.sync_bn_group}
+            if self.training:
+                if bn.track_running_stats:
+                    bn_state.update(running_mean=bn.running_mean, running_var=bn.running_var, num_batches_tracked=bn.num_batches_tracked)
+            else:
+                bn_state.update(eval=True, eval_mean=bn.running_mean, eval_var=bn.running_var)
+            rpe = (a.rel_pos_bias_table, a.rel_pos_idx) if a.rel_pos_embed else (None, None)
+            X = Fn.cvt_block_multi(X, segs, a.heads, a.window_size, dp, bn_state,
+                                   (attn.norm.weight, attn.norm.bias, a.qkv.dw.weight, bn.weight, bn.bias, a.qkv.pw.weight, a.qkv.pw.bias,
+                                    a.proj_out.weight, a.proj_out.bias),
+                                   (ff.norm.weight, ff.norm.bias, ff.fn.net[0].weight, ff.fn.net[0].bias, ff.fn.net[2].weight, ff.fn.net[2].bias),
+                                   rpe[0], rpe[1], bool(self.shift))
+        return X
+
+
 class ConvEmbed(nn.Module):
     def __init__(self, patch_size=7, in_chans=3, embed_dim=64, stride=4, padding=2, norm_layer=None):
         super().__init__()
@@ -149,6 +182,15 @@ class ConvEmbed(nn.Module):
         t = Fn.ConvEmbedFn.apply(src, geo, self.proj.weight, self.proj.bias, self.norm.weight, self.norm.bias)
         o = Fn.ops_module()
         return t, o.conv_out_size(H, self.patch_size, self.stride, self.padding), o.conv_out_size(W, self.patch_size, self.stride, self.padding)
+
+
+    def forward_tokens_multi(self, srcs, nchw, pieces):
+        """srcs: the image batches (nchw, one per piece) or (X,) token rows of all groups; pieces: (nB, H, W) each -> (rows [M', E], pieces')"""
+        o = Fn.ops_module()
+        geo = (nchw, self.in_chans, self.patch_size, self.stride, self.padding, tuple(pieces))
+        t = Fn.ConvEmbedMultiFn.apply(geo, self.proj.weight, self.proj.bias, self.norm.weight, self.norm.bias, *srcs)
+        size = lambda n: o.conv_out_size(n, self.patch_size, self.stride, self.padding)  # noqa: E731
+        return t, [(nB, size(H), size(W)) for (nB, H, W) in pieces]
 
 
 class ResStem(nn.Module):
@@ -207,6 +249,9 @@ class CvT(nn.Module):
         self.num_features = in_chans
         self.head = nn.Linear(in_chans, num_classes) if num_classes > 0 else nn.Identity()
         self.use_dense_prediction = use_dense_prediction
+        # True: the resolution groups of a training step go through the backbone as one row matrix (forward_feature_maps_multi); False: one
+        # pass per group, as the reference schedules it (cvt_v4_transformer.py:625-628) -- same result either way.  Opt-in (ESVIT_CVT_RAGGED=1)
+        self.ragged_multi_crop = os.environ.get("ESVIT_CVT_RAGGED", "0") == "1"
         if self.use_dense_prediction:
             self.head_dense = None
         self.apply(self._init_weights_trunc_normal)
@@ -230,6 +275,56 @@ class CvT(nn.Module):
             src, nchw = tr.forward_tokens(t, H, W), False
         x_region = Fn.FinalNormFn.apply(src, self.norm.weight, self.norm.bias, Fn.CVT_LN_EPS)
         return Fn.TokenMeanFn.apply(x_region), x_region
+
+    def forward_feature_maps_multi(self, crop_groups):
+        """several resolution groups (each a list of equally sized crop batches, in crop order) at once -> (list of (cls, region) per
+        group, all region rows [M, C] in group order).  The token rows of all groups travel as ONE [M, C] matrix: every ConvEmbed
+        projection, LayerNorm and 1x1 convolution is launched once over all of them; padding, the depthwise convolution, BatchNorm (each
+        group with its own batch statistics, running statistics updated in group order) and attention see the grids.  The residual stem
+        (RES_STEM) reads the images and has a BatchNorm of its own: it runs per group and feeds the ragged stage 0."""
+        conv0, tr0 = self.stage0
+        if isinstance(conv0, ResStem):
+            parts, pieces = [], []
+            for grp in crop_groups:
+                imgs = grp[0] if len(grp) == 1 else torch.cat(grp)
+                nB, _, H, W = imgs.shape
+                t, H, W = conv0.forward_tokens(imgs, True, nB, H, W)
+                parts.append(t.reshape(nB * H * W, -1))
+                pieces.append((nB, H, W))
+            X = torch.cat(parts)
+        else:  # every crop batch is a piece of the column matrix (read where it lies); the pieces of a group are consecutive rows
+            flat = [c for grp in crop_groups for c in grp]
+            X, out = conv0.forward_tokens_multi(flat, True, [(c.shape[0], c.shape[2], c.shape[3]) for c in flat])
+            pieces, at = [], 0
+            for grp in crop_groups:
+                pieces.append((sum(c.shape[0] for c in grp), out[at][1], out[at][2]))
+                at += len(grp)
+
+        def segs_of(pieces):
+            segs, r0 = [], 0
+            for (nB, H, W) in pieces:
+                segs.append((r0, nB, H, W))
+                r0 += nB * H * W
+            return tuple(segs)
+
+        X = tr0.forward_tokens_multi(X, segs_of(pieces))
+        for i in range(1, self.num_stages):
+            conv, tr = getattr(self, f'stage{i}')
+            X, pieces = conv.forward_tokens_multi((X,), False, pieces)
+            X = tr.forward_tokens_multi(X, segs_of(pieces))
+        C = X.shape[-1]
+        Xn = Fn.FinalNormFn.apply(X, self.norm.weight, self.norm.bias, Fn.CVT_LN_EPS)
+        parts = torch.split(Xn, [nB * H * W for (nB, H, W) in pieces]) if len(pieces) > 1 else (Xn,)
+        outs = []
+        for part, (nB, H, W) in zip(parts, pieces):
+            x_region = part.view(nB, H * W, C)
+            outs.append((Fn.TokenMeanFn.apply(x_region), x_region))
+        return outs, Xn
+
+    def _ragged(self, bounds):
+        """the ragged route is for training passes over more than one resolution group; a single group (the teacher's two global views,
+        evaluation) keeps the per-group path"""
+        return self.ragged_multi_crop and self.training and 1 < len(bounds) <= Fn.CVT_MAX_GROUPS
 
     def forward_features(self, x):
         cls, region = self.forward_feature_maps(x)
@@ -268,6 +363,13 @@ class CvT(nn.Module):
                 start = i
         if self.use_dense_prediction:
             cls_parts, fea_parts, npatch = [], [], []
+            if self._ragged(bounds):
+                maps, all_fea = self.forward_feature_maps_multi([x[a:b] for a, b in bounds])
+                for cls, fea in maps:
+                    cls_parts.append(cls)
+                    npatch.append(fea.shape[1])
+                # (the final norm's output already is the concatenation of the groups' region rows)
+                return self.head(torch.cat(cls_parts)), self.head_dense(all_fea), all_fea, npatch
             for a, b in bounds:
                 cls, fea = self.forward_feature_maps(torch.cat(x[a:b]))
                 B, N, C = fea.shape
@@ -277,6 +379,9 @@ class CvT(nn.Module):
             output_cls = cls_parts[0] if len(cls_parts) == 1 else torch.cat(cls_parts)
             output_fea = fea_parts[0] if len(fea_parts) == 1 else torch.cat(fea_parts)
             return self.head(output_cls), self.head_dense(output_fea), output_fea, npatch
+        if self._ragged(bounds):
+            maps, _ = self.forward_feature_maps_multi([x[a:b] for a, b in bounds])
+            return self.head(torch.cat([cls for cls, _ in maps]))
         outs = [self.forward_features(torch.cat(x[a:b])) for a, b in bounds]
         return self.head(outs[0] if len(outs) == 1 else torch.cat(outs))
 

@@ -10,7 +10,7 @@ import os
 import numpy as np
 import torch
 
-from ._lib import BF16, EPI_GELU, EPI_GELU_BWD, EPI_NONE, EPI_QGELU, EPI_QGELU_BWD, F32, GEMM_AUTO, GEMM_DMA8, GEMM_P8, GemmDesc, GemmTopk, check, lib
+from ._lib import BF16, EPI_GELU, EPI_GELU_BWD, EPI_NONE, EPI_QGELU, EPI_QGELU_BWD, F32, GEMM_AUTO, GEMM_DMA8, GEMM_P8, GemmDesc, GemmTopk, GridGroup, MAX_GRID_GROUPS, check, lib
 
 _ACT_DTYPE = torch.bfloat16
 
@@ -1033,24 +1033,29 @@ def conv_out_size(n, k, stride, pad):
     return (n + 2 * pad - k) // stride + 1
 
 
-def conv_im2col(src, nchw, nB, H, W, Cin, k, stride, pad, dtype=None):
+IM2COL_OUT = True  # conv_im2col / conv_col2im take `out=` (a row slice of a larger matrix: the ragged multi-crop ConvEmbed)
+
+
+def conv_im2col(src, nchw, nB, H, W, Cin, k, stride, pad, dtype=None, out=None):
     """-> cols [nB*Ho*Wo, Kpad] (Kpad = k*k*Cin rounded up to 8), column order (ky, kx, c).
     src: fp32 NCHW images (nchw=True) or activation-dtype NHWC tokens [nB*H*W, Cin]."""
     dt = dtype or (_ACT_DTYPE if nchw else src.dtype)
     Ho, Wo = conv_out_size(H, k, stride, pad), conv_out_size(W, k, stride, pad)
     Kpad = -(-(k * k * Cin) // 8) * 8
     assert src.is_contiguous() and (src.dtype == torch.float32 if nchw else src.dtype == dt)
-    cols = torch.empty((nB * Ho * Wo, Kpad), dtype=dt, device=src.device)
+    cols = torch.empty((nB * Ho * Wo, Kpad), dtype=dt, device=src.device) if out is None else out
+    assert cols.shape == (nB * Ho * Wo, Kpad) and cols.dtype == dt and cols.is_contiguous()
     check(lib.esvit_conv_im2col(_code(dt), _p(src), int(bool(nchw)), nB, H, W, Cin, k, stride, pad, Ho, Wo, Kpad, _p(cols), _stream()),
           "conv_im2col")
     return cols
 
 
-def conv_col2im(dcols, nB, H, W, Cin, k, stride, pad):
+def conv_col2im(dcols, nB, H, W, Cin, k, stride, pad, out=None):
     """adjoint of conv_im2col for NHWC sources: dcols act [nB*Ho*Wo, Kpad] -> dsrc fp32 [nB*H*W, Cin]."""
     dcols = _actc(dcols)
     Ho, Wo = conv_out_size(H, k, stride, pad), conv_out_size(W, k, stride, pad)
-    dsrc = torch.empty((nB * H * W, Cin), dtype=torch.float32, device=dcols.device)
+    dsrc = torch.empty((nB * H * W, Cin), dtype=torch.float32, device=dcols.device) if out is None else _f32c(out)
+    assert dsrc.shape == (nB * H * W, Cin)
     check(lib.esvit_conv_col2im(_code(dcols.dtype), _p(dcols), nB, H, W, Cin, k, stride, pad, Ho, Wo, dcols.shape[1], _p(dsrc), _stream()),
           "conv_col2im")
     return dsrc
@@ -1144,6 +1149,79 @@ def pad_crop_tokens(src, nB, Hs, Ws, Hd, Wd):
     dst = torch.empty((nB * Hd * Wd, Cc), dtype=src.dtype, device=src.device)
     check(lib.esvit_pad_crop_tokens(_code(src.dtype), _p(src), nB, Hs, Ws, Hd, Wd, Cc, _p(dst), _stream()), "pad_crop_tokens")
     return dst
+
+
+# ---- grouped mode of the four spatial kernels (include/esvit_hip.h): the resolution groups of a ragged multi-crop step in one launch ----
+def _grid_groups(recs):
+    """recs: list of dicts of esvit_grid_group fields (tensors for the pointers) -> (host record array, -G)"""
+    assert 1 <= len(recs) <= MAX_GRID_GROUPS, len(recs)
+    arr = (GridGroup * len(recs))()
+    for r, d in zip(arr, recs):
+        for k, v in d.items():
+            setattr(r, k, _p(v) if k in ("p0", "p1", "out", "a1", "a2", "a3") else int(v))
+    return arr, -len(recs)
+
+
+def _group_outs(outs, shapes, dt, device):
+    """outs: None (allocate) or one tensor per group -- e.g. row slices of one matrix"""
+    if outs is None:
+        return [torch.empty(sh, dtype=dt, device=device) for sh in shapes]
+    assert len(outs) == len(shapes) and all(t.shape == tuple(sh) and t.dtype == dt and t.is_contiguous() for t, sh in zip(outs, shapes))
+    return list(outs)
+
+
+def pad_crop_tokens_grouped(srcs, geos, outs=None):
+    """pad_crop_tokens of every group in one launch; geos: (nB, Hs, Ws, Hd, Wd) per group -> list of [nB*Hd*Wd, C]"""
+    srcs = [_actc(t) for t in srcs]
+    Cc, dt = srcs[0].shape[1], srcs[0].dtype
+    assert all(t.shape[1] == Cc and t.dtype == dt for t in srcs)
+    assert all(t.shape[0] == nB * Hs * Ws for t, (nB, Hs, Ws, Hd, Wd) in zip(srcs, geos))
+    dsts = _group_outs(outs, [(nB * Hd * Wd, Cc) for (nB, Hs, Ws, Hd, Wd) in geos], dt, srcs[0].device)
+    arr, negG = _grid_groups([dict(p0=t, out=d, nB=nB, H=Hs, W=Ws, Hd=Hd, Wd=Wd, C=Cc, dtype=_code(dt))
+                              for t, d, (nB, Hs, Ws, Hd, Wd) in zip(srcs, dsts, geos)])
+    check(lib.esvit_pad_crop_tokens(_code(dt), C.c_void_p(C.addressof(arr)), negG, 0, 0, 0, 0, Cc, None, _stream()), "pad_crop_tokens(grouped)")
+    return dsts
+
+
+def dwconv3x3_grouped(xs, w, geos, flip=False, outs=None):
+    """dwconv3x3 of every group in one launch; geos: (nB, H, W) per group -> list of y"""
+    xs = [_actc(t) for t in xs]
+    Cc, dt = xs[0].shape[1], xs[0].dtype
+    assert all(t.shape == (nB * H * W, Cc) and t.dtype == dt for t, (nB, H, W) in zip(xs, geos)) and w.numel() == 9 * Cc
+    ys = _group_outs(outs, [t.shape for t in xs], dt, xs[0].device)
+    arr, negG = _grid_groups([dict(p0=t, out=y, nB=nB, H=H, W=W, C=Cc, dtype=_code(dt)) for t, y, (nB, H, W) in zip(xs, ys, geos)])
+    check(lib.esvit_dwconv3x3(_code(dt), C.c_void_p(C.addressof(arr)), _p(_f32c(w)), int(bool(flip)), negG, 0, 0, Cc, None, _stream()), "dwconv3x3(grouped)")
+    return ys
+
+
+def col_sums2_grouped(a_list, b_list):
+    """col_sums2 of every group in one launch -> fp32 [G, 2, C]; row g has the bits of col_sums2(a_list[g], b_list[g])"""
+    a_list, b_list = [_actc(t) for t in a_list], [_actc(t) for t in b_list]
+    Cc, dt = a_list[0].shape[1], a_list[0].dtype
+    assert all(a.shape == b.shape and a.dtype == dt and b.dtype == dt and a.shape[1] == Cc for a, b in zip(a_list, b_list))
+    out = torch.empty((len(a_list), 2, Cc), dtype=torch.float32, device=a_list[0].device)
+    ws = workspace(sum(query(Q_COL_REDUCE_BLOCKS, a.shape[0]) for a in a_list) * 2 * Cc, a_list[0].device, slot=1)
+    arr, negG = _grid_groups([dict(p0=a, p1=b, nB=a.shape[0], H=1, W=1, C=Cc, dtype=_code(dt)) for a, b in zip(a_list, b_list)])
+    check(lib.esvit_col_sums2(_code(dt), C.c_void_p(C.addressof(arr)), None, negG, Cc, _p(out), _p(ws), _stream()), "col_sums2(grouped)")
+    return out
+
+
+def col_affine2_grouped(x1s, a1s, a3s, x2s=None, a2s=None, act=0, outs=None):
+    """col_affine2 of every group (its own coefficient vectors) in one launch -> list of y"""
+    x1s = [_actc(t) for t in x1s]
+    Cc, dt = x1s[0].shape[1], x1s[0].dtype
+    n = len(x1s)
+    x2s = [None] * n if x2s is None else list(x2s)
+    a2s = [None] * n if a2s is None else [None if a is None else _f32c(a) for a in a2s]
+    a1s, a3s = [_f32c(a) for a in a1s], [_f32c(a) for a in a3s]
+    for x1, x2, a1, a2, a3 in zip(x1s, x2s, a1s, a2s, a3s):
+        assert x1.shape[1] == Cc and x1.dtype == dt and a1.numel() == Cc and a3.numel() == Cc and (a2 is None or a2.numel() == Cc)
+        assert x2 is None or (x2.dtype == dt and x2.shape == x1.shape and x2.is_contiguous())
+    ys = _group_outs(outs, [t.shape for t in x1s], dt, x1s[0].device)
+    arr, negG = _grid_groups([dict(p0=x1, p1=x2, out=y, a1=a1, a2=a2, a3=a3, nB=x1.shape[0], H=1, W=1, C=Cc, dtype=_code(dt))
+                              for x1, x2, y, a1, a2, a3 in zip(x1s, x2s, ys, a1s, a2s, a3s)])
+    check(lib.esvit_col_affine2(_code(dt), C.c_void_p(C.addressof(arr)), None, negG, Cc, None, None, None, int(act), None, _stream()), "col_affine2(grouped)")
+    return ys
 
 
 # ------------------------------------------------------------------------------------------------

@@ -553,7 +553,36 @@ int esvit_fused_clip_update_ema(int rule, const int64_t* tensors, int ntensors, 
  *   and esvit_dwconv3x3_wgrad take C % 4 == 0 up to 1024, and bf16 with C % 8 == 0 and 16-byte aligned tensors up to 2048.
  *   These three move four channels per load: x, y, dy, a, b must be aligned to 8 bytes in bf16 and 16 in fp32 (ws: 16).
  *   esvit_pad_crop_tokens wants src and dst on 16 bytes.  The BatchNorm variance is sum(d^2)/n - mean^2 in fp32: the relative
- *   error of rstd grows as 8 (1 + (mean/std)^2) 2^-24 (tests/test_conv_gpu.py holds it to that). */
+ *   error of rstd grows as 8 (1 + (mean/std)^2) 2^-24 (tests/test_conv_gpu.py holds it to that).
+ *
+ * GROUPED MODE of esvit_pad_crop_tokens, esvit_dwconv3x3, esvit_col_sums2 and esvit_col_affine2 (the ragged multi-crop route of
+ *   CvT: the resolution groups of a step differ in their grid, not in C or dtype).  A NEGATIVE batch / row count -G, 1 <= G <= 4,
+ *   turns the entry's FIRST pointer argument (src / x / a / x1) into a HOST array of G esvit_grid_group records; ONE launch then
+ *   does what the G separate calls on the records would do, bit for bit.  The entry copies the records into the kernel's
+ *   argument block: the array may be reused as soon as the call returns, there is no device-side table, allocation or sync.
+ *   Fields of a record:   pad_crop_tokens: p0 = src, out = dst, (nB, H, W) the source grid, (Hd, Wd) the destination grid
+ *                         dwconv3x3:       p0 = x, out = y, (nB, H, W)
+ *                         col_sums2:       p0 = a, p1 = b, rows = nB*H*W
+ *                         col_affine2:     p0 = x1, p1 = x2 (or NULL), out = y, a1 / a2 / a3 this group's coefficients, rows = nB*H*W
+ *   Every record carries the entry's C and dtype (they must equal the entry's arguments).  Arguments of the entry that a record
+ *   replaces (H, W, Hs.., dst / y / b / x2 / a1..a3) are ignored; w, flip, act, ws and the stream are shared.
+ *   esvit_col_sums2: out is fp32 [G][2*C]; group g keeps the ESVIT_Q_COL_REDUCE_BLOCKS(rows_g) partition and the reduction order of
+ *   the plain call on that group alone; ws: fp32 [sum_g ESVIT_Q_COL_REDUCE_BLOCKS(rows_g) * 2*C], the groups' partials one after the
+ *   other.  Grouped esvit_col_sums2 takes C <= 1024; grouped esvit_dwconv3x3 wants all records on the same side of the 16-byte
+ *   test that selects its strip kernel.  Everything the plain call refuses is refused per record, before anything is launched. */
+typedef struct esvit_grid_group {
+    const void* p0;
+    const void* p1;
+    void* out;
+    const float* a1;
+    const float* a2;
+    const float* a3;
+    int32_t nB, H, W;
+    int32_t Hd, Wd;
+    int32_t C, dtype;
+    int32_t reserved; /* 0 */
+} esvit_grid_group;
+#define ESVIT_MAX_GRID_GROUPS 4
 int esvit_conv_im2col(int dtype, const void* src, int nchw, int nB, int H, int W, int Cin, int k, int stride, int pad,
                       int Ho, int Wo, int Kpad, void* cols, esvit_stream_t stream);
 int esvit_conv_col2im(int dtype, const void* dcols, int nB, int H, int W, int Cin, int k, int stride, int pad, int Ho,
