@@ -669,6 +669,10 @@ int launch_ab(const ABParams& prm, hipStream_t stream) {
 }  // namespace
 
 int esvit_i_fill_bias_frag(const float* rel_table, int ws, int N, int nH, float* bias_frag_ws, hipStream_t stream);
+// the backward mode (attn_branch_bwd.hip)
+int esvit_i_attn_branch_bwd(const float* x, const float* gamma, const float* beta, float eps, const void* Wqkv, const float* bqkv, const void* WprojT,
+                            const int32_t* win2tok, int L, const float* bias_frag, const int32_t* region_ids, int nW, int nB, int N, int nH, float scale,
+                            const float* rowscale, const esvit_attn_bwd_desc* d, hipStream_t stream);
 
 #ifdef ESVIT_AB_TIMELINE
 static unsigned* g_ab_timeline = nullptr;
@@ -679,9 +683,19 @@ extern "C" int esvit_attn_branch_fwd(int dtype, const float* x, const float* gam
                                      const float* bqkv, const void* Wproj_p, const float* bproj, const int32_t* win2tok, int L,
                                      const float* rel_table, int ws, float* bias_frag_ws, const int32_t* region_ids, int nW, int nB, int N,
                                      int nH, float scale, const float* rowscale, float* y, void* xw, void* qkv, void* ao, float* mean,
-                                     float* rstd, esvit_stream_t s_) {
+                                     float* rstd, esvit_stream_t s_, const esvit_attn_bwd_desc* bwd) {
     hipStream_t stream = reinterpret_cast<hipStream_t>(s_);
     ESVIT_CHECK_ARG(dtype == ESVIT_BF16, "esvit_attn_branch_fwd: bf16 activations only");
+    if (bwd) {  // the backward mode: the same geometry arguments, no forward output
+        ESVIT_CHECK_ARG(!y && !xw && !qkv && !ao && !mean && !rstd, "esvit_attn_branch_fwd(backward): y and the side outputs must be NULL");
+        ESVIT_CHECK_ARG(!rel_table, "esvit_attn_branch_fwd(backward): bias_frag_ws must already be filled (rel_table = NULL)");
+        ESVIT_CHECK_ARG(x && gamma && beta && Wqkv_p && bqkv && Wproj_p && win2tok && bias_frag_ws && L > 0 && nW > 0 && nB > 0 && N == ws * ws,
+                        "esvit_attn_branch_fwd(backward): bad arguments");
+        ESVIT_CHECK_ARG((long)nB * L * 96 * 4 < 0x7fff0000L && (long)nB * nW < (1L << 22), "esvit_attn_branch_fwd(backward): the rows of one call must stay below 2 GiB and 2^22 windows");
+        ESVIT_CHECK_ARG((((uintptr_t)x | (uintptr_t)Wqkv_p | (uintptr_t)Wproj_p | (uintptr_t)bias_frag_ws | (uintptr_t)gamma | (uintptr_t)beta | (uintptr_t)bqkv) & 15) == 0,
+                        "esvit_attn_branch_fwd(backward): x, the weights, gamma, beta, bqkv and the bias fragments are read in 16-byte pieces: align them");
+        return esvit_i_attn_branch_bwd(x, gamma, beta, eps, Wqkv_p, bqkv, Wproj_p, win2tok, L, bias_frag_ws, region_ids, nW, nB, N, nH, scale, rowscale, bwd, stream);
+    }
     ESVIT_CHECK_ARG(x && gamma && beta && Wqkv_p && bqkv && Wproj_p && bproj && win2tok && bias_frag_ws && y && L > 0 && nW > 0 && nB > 0,
                     "esvit_attn_branch_fwd: bad arguments");
     ESVIT_CHECK_ARG((nH == 3 || nH == 6) && N > 0 && N <= 64 && N == ws * ws, "esvit_attn_branch_fwd: C = 32 nH in {96, 192}, windows of <= 64 tokens (nH=%d N=%d)", nH, N);

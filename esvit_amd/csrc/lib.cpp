@@ -39,6 +39,7 @@ int64_t esvit_i_topk_ws(int64_t M, int64_t N, int64_t k);
 int64_t esvit_i_probe_ce_reg_row();
 int64_t esvit_i_global_attn_ws(int64_t Z, int64_t L, int64_t backward);
 int64_t esvit_i_mlp_dw_ws(int dtype, int C, int64_t M);
+int64_t esvit_i_attn_branch_bwd_grid(int dtype, int C, int64_t windows);
 
 extern "C" int64_t esvit_query(int what, int64_t a, int64_t b, int64_t c) {
     switch (what) {
@@ -59,6 +60,7 @@ extern "C" int64_t esvit_query(int what, int64_t a, int64_t b, int64_t c) {
         case ESVIT_Q_PROBE_CE_REG_ROW: return esvit_i_probe_ce_reg_row();
         case ESVIT_Q_GLOBAL_ATTN_WS: return esvit_i_global_attn_ws(a, b, c);
         case ESVIT_Q_MLP_DW_WS: return esvit_i_mlp_dw_ws((int)a, (int)b, c);
+        case ESVIT_Q_ATTN_BWD_FUSED_GRID: return esvit_i_attn_branch_bwd_grid((int)a, (int)b, c);
     }
     esvit_set_error("esvit_query: unknown question %d", what);
     return ESVIT_ERR_ARG;

@@ -182,6 +182,54 @@ def _attn_fused(dt, C, nH, geoms, save, sizes=None):
     return C == 96 or not save
 
 
+# stage 0 (bf16, C = 96, 7x7 windows): the branch's BACKWARD as one kernel per resolution group too (the backward mode of
+# esvit_attn_branch_fwd): it recomputes the forward per window and keeps dWqkv, dWproj and the small gradients on the chip, so the forward
+# writes no side outputs and the chain from the proj weight gradient to the LayerNorm backward disappears.  Opt-in ("1") until its A-B is
+# won (profiles/attn_bwd_fused_ab.txt); the decision is taken in the forward (it decides what is saved) and read back from what was saved.
+ATTN_BWD_FUSED = os.environ.get("ESVIT_ATTN_BWD_FUSED", "0") == "1"
+
+
+def _attn_bwd_fused(o, dt, C, nH, geoms, sizes):
+    """sizes: (token rows, windows) of every call"""
+    return (ATTN_BWD_FUSED and hasattr(o, "attn_branch_bwd") and all(g.ws == 7 for g in geoms)
+            and all(o.attn_branch_bwd_supported(dt, C, nH, g.N, r, w) for g, (r, w) in zip(geoms, sizes)))
+
+
+def _attn_bwd_w(o, Wqkv_p, Wproj_p, Wqkv):
+    """the bf16 copies the backward mode reads: the plain cast of qkv.weight (the copy every GEMM uses), its transpose and the transpose of
+    proj.weight (ops.cast_weight), cached per parameter version like _perm_w"""
+    def one(p_, kind):
+        fn = lambda: o.cast_weight(p_.detach().contiguous(), transpose=True)  # noqa: E731
+        return P.cached(p_, kind, fn) if (p_.requires_grad or P.is_managed(p_)) else fn()
+    return Wqkv, one(Wqkv_p, "ATTN_BWD_QKVT"), one(Wproj_p, "ATTN_BWD_PROJT")
+
+
+def _attn_branch_bwd(o, X, gx1, segs, nH, frags, index, table, Wqkv, params, g1, b1, bqkv, dp1, prev_scale, want_act):
+    """the attention branch's backward, one launch per resolution group: X, gx1 fp32 [M, C] (branch input, dL/dx1); segs: (row0, nB, L,
+    geom); frags: the groups' filled fragment-order bias; params: (g1, b1, table, Wqkv, bqkv, Wproj, bproj) parameters; dp1: per-row
+    DropPath factors of the branch or None -> (gx, gx_act or None, dg1, db1, dtable, dWqkv, dbqkv, dWproj, dbproj).  The groups stack their
+    partials and bias-gradient slabs: the last call's reduce goes straight into the armed bucket slots, the table's included"""
+    g1_p, b1_p, table_p, Wqkv_p, bqkv_p, Wproj_p, bproj_p = params
+    M, C = X.shape
+    scale = (C // nH) ** -0.5
+    sinks = [P.grad_out(p_) for p_ in (Wqkv_p, bqkv_p, Wproj_p, bproj_p, g1_p, b1_p)]
+    tsink = P.grad_out(table_p)
+    weights = _attn_bwd_w(o, Wqkv_p, Wproj_p, Wqkv)
+    part, dbias, firsts = o.attn_branch_bwd_workspaces([nB * geom.nW for (_, nB, _, geom) in segs], nH, X.device)
+    gx = torch.empty_like(X)
+    gxb = torch.empty((M, C), dtype=Wqkv.dtype, device=X.device) if want_act else None
+    outs = dtable = None
+    for i, ((r0, nB, L, geom), frag) in enumerate(zip(segs, frags)):
+        r1 = r0 + nB * L
+        _, _, outs, _, dtable = o.attn_branch_bwd(X[r0:r1], gx1[r0:r1], g1, b1, LN_EPS, weights, bqkv, geom.win2tok, L, geom.ws, geom.region_ids, geom.nW, geom.N, nH,
+                                          scale, bias_frag=frag, rowscale=None if dp1 is None else dp1[r0:r1],
+                                          rowscale_out=None if (prev_scale is None or not want_act) else prev_scale[r0:r1], out=sinks if outs is None else outs,
+                                          workspaces=(part, dbias), first_partial=firsts[i], finish=i == len(segs) - 1, gx_out=gx[r0:r1],
+                                          gx_act_out=None if gxb is None else gxb[r0:r1], index=index, dtable=tsink, table_rows=table.shape[0])
+    dWqkv, dbqkv, dWproj, dbproj, dg1, db1 = [_alias(t, sk) for t, sk in zip(outs, sinks)]
+    return gx, gxb, dg1, db1, _alias(dtable, tsink), dWqkv, dbqkv, dWproj, dbproj
+
+
 # ---- fused MLP branch (narrow stages, bf16): nothing hidden-sized is kept between forward and backward ------------------------
 # forward: ONE kernel x1 -> x2 (esvit_mlp_fused_fwd).  backward: esvit_mlp_fused_bwd recomputes LayerNorm + pre-activation,
 # produces dL/dx1 (+ its activation-dtype copy) and the operands of the two weight-gradient GEMMs; the LayerNorm parameter
@@ -265,10 +313,12 @@ def _block_forward(x, geom, nH, index, dp, prm, wts, save, w1p=None, wattn=None)
     frag = o.new_bias_frag(nH, geom.N, x.device) if save else None  # kept for the backward (no second fill)
     if wattn is not None and _attn_fused(Wqkv.dtype, C, nH, (geom,), save, [(nB * L, nB * geom.nW)]):
         rs1 = None if dp1 is None else dp1.repeat_interleave(L)
+        # (a training pass whose backward is the one-kernel mode needs no side outputs: the saved tuple keeps its length, with None in their places)
+        side = bool(save) and not _attn_bwd_fused(o, Wqkv.dtype, C, nH, (geom,), [(nB * L, nB * geom.nW)])
         res = o.attn_branch_fwd(x2d, g1, b1, LN_EPS, _perm_w(wattn[0]), bqkv, _perm_w(wattn[1]), bproj, geom.win2tok, L, table, geom.ws, geom.region_ids,
-                                geom.nW, geom.N, nH, scale, rowscale=rs1, bias_frag=frag, save=bool(save))
+                                geom.nW, geom.N, nH, scale, rowscale=rs1, bias_frag=frag, save=side)
         lse = None
-        if save:
+        if side:
             x1, (xw, mean1, rstd1, qkv, ao) = res
         else:
             x1 = res
@@ -307,6 +357,8 @@ class SwinBlockFn(torch.autograd.Function):
         ctx.wparams = (Wqkv_p, Wproj_p, W1_p, W2_p)
         ctx.mlp_params = (g2, b2, W1_p, bfc1, W2_p, bfc2)
         ctx.fused_mlp = len(saved) == 8
+        ctx.attn_bwd_fused = saved[3] is None  # (no qkv was saved: _block_forward chose the one-kernel backward)
+        ctx.attn_params = (g1, b1, table, Wqkv_p, bqkv, Wproj_p, bproj)
         ctx.save_for_backward(x, index, g1, table, g2, bqkv, b2, bfc1, *wts, *saved)
         return y
 
@@ -339,6 +391,13 @@ class SwinBlockFn(torch.autograd.Function):
             dh = o.linear_dgrad(da1, W1)
             # ---- attention branch ---- (the LayerNorm backward also emits the DropPath-scaled activation-dtype copy of gx1)
             gx1, dyw, dg2, db2 = o.layernorm_bwd_cast(dh, x1, mean2, rstd2, g2, g_in=gy, rowscale=dp1, rows_per_sample=L)
+        if ctx.attn_bwd_fused:
+            gx, _, dg1, db1, dtable, dWqkv, dbqkv, dWproj, dbproj = _attn_branch_bwd(
+                o, x.view(M, C), gx1, ((0, nB, L, geom),), nH, (frag,), index, table, Wqkv, ctx.attn_params, g1, ctx.attn_params[1].detach(), bqkv,
+                None if dp1 is None else dp1.repeat_interleave(L), None, False)
+            _side_join()
+            return (gx.view(nB, L, C), None, None, None, None, dg1, db1, dtable, dWqkv, dbqkv, dWproj, dbproj, dg2, db2, dW1, dbfc1,
+                    dW2, dbfc2)
         dWproj, dbproj = _wgrad(dyw, ao, Wproj_p, want_bias=True)
         dao = o.linear_dgrad(dyw, Wproj)
         dqkv, dbias_ws, dpad_ws = o.window_attn_bwd(qkv, bqkv, geom.win2tok, L, dao, ao, lse, None, geom.ws, geom.region_ids,
@@ -377,7 +436,9 @@ def _block_forward_multi(X, segs, nH, dp_rows, prm, wts, save, pre=None, next_no
         # have produced) is not needed: the kernel normalises the rows it loads for the residual anyway
         Wq_p, Wp_p = _perm_w(wattn[0]), _perm_w(wattn[1])
         x1 = torch.empty_like(X)
-        if save:
+        # (a training pass whose backward is the one-kernel mode needs no side outputs)
+        side = bool(save) and not _attn_bwd_fused(o, Wqkv.dtype, C, nH, [sg[3] for sg in segs], [(sg[1] * sg[2], sg[1] * sg[3].nW) for sg in segs])
+        if side:
             xw = torch.empty((M, C), dtype=Wqkv.dtype, device=X.device)
             qkv = torch.empty((M, 3 * C), dtype=Wqkv.dtype, device=X.device)
             ao = torch.empty((M, C), dtype=Wqkv.dtype, device=X.device)
@@ -390,7 +451,7 @@ def _block_forward_multi(X, segs, nH, dp_rows, prm, wts, save, pre=None, next_no
             first = (geom.ws, geom.N) not in frags
             if first:
                 frags[(geom.ws, geom.N)] = o.new_bias_frag(nH, geom.N, X.device)
-            sv = (xw[r0:r1], mean1[r0:r1], rstd1[r0:r1], qkv[r0:r1], ao[r0:r1]) if save else False
+            sv = (xw[r0:r1], mean1[r0:r1], rstd1[r0:r1], qkv[r0:r1], ao[r0:r1]) if side else False
             o.attn_branch_fwd(X[r0:r1], g1, b1, LN_EPS, Wq_p, bqkv, Wp_p, bproj, geom.win2tok, L, table if first else None, geom.ws, geom.region_ids,
                               geom.nW, geom.N, nH, scale, rowscale=None if dp1 is None else dp1[r0:r1], out=x1[r0:r1],
                               bias_frag=frags[(geom.ws, geom.N)], save=sv)
@@ -464,6 +525,7 @@ class SwinBlockMultiFn(torch.autograd.Function):
         ctx.emit_shadow, ctx.prev_scale = Xsh is not None, prev_scale
         ctx.set_materialize_grads(False)
         ctx.fused_mlp = len(saved) == 6
+        ctx.attn_bwd_fused = saved[3] is None  # (no qkv was saved: _block_forward_multi chose the one-kernel backward)
         ctx.save_for_backward(X, index, g1, table, g2, bqkv, b2, bfc1, *wts, *saved)
         ysh = torch.empty(X.shape, dtype=wts[0].dtype, device=X.device)
         if nxt is None:
@@ -502,6 +564,12 @@ class SwinBlockMultiFn(torch.autograd.Function):
             gx1, dyw, dg2, db2 = o.layernorm_bwd_cast(dh, x1, mean2, rstd2, g2, g_in=gy, rowscale=dp1, rows_per_sample=1, gb_out=ln2)
             dg2, db2 = _alias(dg2, ln2), _alias(db2, ln2)
         # ---- attention branch ----
+        if ctx.attn_bwd_fused:
+            gx, gxb, dg1, db1, dtable, dWqkv, dbqkv, dWproj, dbproj = _attn_branch_bwd(
+                o, X, gx1, segs, nH, [fr for (_, fr) in ctx.lses], index, table, Wqkv, (g1_p, b1_p, table_p, Wqkv_p, bqkv_p, Wproj_p, bproj_p), g1,
+                b1_p.detach(), bqkv, dp1, ctx.prev_scale, ctx.emit_shadow)
+            _side_join()
+            return (gx, gxb, None, None, None, None, None, None, None, dg1, db1, dtable, dWqkv, dbqkv, dWproj, dbproj, dg2, db2, dW1, dbfc1, dW2, dbfc2)
         dWproj, dbproj = _side_run(lambda: _wgrad(dyw, ao, Wproj_p, want_bias=True, bias_param=bproj_p), dyw, ao)
         dao = o.linear_dgrad(dyw, Wproj)
         dqkv = torch.empty_like(qkv)

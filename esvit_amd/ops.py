@@ -84,8 +84,9 @@ def relative_position_index(ws):
 # esvit_query questions (include/esvit_hip.h)
 (Q_ATTN_FRAG_ELEMS, Q_ATTN_LSE_ELEMS, Q_ATTN_BWD_PARTS, Q_ATTN_BWD_PAD_ROWS, Q_LN_BWD_BLOCKS, Q_COLSUM_BLOCKS, Q_COL_REDUCE_BLOCKS,
  Q_UPDATE_CHUNK_ELEMS, Q_MLP_FUSED, Q_AUG_MAX_BOX, Q_JPEG_WORKSPACE, Q_RESIZE_FITS, Q_CHUNK_ATTN_WS, Q_TOPK_WS, Q_PROBE_CE_REG_ROW,
- Q_GLOBAL_ATTN_WS, Q_MLP_DW_WS) = range(1, 18)
+ Q_GLOBAL_ATTN_WS, Q_MLP_DW_WS, Q_ATTN_BWD_FUSED_GRID) = range(1, 19)
 MLP_DW_PARTIAL_FLOATS = 74208  # ESVIT_MLP_DW_PARTIAL_FLOATS
+ATTN_BWD_PARTIAL_FLOATS = 37440  # ESVIT_ATTN_BWD_PARTIAL_FLOATS
 
 
 def query(what, a=0, b=0, c=0):
@@ -797,8 +798,102 @@ def attn_branch_fwd(x, gamma, beta, eps, Wqkv_p, bqkv, Wproj_p, bproj, win2tok, 
     assert rel_table is not None or bias_frag is not None
     check(lib.esvit_attn_branch_fwd(BF16, _p(x), _p(_f32c(gamma)), _p(_f32c(beta)), eps, _p(Wqkv_p), _p(_f32c(bqkv)), _p(Wproj_p), _p(_f32c(bproj)),
                                     _p(win2tok), L, _p(None if rel_table is None else _f32c(rel_table)), ws, _p(bias_ws), _p(region_ids), nW, nB, N, nH,
-                                    scale, _p(rowscale), _p(y), _p(xw), _p(qkv), _p(ao), _p(mean), _p(rstd), _stream()), "attn_branch_fwd")
+                                    scale, _p(rowscale), _p(y), _p(xw), _p(qkv), _p(ao), _p(mean), _p(rstd), _stream(), None), "attn_branch_fwd")
     return (y, (xw, mean, rstd, qkv, ao)) if save else y
+
+
+class AttnBwdDesc(C.Structure):
+    """esvit_attn_bwd_desc (include/esvit_hip.h)"""
+    _fields_ = [(n, C.c_void_p) for n in ("gin", "rowscale_out", "gx", "gx_act", "WqkvT", "dWqkv", "dbqkv", "dWproj", "dbproj", "dgamma", "dbeta",
+                                         "dbias_ws", "partials_ws")] + [("first_partial", C.c_int32), ("finish", C.c_int32), ("index", C.c_void_p),
+                                                                        ("dtable", C.c_void_p), ("table_rows", C.c_int32)]
+
+
+def attn_branch_bwd_grid(dt, Cc, windows):
+    """workgroups (= partials, = bias-gradient slabs, = the summation order) of one attn_branch_bwd call over `windows` windows on the
+    current device; 0 where the mode does not exist"""
+    return query(Q_ATTN_BWD_FUSED_GRID, _code(dt) if dt in (torch.float32, torch.bfloat16) else -1, int(Cc), int(windows))
+
+
+def attn_branch_bwd_supported(dt, Cc, nH, N, rows=0, windows=1):
+    """the backward mode of the fused attention branch exists for this call: bf16, C = 96 = 3 heads of 32, 7x7 windows, inside the
+    forward's buffer-range and window-count limits"""
+    return (dt == torch.bfloat16 and int(Cc) == 96 and int(nH) == 3 and int(N) == 49 and attn_branch_supported(dt, Cc, nH, N, rows, windows)
+            and attn_branch_bwd_grid(dt, Cc, max(int(windows), 1)) > 0)
+
+
+def attn_branch_bwd_weights(Wqkv, Wproj):
+    """the three bf16 copies the backward mode reads, from the fp32 masters: (qkv.weight [3C, C], its transpose [C, 3C], the transpose of
+    proj.weight [C, C])"""
+    return cast_weight(Wqkv), cast_weight(Wqkv, transpose=True), cast_weight(Wproj, transpose=True)
+
+
+def attn_branch_bwd_workspaces(windows, nH, device):
+    """partials and bias-gradient slabs for the calls of one block (its resolution groups, `windows` = their window counts), stacked so
+    that the LAST call's finish (partial reduce, slab fold, table gather) serves them all -> (partials_ws [n, ATTN_BWD_PARTIAL_FLOATS], dbias_ws [n, nH, frag], firsts)"""
+    grids = [attn_branch_bwd_grid(torch.bfloat16, 32 * nH, w) for w in windows]
+    assert all(g_ > 0 for g_ in grids)
+    n = sum(grids)
+    firsts = [sum(grids[:i]) for i in range(len(grids))]
+    return (torch.empty((n, ATTN_BWD_PARTIAL_FLOATS), dtype=torch.float32, device=device),
+            torch.empty((n, nH, attn_frag_elems(49)), dtype=torch.float32, device=device), firsts)
+
+
+def attn_branch_bwd(x, gin, gamma, beta, eps, weights, bqkv, win2tok, L, ws, region_ids, nW, N, nH, scale, *, bias_frag, rowscale=None,
+                    rowscale_out=None, out=None, workspaces=None, first_partial=0, finish=True, gx_out=None, gx_act_out=None,
+                    index=None, dtable=None, table_rows=0):
+    """backward of attn_branch_fwd for one resolution group in one kernel: x fp32 [nB*L, C] (the branch input), gin = dL/dx1 fp32 ->
+    (gx fp32, gx_act bf16 = cast(rowscale_out * gx) or None, (dWqkv, dbqkv, dWproj, dbproj, dgamma, dbeta), dbias_ws, dtable or None).
+    weights = attn_branch_bwd_weights(...); bias_frag: the block's filled fragment-order bias.  out: the six fp32 tensors to write the
+    gradients to (each or any None).  workspaces = (partials_ws, dbias_ws) of attn_branch_bwd_workspaces with this call's first_partial;
+    finish=False leaves the reduce to a later call of the same block (the gradients are then not yet written), finish=True sums every
+    partial up to and including this call's.  index (the relative-position index) with table_rows, or a dtable fp32 [table_rows, nH] to write
+    to: the finishing call also sums the slabs and gathers the table's gradient, without atomics (bit-reproducible, unlike relpos_bias_bwd,
+    which the slabs may go to instead).  gx_out / gx_act_out: row slices of a block's matrices
+    to write gx / gx_act to."""
+    x, gin = _f32c(x), _f32c(gin)
+    rows, Cc = x.shape
+    nB = rows // L
+    Wq, WqT, WpT = weights
+    dev = x.device
+    assert gin.shape == x.shape and rows == nB * L and Wq.shape == (3 * Cc, Cc) and WqT.shape == (Cc, 3 * Cc) and WpT.shape == (Cc, Cc)
+    assert Wq.dtype == WqT.dtype == WpT.dtype == torch.bfloat16 and Wq.is_contiguous() and WqT.is_contiguous() and WpT.is_contiguous()
+    grid = attn_branch_bwd_grid(torch.bfloat16, Cc, nB * nW)
+    if grid <= 0:
+        raise RuntimeError("attn_branch_bwd: no backward mode of the fused attention branch at C = %d" % Cc)
+    shapes = ((3 * Cc, Cc), (3 * Cc,), (Cc, Cc), (Cc,), (Cc,), (Cc,))
+    outs = list(out) if out is not None else [None] * 6
+    for i, sh in enumerate(shapes):
+        if outs[i] is None:
+            outs[i] = torch.empty(sh, dtype=torch.float32, device=dev)
+        assert tuple(outs[i].shape) == sh
+        _f32c(outs[i])
+    if workspaces is None:
+        part, dbias, _ = attn_branch_bwd_workspaces([nB * nW], nH, dev)
+        first_partial = 0
+    else:
+        part, dbias = workspaces
+    assert part.shape[0] >= first_partial + grid and dbias.shape[0] == part.shape[0] and part.shape[1] == ATTN_BWD_PARTIAL_FLOATS
+    for r_ in (rowscale, rowscale_out):
+        assert r_ is None or (r_.shape == (rows,) and r_.dtype == torch.float32 and r_.is_contiguous())
+    gx = torch.empty_like(x) if gx_out is None else _f32c(gx_out)
+    gxa = gx_act_out
+    assert gx.shape == x.shape and (gxa is None or (gxa.shape == x.shape and gxa.dtype == torch.bfloat16 and gxa.is_contiguous()))
+    if finish and index is not None:
+        if dtable is None:
+            dtable = torch.empty((int(table_rows), nH), dtype=torch.float32, device=dev)
+        assert index.dtype == torch.int64 and index.is_contiguous() and index.numel() == N * N and dtable.shape[1] == nH
+        _f32c(dtable)
+    else:
+        dtable = None
+    a = lambda t: None if t is None else _p(t).value  # noqa: E731
+    d = AttnBwdDesc(a(gin), a(rowscale_out), a(gx), a(gxa), a(WqT), a(outs[0]), a(outs[1]), a(outs[2]), a(outs[3]), a(outs[4]), a(outs[5]),
+                    a(_f32c(dbias)), a(_f32c(part)), int(first_partial), int(first_partial + grid) if finish else 0, a(index if dtable is not None else None),
+                    a(dtable), 0 if dtable is None else int(dtable.shape[0]))
+    check(lib.esvit_attn_branch_fwd(BF16, _p(x), _p(_f32c(gamma)), _p(_f32c(beta)), eps, _p(Wq), _p(_f32c(bqkv)), _p(WpT), None, _p(win2tok), L, None, ws,
+                                    _p(_f32c(bias_frag)), _p(region_ids), nW, nB, N, nH, scale, _p(rowscale), None, None, None, None, None, None,
+                                    _stream(), C.byref(d)), "attn_branch_bwd")
+    return gx, gxa, tuple(outs), dbias, dtable
 
 
 def attn_dbias_slabs(N, windows, nH, device):

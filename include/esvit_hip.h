@@ -80,6 +80,11 @@ const char* esvit_last_error(void);
 #define ESVIT_Q_GLOBAL_ATTN_WS 16
 #define ESVIT_Q_MLP_DW_WS 17
 #define ESVIT_MLP_DW_PARTIAL_FLOATS 74208 /* dW2 96 x 384 + G 384 x 96 + db1 384 + db2 96 */
+/*   ESVIT_Q_ATTN_BWD_FUSED_GRID (dtype, C, windows)  workgroups of one launch of the backward mode of the fused attention branch over `windows`
+ *                                              windows (= partials and bias-gradient slabs it writes; one per CU, at most one per window); 0 where
+ *                                              the mode does not exist (anything but bf16, C = 96).  Needs no device (then: the size of an MI355X) */
+#define ESVIT_Q_ATTN_BWD_FUSED_GRID 18
+#define ESVIT_ATTN_BWD_PARTIAL_FLOATS 37440 /* dWqkv 288 x 96 + dWproj 96 x 96 + dbqkv 288 + dbproj 96 + dgamma 96 + dbeta 96 */
 int64_t esvit_query(int what, int64_t a, int64_t b, int64_t c);
 
 /* ---- host-side integer index maps (bit-exact vs reference) -------------
@@ -320,12 +325,60 @@ int esvit_token_mean_bwd(const float* g_mean, const float* g_tok, int nB, int T,
  * dropped).  Wqkv_p bf16 [3C, C] and Wproj_p bf16 [C, C]: esvit_cast_weight(W, perm32 = 1) of qkv.weight / proj.weight.
  * rowscale fp32 [nB*L] (DropPath factor of every row) or NULL.  Side outputs for a training pass whose backward runs the
  * unfused kernels -- all five or none: xw bf16 [nB*L, C] = LayerNorm(x), qkv bf16 [nB*L, 3C], ao bf16 [nB*L, C] (attention
- * output before the projection), mean / rstd fp32 [nB*L].  The rows of one call must fit 2 GiB buffer ranges. */
+ * output before the projection), mean / rstd fp32 [nB*L].  The rows of one call must fit 2 GiB buffer ranges.  bwd = NULL: this
+ * forward; otherwise the backward mode described below. */
+/* Backward mode of the fused attention branch (bf16, C = 96, nH = 3, head_dim 32, 7x7 windows): with bwd != NULL the call is the
+ * branch's BACKWARD for the same geometry arguments.  It recomputes the forward per window from x and writes gx = dL/dx; the weight
+ * gradients, the LayerNorm gradients and the relative-position-bias gradient are accumulated on the chip: every workgroup writes one
+ * partial of ESVIT_ATTN_BWD_PARTIAL_FLOATS floats and one bias-gradient slab [nH][4096] in the frag layout esvit_relpos_bias_bwd
+ * folds; a second launch sums the partials in index order (no atomics: identical launches give identical bits).  In this mode
+ *   y and the five side outputs must be NULL, bias_frag_ws must already be filled (rel_table = NULL), bproj is not read;
+ *   Wqkv_p  = the plain bf16 cast of qkv.weight [3C, C] (esvit_cast_weight, no flags);
+ *   Wproj_p = the TRANSPOSED plain bf16 cast of proj.weight [C, C] (esvit_cast_weight, transpose = 1);
+ *   rowscale = the branch's DropPath row factors (dy = rowscale * gin), or NULL.
+ * Layout (64-bit pointers), offsets in bytes:
+ *     0 gin            fp32 [rows, C]  dL/dx1 (required, 16-byte aligned)
+ *     8 rowscale_out   fp32 [rows] or NULL: factors of gx_act
+ *    16 gx             fp32 [rows, C]  out (required, 16-byte aligned)
+ *    24 gx_act         bf16 [rows, C] or NULL: cast(rowscale_out * gx)
+ *    32 WqkvT          bf16 [C, 3C]: the transposed plain cast of qkv.weight (required)
+ *    40 dWqkv  48 dbqkv  56 dWproj  64 dbproj  72 dgamma  80 dbeta     fp32 outputs (required; written by the call with finish > 0)
+ *    88 dbias_ws       fp32 [partials, nH, 4096] (required, 16-byte aligned)
+ *    96 partials_ws    fp32 [partials, ESVIT_ATTN_BWD_PARTIAL_FLOATS] (required, 16-byte aligned)
+ *   104 first_partial  index of this call's first partial / slab; the call writes esvit_query(ESVIT_Q_ATTN_BWD_FUSED_GRID, ...) of them
+ *   108 finish         0: do not reduce yet; n > 0: after this launch sum partials [0, n) into the six outputs (n >= first_partial + this
+ *                      call's workgroups), so that the groups of a ragged block stack their partials and reduce once
+ *   112 index          int64 [N*N] relative-position index, 120 dtable fp32 [table_rows, nH], 128 table_rows: optional, all or none.  With
+ *                      them the finishing call also writes the table's gradient (overwritten) WITHOUT atomics: the slabs [0, n) are
+ *                      summed in index order into slab 0, whose sum the table's rows then gather in query order -- identical launches give
+ *                      identical bits, which esvit_relpos_bias_bwd (an atomicAdd scatter) does not.  dtable = NULL: the slabs are left for
+ *                      esvit_relpos_bias_bwd(dbias_ws, n, ...)
+ * Every misuse returns ESVIT_ERR_ARG before any launch. */
+typedef struct esvit_attn_bwd_desc {
+    const float* gin;
+    const float* rowscale_out;
+    float* gx;
+    void* gx_act;
+    const void* WqkvT;
+    float* dWqkv;
+    float* dbqkv;
+    float* dWproj;
+    float* dbproj;
+    float* dgamma;
+    float* dbeta;
+    float* dbias_ws;
+    float* partials_ws;
+    int32_t first_partial;
+    int32_t finish;
+    const int64_t* index;
+    float* dtable;
+    int32_t table_rows;
+} esvit_attn_bwd_desc;
 int esvit_attn_branch_fwd(int dtype, const float* x, const float* gamma, const float* beta, float eps, const void* Wqkv_p,
                           const float* bqkv, const void* Wproj_p, const float* bproj, const int32_t* win2tok, int L,
                           const float* rel_table, int ws, float* bias_frag_ws, const int32_t* region_ids, int nW, int nB, int N,
                           int nH, float scale, const float* rowscale, float* y, void* xw, void* qkv, void* ao, float* mean,
-                          float* rstd, esvit_stream_t stream);
+                          float* rstd, esvit_stream_t stream, const esvit_attn_bwd_desc* bwd);
 
 /* ---- window attention (swin_transformer.py:126-152) ---------------------
  * "frag layout" of an NP x NP matrix X[q][key] (NP = 64 for 7x7 windows): the order in which the
