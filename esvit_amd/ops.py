@@ -949,6 +949,9 @@ def relpos_bias_bwd(dbias_ws, index, N, table_rows, out=None, accumulate=None):
     """out: optional fp32 [table_rows, nH]; accumulate (default: True when out is given -- the second resolution group of a
     ragged block) adds to it, False overwrites it (a gradient-bucket slot written for the first time)"""
     parts, nH, _ = dbias_ws.shape
+    if index.shape[-1] != N:  # N < ws^2 (a ViT crop on the first N positions of the grid): the kernel reads index[q * N + key]
+        index = index[:N, :N].contiguous()
+    assert index.dtype == torch.int64 and index.is_contiguous() and tuple(index.shape) == (N, N), (index.dtype, index.shape, N)
     dtable = torch.empty((table_rows, nH), dtype=torch.float32, device=dbias_ws.device) if out is None else _f32c(out)
     acc = (out is not None) if accumulate is None else (bool(accumulate) and out is not None)
     check(lib.esvit_relpos_bias_bwd(_p(dbias_ws), parts, _p(index), N, nH, table_rows, _p(dtable), int(acc), _stream()),

@@ -627,6 +627,7 @@ def window_attn_bwd(qkv, qkv_bias, win2tok, L, dout, fwd_out, lse, rel_table, ws
 def relpos_bias_bwd(dbias_ws, index, N, table_rows, out=None, accumulate=None):
     nH = dbias_ws.shape[1]
     dense = _dense_from_frag(dbias_ws.sum(0), N)  # [nH, N, N]
+    index = index[:N, :N].contiguous()  # (N < ws^2: the first N positions of the grid, as relpos_bias_fwd)
     dtable = torch.zeros((table_rows, nH), dtype=torch.float32, device=dbias_ws.device) if out is None else out
     if out is not None and accumulate is not None and not accumulate:
         dtable.zero_()
