@@ -57,9 +57,14 @@ def attention_entropy(model, images, queries=None, unit="bits"):
     window maps of `forward_selfattention(images, n=2)`.  Any other backbone: TypeError.
 
     unit: "bits" (the reference's log2) or "nats".  Convention 0 log 0 = 0: a probability that underflowed to zero contributes nothing.
-    The reference's `(-p * torch.log2(p)).sum(-1)` (analyze_models.py:116-135) evaluates 0 * -inf there and returns NaN for the row."""
+    The reference's `(-p * torch.log2(p)).sum(-1)` (analyze_models.py:116-135) evaluates 0 * -inf there and returns NaN for the row.
+
+    images: one batch [B, 3, H, W] (H and W need not be equal for a VisionTransformer), or a list of batches of different shapes --
+    then a list of results in the same order, one pass per batch (the reference's loop feeds one picture at a time)."""
     if unit not in _UNITS:
         raise ValueError("unit: bits or nats, not %r" % (unit,))
+    if isinstance(images, (list, tuple)):
+        return [attention_entropy(model, im, queries, unit) for im in images]
     k = _UNITS[unit]
     if _is_vit(model):
         ents, _ = _vit_block_stats(model, images, None, None, False)
@@ -84,7 +89,9 @@ def attention_entropy(model, images, queries=None, unit="bits"):
 def attention_rows(model, images, queries, blocks=None):
     """the attention maps of the listed query tokens, what `attentions[0, :, query, :]` reads of `forward_selfattention`, for every
     image and every chosen block: -> fp32 [len(blocks), B, nH, len(queries), N].  blocks: indices into model.blocks (default: the last
-    block).  VisionTransformer only."""
+    block).  VisionTransformer only.  images: a batch of any (H, W), or a list of batches -> a list in the same order."""
+    if isinstance(images, (list, tuple)):
+        return [attention_rows(model, im, queries, blocks) for im in images]
     if not _is_vit(model):
         raise TypeError("attention_rows: VisionTransformer backbones only, not %s" % type(model).__name__)
     if queries is None or len(queries) == 0:
@@ -115,6 +122,11 @@ class AttentionEntropyMeter:
         self.images = 0
 
     def update(self, model, images, queries=None):
+        """images: a batch, or a list of batches of different shapes (each image counts once whatever its size)"""
+        if isinstance(images, (list, tuple)):
+            for im in images:
+                self.update(model, im, queries)
+            return self
         ent = attention_entropy(model, images, queries, self.unit)
         if isinstance(ent, list):  # Swin: a window is a sample of its block; the heads differ from stage to stage -> a list per block
             per = [e.double().mean(-1).mean(0) * images.shape[0] for e in ent]

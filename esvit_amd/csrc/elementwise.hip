@@ -122,23 +122,23 @@ __global__ __launch_bounds__(32 * SLICES) void partial_reduce_kernel(const float
 }
 
 // ---- PatchEmbed im2col -------------------------------------------------------------------------
-// cols[(b*G + i)*G + j][c*P*P + ph*P + pw] = img[b][c][i*P+ph][j*P+pw]  (weight.view(E, 3*P*P) order)
+// cols[(b*Gh + i)*Gw + j][c*P*P + ph*P + pw] = img[b][c][i*P+ph][j*P+pw]  (weight.view(E, 3*P*P) order); Gh = H/P, Gw = W/P
 template <typename T>
-__global__ __launch_bounds__(256) void im2col_kernel(const float* __restrict__ img, T* __restrict__ cols, int nB, int S, int P,
+__global__ __launch_bounds__(256) void im2col_kernel(const float* __restrict__ img, T* __restrict__ cols, int nB, int H, int W, int P,
                                                      int Kpad) {
-    const int G = S / P;
-    const long total = (long)nB * G * G * (Kpad / 4);
+    const int Gh = H / P, Gw = W / P;
+    const long total = (long)nB * Gh * Gw * (Kpad / 4);
     const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= total) return;
     const int k4 = (int)(i % (Kpad / 4));
     const long row = i / (Kpad / 4);
-    const int j = (int)(row % G), ii = (int)((row / G) % G);
-    const long b = row / ((long)G * G);
+    const int j = (int)(row % Gw), ii = (int)((row / Gw) % Gh);
+    const long b = row / ((long)Gh * Gw);
     f32x4 v = {0.f, 0.f, 0.f, 0.f};
     const int k = k4 * 4;
     if (k < 3 * P * P) {
         const int c = k / (P * P), ph = (k / P) % P, pw = k % P;  // P % 4 == 0 so 4 consecutive pw stay in one row
-        v = *reinterpret_cast<const f32x4*>(img + ((b * 3 + c) * S + (ii * P + ph)) * (long)S + j * P + pw);
+        v = *reinterpret_cast<const f32x4*>(img + ((b * 3 + c) * H + (ii * P + ph)) * (long)W + j * P + pw);
     }
     if constexpr (sizeof(T) == 4) {
         *reinterpret_cast<f32x4*>(cols + row * Kpad + k) = v;
@@ -281,13 +281,15 @@ extern "C" int esvit_colsum(int dtype, const void* x, int64_t rows, int N, int64
 
 extern "C" int esvit_patch_im2col(int dtype, const float* img, void* cols, int nB, int S, int P, int Kpad, esvit_stream_t s_) {
     STREAM(s_);
-    ESVIT_CHECK_ARG(img && cols && nB > 0 && S > 0 && P > 0 && P % 4 == 0 && S % P == 0 && Kpad % 8 == 0 && Kpad >= 3 * P * P,
-                    "esvit_patch_im2col: bad args (S=%d P=%d Kpad=%d)", S, P, Kpad);
-    const int G = S / P;
-    const long total = (long)nB * G * G * (Kpad / 4);
+    // S < 65536: the side of a square image; otherwise the rectangle H = S & 0xffff (rows), W = S >> 16 (columns)
+    const int H = S < 65536 ? S : (S & 0xffff), W = S < 65536 ? S : (S >> 16);
+    ESVIT_CHECK_ARG(img && cols && nB > 0 && S > 0 && H > 0 && W > 0 && P > 0 && P % 4 == 0 && H % P == 0 && W % P == 0 && Kpad % 8 == 0 &&
+                        Kpad >= 3 * P * P,
+                    "esvit_patch_im2col: bad args (H=%d W=%d P=%d Kpad=%d)", H, W, P, Kpad);
+    const long total = (long)nB * (H / P) * (W / P) * (Kpad / 4);
     const int grid = ceil_div(total, 256);
-    if (dtype == ESVIT_BF16) hipLaunchKernelGGL(im2col_kernel<bf16>, dim3(grid), dim3(256), 0, stream, img, (bf16*)cols, nB, S, P, Kpad);
-    else if (dtype == ESVIT_F32) hipLaunchKernelGGL(im2col_kernel<float>, dim3(grid), dim3(256), 0, stream, img, (float*)cols, nB, S, P, Kpad);
+    if (dtype == ESVIT_BF16) hipLaunchKernelGGL(im2col_kernel<bf16>, dim3(grid), dim3(256), 0, stream, img, (bf16*)cols, nB, H, W, P, Kpad);
+    else if (dtype == ESVIT_F32) hipLaunchKernelGGL(im2col_kernel<float>, dim3(grid), dim3(256), 0, stream, img, (float*)cols, nB, H, W, P, Kpad);
     else {
         BAD_DTYPE("esvit_patch_im2col");
     }

@@ -13,6 +13,7 @@ Stages (reference lines):
   ConvEmbedFn, CvtAttnFn, CvtFfnFn   cvt_v4_transformer.py:349-382, 108-220 (+75-105), 62-72  (BASELINE config 5)
   ConvEmbedMultiFn, CvtAttnMultiFn, CvtFfnMultiFn   the same over the token rows of several resolution groups (cvt_v4_transformer.py:625-628)
 """
+import math
 import os
 
 import torch
@@ -1781,19 +1782,26 @@ class ConvEmbedMultiFn(torch.autograd.Function):
 # monolithic ViT (models/vision_transformer.py:96-381): patch embedding without a norm, blocks with global attention
 # ------------------------------------------------------------------------------------------------
 class VitPatchEmbedFn(torch.autograd.Function):
-    """PatchEmbed (vision_transformer.py:121-139): Conv2d(k = stride = patch) as im2col + GEMM, fp32 tokens out"""
+    """PatchEmbed (vision_transformer.py:121-139): Conv2d(k = stride = patch) as im2col + GEMM, fp32 tokens out.  img [nB, 3, H, W], both
+    sides multiples of the patch size -> [nB, (H / patch) * (W / patch), E], patch rows first.  An ops module whose patch_im2col takes
+    square images only (the CPU restatement) gets the columns of a rectangle from F.unfold, which has the same (c, ph, pw) order."""
 
     @staticmethod
     def forward(ctx, img, Wp, bp, patch):
         o = ops_module()
         E = Wp.shape[0]
         Kc = Wp.shape[1] * patch * patch
-        nB, _, S, _ = img.shape
-        cols = o.patch_im2col(img.contiguous(), patch, Kc)
+        nB, _, H, Wd = img.shape
+        if H == Wd or getattr(o, "PATCH_IM2COL_RECT", False):
+            cols = o.patch_im2col(img.contiguous(), patch, Kc)
+        else:
+            if H % patch or Wd % patch:
+                raise ValueError("VitPatchEmbedFn: image %dx%d is not made of whole %d-pixel patches" % (H, Wd, patch))
+            cols = o.cast_to_act(torch.nn.functional.unfold(img.float(), patch, stride=patch).transpose(1, 2).reshape(-1, Kc).contiguous())
         y = o.linear_fwd(cols, _weight(Wp, (E, Kc)), bp, out_f32=True)
         ctx.save_for_backward(cols)
         ctx.wparam, ctx.bparam, ctx.wshape = Wp, bp, tuple(Wp.shape)
-        return y.view(nB, (S // patch) ** 2, E)
+        return y.view(nB, (H // patch) * (Wd // patch), E)
 
     @staticmethod
     def backward(ctx, gx):
@@ -1805,6 +1813,62 @@ class VitPatchEmbedFn(torch.autograd.Function):
         # backward -- autograd sums them and the reducer's hook packs the sum)
         dW, dbp = o.linear_wgrad(dyb, cols, want_bias=True)
         return None, dW.view(ctx.wshape), dbp, None
+
+
+# position embedding on an (h, w) patch grid (vision_transformer.py:296-312)
+_VIT_POS = {}
+_CUBIC_A = -0.75
+
+
+def vit_pos_axis_matrix(S, n_base, g):
+    """one axis of torch's F.interpolate(mode="bicubic", scale_factor=g / sqrt(n_base)) from S lines to g, as a matrix: fp64 [g, S].
+    Output line d < floor(S * sf) reads the source coordinate x = s (d + 0.5) - 0.5 with s the FLOAT32 value of 1 / sf (torch hands the
+    kernel the scale factor, not the size ratio; align_corners False), four taps around floor(x) weighted by the cubic convolution
+    kernel with A = -0.75, taps outside the grid clamped to the border.  Lines floor(S * sf) .. g - 1 are zero rows."""
+    import numpy as np
+    sf = g / math.sqrt(n_base)
+    n_out = min(g, int(math.floor(S * sf)))
+    s = float(np.float32(1.0 / sf))
+    R = np.zeros((g, S), dtype=np.float64)
+    A = _CUBIC_A
+    for d in range(n_out):
+        x = s * (d + 0.5) - 0.5
+        ix = math.floor(x)
+        t = x - ix
+        w = (((A * (t + 1) - 5 * A) * (t + 1) + 8 * A) * (t + 1) - 4 * A,
+             ((A + 2) * t - (A + 3)) * t * t + 1,
+             ((A + 2) * (1 - t) - (A + 3)) * (1 - t) * (1 - t) + 1,
+             ((A * (2 - t) - 5 * A) * (2 - t) + 8 * A) * (2 - t) - 4 * A)
+        for k in range(4):
+            R[d, min(max(ix - 1 + k, 0), S - 1)] += w[k]
+    return R
+
+
+def vit_pos_matrices(n_base, gh, gw, device):
+    """(Ry fp32 [gh, S], Rx fp32 [gw, S]) of vit_pos_resample, built on the host in fp64 once per (S, gh, gw, device)"""
+    S = int(math.sqrt(n_base))
+    key = (S, n_base, gh, gw, str(device))
+    m = _VIT_POS.get(key)
+    if m is None:
+        m = _VIT_POS[key] = tuple(torch.from_numpy(vit_pos_axis_matrix(S, n_base, g)).float().to(device) for g in (gh, gw))
+    return m
+
+
+def vit_pos_resample(pos_embed, gh, gw):
+    """the position embedding [1, 1 + N, C] of an S x S patch grid (S = int(sqrt(N))) on a gh x gw grid -> [1, 1 + gh * gw, C], patch
+    rows first, the class-token entry passed through.  The reference's forward_selfattention (vision_transformer.py:296-312): bicubic
+    F.interpolate with the scale-factor tuple (gh / sqrt(N), gw / sqrt(N)), then zero rows / columns where floor(S * sf) falls short of
+    the grid (at side 61 from S = 14 or 28, and nowhere else up to 80).  The reference's second pad (:308-310, short columns) assigns
+    its result to a name nobody reads and then fails in the add; what it evidently means, zero columns, is built here.
+
+    The map is separable, pos_r = Ry pos Rx^T per channel, so forward and backward are two small fp32 matrix products each, without
+    atomics: the gradient of pos_embed comes out with the same bits on every pass."""
+    N, C = pos_embed.shape[1] - 1, pos_embed.shape[2]
+    S = int(math.sqrt(N))
+    Ry, Rx = vit_pos_matrices(N, gh, gw, pos_embed.device)
+    rows = torch.matmul(Ry, pos_embed[0, 1:].reshape(S, S * C)).view(gh, S, C)   # [gh, S, C]
+    grid = torch.matmul(Rx, rows)                                                # [gw, S] @ [gh, S, C] -> [gh, gw, C]
+    return torch.cat((pos_embed[:, :1], grid.reshape(1, gh * gw, C)), dim=1)
 
 
 VIT_WINDOW_TOKENS = 224  # crops of at most this many tokens run through the fused windowed kernels (one "window" per image)

@@ -5,7 +5,8 @@ As for Swin, the module tree only HOLDS parameters -- names, shapes, registratio
 state_dicts are interchangeable -- and every forward runs esvit_amd.functional: one autograd node per block (LayerNorm, the four
 GEMMs with fused epilogues, global attention over the 197 / 37 tokens of a crop on the batched GEMM family + a row softmax, csrc/
 vit_attn.hip).  The class token / position embedding (with the reference's bicubic interpolation for the 96^2 crops) are small
-torch tensor ops.
+torch tensor ops.  Images need not be square: an H x W image gives an (H / patch) x (W / patch) grid of patch tokens, and the position
+embedding is resampled to that grid as the reference's forward_selfattention does (functional.vit_pos_resample).
 """
 import math
 from functools import partial
@@ -80,6 +81,12 @@ class PatchEmbed(nn.Module):
         self.proj = nn.Conv2d(in_chans, embed_dim, kernel_size=patch_size, stride=patch_size)
 
     def forward(self, x):
+        """[B, 3, H, W] -> [B, (H // patch) * (W // patch), E].  A rectangular image is cropped to whole patches first, which is what
+        the reference's strided convolution does by not reaching the rest; square images go on as they are."""
+        H, W = x.shape[-2:]
+        if H != W:
+            P = self.patch_size
+            x = x[..., :H // P * P, :W // P * P]
         return Fn.VitPatchEmbedFn.apply(x, self.proj.weight, self.proj.bias, self.patch_size)
 
 
@@ -136,14 +143,15 @@ class VisionTransformer(nn.Module):
         return torch.cat((pos_embed[:, :1], grid.permute(0, 2, 3, 1).reshape(1, -1, dim)), dim=1)
 
     def _tokens(self, x):
-        """patches -> [class token | patch tokens] + position embedding (vision_transformer.py:236-243)"""
-        if x.shape[-1] != x.shape[-2]:
-            raise NotImplementedError("VisionTransformer: square images only (got %dx%d): the patch embedding and the position-embedding "
-                                      "interpolation here assume a square patch grid; the reference's (w0, h0) resampling of "
-                                      "vision_transformer.py:236-262 for other shapes is not built" % (x.shape[-2], x.shape[-1]))
+        """patches -> [class token | patch tokens] + position embedding (vision_transformer.py:236-243).  Square images take the
+        reference's scalar-scale interpolation above; any other shape its (w0, h0) resampling (vision_transformer.py:296-312)."""
+        H, W = x.shape[-2:]
         patches = self.patch_embed(x)
         x = torch.cat((self.cls_token.expand(patches.shape[0], -1, -1), patches), dim=1)
-        return Fn.ApeAddFn.apply(x, self.interpolate_pos_encoding(x, self.pos_embed).contiguous())
+        if H == W:
+            return Fn.ApeAddFn.apply(x, self.interpolate_pos_encoding(x, self.pos_embed).contiguous())
+        P = self.patch_embed.patch_size
+        return Fn.ApeAddFn.apply(x, Fn.vit_pos_resample(self.pos_embed, H // P, W // P).contiguous())
 
     def _normed(self, x):
         return Fn.FinalNormFn.apply(x, self.norm.weight, self.norm.bias)
@@ -206,7 +214,7 @@ class VisionTransformer(nn.Module):
         crops = x if isinstance(x, list) else [x]
         runs, start = [], 0
         for i in range(1, len(crops) + 1):
-            if i == len(crops) or crops[i].shape[-1] != crops[start].shape[-1]:
+            if i == len(crops) or crops[i].shape[-2:] != crops[start].shape[-2:]:  # a run: neighbours of equal (H, W)
                 runs.append(torch.cat(crops[start:i]))
                 start = i
         if self.ragged_multi_crop and len(runs) > 1:
@@ -228,8 +236,10 @@ class VisionTransformer(nn.Module):
 
     # ---- evaluation hooks (vision_transformer.py:279-362) ---------------------------------------------------------------
     def forward_selfattention(self, x, n=1):
-        """attention probabilities of the last block (n = 1) or of every block; images whose sides are multiples of the patch
-        size (the reference's zero-padding branch for other sizes is not needed by its own callers)"""
+        """attention probabilities of the last block (n = 1) or of every block: [B, nH, N, N] with N = 1 + (H // patch) * (W // patch),
+        or the list of them.  H and W need not be equal (vision_transformer.py:287-322; a rectangle is cropped to whole patches, its
+        position grid comes from functional.vit_pos_resample, zero lines at side 61 included); a square image keeps the route of
+        `forward`, so its sides must be multiples of the patch size."""
         x = self._tokens(x)
         maps = []
         for i, blk in enumerate(self.blocks):

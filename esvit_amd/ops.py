@@ -685,18 +685,23 @@ def cast_to_act(x, dtype=None, out=None):
 
 
 
+PATCH_IM2COL_RECT = True  # patch_im2col takes [nB, 3, H, W] with H != W (esvit_patch_im2col's packed form of S)
+
+
 def patch_im2col(img, P, Kpad, dtype=None, out=None):
+    """img fp32 [nB, 3, H, W] -> cols [nB * (H/P) * (W/P), Kpad], column order (c, ph, pw).  A square image goes in the library's plain
+    form (S = the side), a rectangle as S = H | W << 16 (include/esvit_hip.h)."""
     img = _f32c(img)
-    nB, ch, S, S2 = img.shape
-    assert ch == 3 and S == S2
+    nB, ch, H, W = img.shape
+    assert ch == 3 and 0 < H < 65536 and 0 < W < 32768, tuple(img.shape)
     dt = dtype or _ACT_DTYPE
-    G = S // P
+    rows = nB * (H // P) * (W // P)
     if out is not None:
-        assert out.shape == (nB * G * G, Kpad) and out.dtype == dt and out.is_contiguous()
+        assert out.shape == (rows, Kpad) and out.dtype == dt and out.is_contiguous()
         cols = out
     else:
-        cols = torch.empty((nB * G * G, Kpad), dtype=dt, device=img.device)
-    check(lib.esvit_patch_im2col(_code(dt), _p(img), _p(cols), nB, S, P, Kpad, _stream()), "patch_im2col")
+        cols = torch.empty((rows, Kpad), dtype=dt, device=img.device)
+    check(lib.esvit_patch_im2col(_code(dt), _p(img), _p(cols), nB, H if H == W else (H | (W << 16)), P, Kpad, _stream()), "patch_im2col")
     return cols
 
 

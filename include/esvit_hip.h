@@ -293,8 +293,13 @@ int esvit_cast_f32_to(int dtype, const float* src, void* dst, int64_t n, esvit_s
 int esvit_colsum(int dtype, const void* x, int64_t rows, int N, int64_t ld, float* out, float* ws,
                  int accumulate, esvit_stream_t stream);
 
-/* PatchEmbed im2col for the 4x4/4 conv (swin_transformer.py:531,544): img fp32 NCHW [nB,3,S,S]
- * -> cols dtype [nB*(S/P)^2, Kpad], column order (c, ph, pw), zero padded to Kpad. */
+/* PatchEmbed im2col for the 4x4/4 conv (swin_transformer.py:531,544) and the ViT patch embedding
+ * (vision_transformer.py:121-139): img fp32 NCHW [nB,3,H,W] -> cols dtype [nB*(H/P)*(W/P), Kpad],
+ * rows (image, patch row, patch column), column order (c, ph, pw), zero padded to Kpad.
+ * S < 65536: a square image, H = W = S.  Otherwise S carries a rectangle: H = S & 0xffff (rows),
+ * W = S >> 16 (columns); a square image in this form gives the same bits as the plain call.
+ * ESVIT_ERR_ARG before any launch unless P % 4 == 0, H % P == 0, W % P == 0, H > 0, W > 0,
+ * Kpad % 8 == 0 and Kpad >= 3*P*P. */
 int esvit_patch_im2col(int dtype, const float* img, void* cols, int nB, int S, int P, int Kpad,
                        esvit_stream_t stream);
 /* PatchMerging gather + LayerNorm(4C) (swin_transformer.py:410-417): x fp32 [nB,H,W,C] ->
