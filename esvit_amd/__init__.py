@@ -14,6 +14,7 @@ os.environ.setdefault("HIP_FORCE_DEV_KERNARG", "1")
 
 import torch  # noqa: E402
 
+from .determinism import is_deterministic, set_deterministic  # noqa: F401,E402  (ESVIT_DETERMINISTIC; a bad value raises)
 from . import _lib  # noqa: F401  (raises if libesvit_hip.so is missing -- there is no fallback)
 from . import models, ops  # noqa: F401
 from . import analysis  # noqa: F401,E402  (attention entropy / rows / correspondence measurements)

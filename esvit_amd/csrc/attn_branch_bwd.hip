@@ -35,6 +35,7 @@
 //   HT, DYT [96][72] | H -> DAO -> AOT | DY -> DAOT | QKV -> DQKV [64][296] | QKVT -> DQKVT [288][72] | P^T -> dS^T 3 x [64][72] | row
 //   statistics = 163 328 bytes.
 #include "common.h"
+#include "relpos_fold.h"
 #include "../../include/esvit_hip.h"
 
 namespace {
@@ -541,43 +542,8 @@ __global__ __launch_bounds__(256) void attn_branch_bwd_reduce_kernel(const float
     else dbeta[i - P_BETA] = s;
 }
 
-// The table's gradient without atomics (esvit_relpos_bias_bwd scatters with atomicAdd: the same slabs give sums that differ in the last
-// bits from launch to launch).  First the slabs [0, nblk) are summed in index order, element by element, INTO slab 0 (each element is
-// read and written by one thread only); then table row t gathers its (query, key) pairs from that sum in query order.
-__global__ __launch_bounds__(256) void attn_branch_bwd_fold_kernel(float* __restrict__ dbias, int nblk) {
-    const int i = blockIdx.x * 256 + threadIdx.x;  // < BW_NH * BW_FRAG (the launch covers it exactly)
-    float* p = dbias + i;
-    constexpr long LD = (long)BW_NH * BW_FRAG;
-    float s = 0.f;
-    int b = 0;
-    for (; b + 8 <= nblk; b += 8) {
-        float v[8];
-#pragma unroll
-        for (int k = 0; k < 8; ++k) v[k] = p[(long)(b + k) * LD];
-#pragma unroll
-        for (int k = 0; k < 8; ++k) s += v[k];
-    }
-    for (; b < nblk; ++b) s += p[(long)b * LD];
-    p[0] = s;
-}
-
-__global__ __launch_bounds__(64) void attn_branch_bwd_table_kernel(const float* __restrict__ folded, const long* __restrict__ index, int N,
-                                                                   float* __restrict__ dtable) {
-    __shared__ int off[64];
-    const int t = blockIdx.x, q = threadIdx.x;
-    int o = -1;
-    if (q < N)
-        for (int key = 0; key < N; ++key)
-            if (index[q * N + key] == t) o = (((key >> 4) * 4 + (q >> 4)) * 64 + ((key & 15) >> 2) * 16 + (q & 15)) * 4 + (key & 3);  // (one key per query at most)
-    off[q] = o;
-    __syncthreads();
-    if (q < BW_NH) {
-        float s = 0.f;
-        for (int k = 0; k < N; ++k)
-            if (off[k] >= 0) s += folded[q * BW_FRAG + off[k]];
-        dtable[t * BW_NH + q] = s;
-    }
-}
+// The table's gradient without atomics (esvit_relpos_bias_bwd scatters with atomicAdd unless it is asked for ESVIT_RELPOS_ORDERED: the
+// same slabs give sums that differ in the last bits from launch to launch): the fold and the gather of relpos_fold.h.
 
 int bwd_grid(long windows) {
     static int cus[64] = {0};
@@ -631,10 +597,7 @@ int esvit_i_attn_branch_bwd(const float* x, const float* gamma, const float* bet
                            d->dbqkv, d->dbproj, d->dgamma, d->dbeta);
         ESVIT_CHECK_LAUNCH("esvit_attn_branch_fwd(backward reduce)");
         if (d->dtable) {
-            hipLaunchKernelGGL(attn_branch_bwd_fold_kernel, dim3(BW_NH * BW_FRAG / 256), dim3(256), 0, stream, d->dbias_ws, d->finish);
-            ESVIT_CHECK_LAUNCH("esvit_attn_branch_fwd(backward bias fold)");
-            hipLaunchKernelGGL(attn_branch_bwd_table_kernel, dim3(d->table_rows), dim3(64), 0, stream, (const float*)d->dbias_ws, (const long*)d->index, N,
-                               d->dtable);
+            relpos_ordered_launch(d->dbias_ws, d->finish, 4, d->index, N, BW_NH, d->table_rows, d->dtable, 0, stream);
             ESVIT_CHECK_LAUNCH("esvit_attn_branch_fwd(backward table)");
         }
     }

@@ -22,7 +22,9 @@ constexpr int CHUNK = 4096;
 constexpr int TFIELDS = 12;
 
 // STATS 1: sqnorms[t] = sum g^2;  STATS 3: sqnorms[3t..3t+2] = (sum g^2, sum p^2, sum g p)
-template <int STATS>
+// ORDERED (ESVIT_SQNORM_ORDERED): the chunk's partial goes to `sqnorms` + blockIdx.x * STATS instead (the caller passes the tail of
+// the buffer), for grad_sqnorm_fold_kernel; a chunk of a tensor without gradient writes nothing, its tensor's fold reads nothing.
+template <int STATS, bool ORDERED = false>
 __global__ __launch_bounds__(256) void grad_sqnorm_kernel(const long* __restrict__ tensors, const int* __restrict__ chunks,
                                                           float* __restrict__ sqnorms) {
     __shared__ float scratch[4];
@@ -56,6 +58,19 @@ __global__ __launch_bounds__(256) void grad_sqnorm_kernel(const long* __restrict
         }
     }
     s = block_sum<256>(s, scratch);
+    if constexpr (ORDERED) {
+        float* out = sqnorms + (long)blockIdx.x * STATS;
+        if (threadIdx.x == 0) out[0] = s;
+        if constexpr (STATS == 3) {
+            __syncthreads();
+            sp = block_sum<256>(sp, scratch);
+            if (threadIdx.x == 0) out[1] = sp;
+            __syncthreads();
+            sgp = block_sum<256>(sgp, scratch);
+            if (threadIdx.x == 0) out[2] = sgp;
+        }
+        return;
+    }
     if (threadIdx.x == 0) atomicAdd(sqnorms + (long)tid * STATS, s);
     if constexpr (STATS == 3) {
         __syncthreads();
@@ -64,6 +79,41 @@ __global__ __launch_bounds__(256) void grad_sqnorm_kernel(const long* __restrict
         __syncthreads();
         sgp = block_sum<256>(sgp, scratch);
         if (threadIdx.x == 0) atomicAdd(sqnorms + (long)tid * 3 + 2, sgp);
+    }
+}
+
+// Second launch of the ordered statistics: workgroup t folds the partials of tensor t, whose chunk-table entries are contiguous (the
+// table is sorted by tensor id): thread j adds the partials j, j + 256, ... in chunk order, then the block's fixed tree.  One writer
+// per statistic; a tensor without gradient (or without chunks) gets 0.
+template <int STATS>
+__global__ __launch_bounds__(256) void grad_sqnorm_fold_kernel(const long* __restrict__ tensors, const int* __restrict__ chunks, int nchunks,
+                                                               const float* __restrict__ partials, float* __restrict__ sqnorms) {
+    __shared__ float scratch[4];
+    const int t = blockIdx.x;
+    int lo = 0, hi = 0;
+    if (tensors[(long)t * TFIELDS + 7] & 1) {
+        // first entries with tensor id >= t and >= t + 1
+        int a = 0, b = nchunks;
+        while (a < b) {
+            const int m = (a + b) >> 1;
+            if (chunks[2 * m] < t) a = m + 1;
+            else b = m;
+        }
+        lo = a;
+        b = nchunks;
+        while (a < b) {
+            const int m = (a + b) >> 1;
+            if (chunks[2 * m] <= t) a = m + 1;
+            else b = m;
+        }
+        hi = a;
+    }
+#pragma unroll
+    for (int k = 0; k < STATS; ++k) {
+        float s = 0.f;
+        for (int i = lo + (int)threadIdx.x; i < hi; i += 256) s += partials[(long)i * STATS + k];
+        s = block_sum<256>(s, scratch);
+        if (threadIdx.x == 0) sqnorms[(long)t * STATS + k] = s;
     }
 }
 
@@ -287,7 +337,19 @@ int esvit_i_update_chunk_elems() { return CHUNK; }  // esvit_query
 extern "C" int esvit_grad_sqnorm(const int64_t* tensors, int ntensors, const int32_t* chunks, int nchunks, int stats, float* sqnorms,
                                  esvit_stream_t s_) {
     hipStream_t stream = reinterpret_cast<hipStream_t>(s_);
+    const bool ordered = (stats & ESVIT_SQNORM_ORDERED) != 0;
+    if (ordered) stats &= ~ESVIT_SQNORM_ORDERED;
     ESVIT_CHECK_ARG(tensors && chunks && sqnorms && ntensors > 0 && nchunks > 0 && (stats == 1 || stats == 3), "esvit_grad_sqnorm: bad args");
+    if (ordered) {
+        float* tail = sqnorms + (long)ntensors * stats;  // [nchunks * stats] partials
+        if (stats == 3) hipLaunchKernelGGL((grad_sqnorm_kernel<3, true>), dim3(nchunks), dim3(256), 0, stream, (const long*)tensors, chunks, tail);
+        else hipLaunchKernelGGL((grad_sqnorm_kernel<1, true>), dim3(nchunks), dim3(256), 0, stream, (const long*)tensors, chunks, tail);
+        ESVIT_CHECK_LAUNCH("grad_sqnorm(ordered)");
+        if (stats == 3) hipLaunchKernelGGL(grad_sqnorm_fold_kernel<3>, dim3(ntensors), dim3(256), 0, stream, (const long*)tensors, chunks, nchunks, (const float*)tail, sqnorms);
+        else hipLaunchKernelGGL(grad_sqnorm_fold_kernel<1>, dim3(ntensors), dim3(256), 0, stream, (const long*)tensors, chunks, nchunks, (const float*)tail, sqnorms);
+        ESVIT_CHECK_LAUNCH("grad_sqnorm(ordered fold)");
+        return ESVIT_OK;
+    }
     hipError_t e = hipMemsetAsync(sqnorms, 0, (size_t)ntensors * stats * sizeof(float), stream);
     if (e != hipSuccess) {
         esvit_set_error("esvit_grad_sqnorm: memset failed: %s", hipGetErrorString(e));

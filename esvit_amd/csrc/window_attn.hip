@@ -19,6 +19,7 @@
 // all windows a wave processes and written once per wave to a partial slab (no atomics).
 #include "common.h"
 #include "mfma.h"
+#include "relpos_fold.h"
 #include "../../include/esvit_hip.h"
 
 namespace {
@@ -753,7 +754,7 @@ int esvit_i_relpos_fold(const float* dbias_ws, int parts, int nt, const int64_t*
     return ESVIT_OK;
 }
 
-extern "C" int esvit_relpos_bias_bwd(const float* dbias_ws, int parts, const int64_t* index, int N, int nH, int table_rows,
+extern "C" int esvit_relpos_bias_bwd(float* dbias_ws, int parts, const int64_t* index, int N, int nH, int table_rows,
                                      float* dtable, int accumulate, esvit_stream_t s_) {
     STREAM(s_);
     ESVIT_CHECK_ARG(dbias_ws && index && dtable && parts > 0 && N > 0 && N <= esvit_big_npb() && nH > 0 && table_rows > 0,
@@ -761,6 +762,13 @@ extern "C" int esvit_relpos_bias_bwd(const float* dbias_ws, int parts, const int
 #ifdef ESVIT_PROBE_SKIP_FINISH  // timing probe (WRONG gradients), see norm.hip
     return ESVIT_OK;
 #endif
+    if (accumulate & ESVIT_RELPOS_ORDERED) {
+        // one writer and one summation order per table element (relpos_fold.h): no memset, no atomics; slab 0 becomes the slabs' sum
+        relpos_ordered_launch(dbias_ws, parts, N > NP ? esvit_big_npb() / 16 : 4, index, N, nH, table_rows, dtable,
+                              (accumulate & ~ESVIT_RELPOS_ORDERED) != 0, stream);
+        ESVIT_CHECK_LAUNCH("relpos_bias_bwd(ordered)");
+        return ESVIT_OK;
+    }
     if (N > NP) return esvit_big_relpos_bias_bwd(dbias_ws, parts, index, N, nH, table_rows, dtable, accumulate, stream);
     hipError_t e = accumulate ? hipSuccess : hipMemsetAsync(dtable, 0, (size_t)table_rows * nH * sizeof(float), stream);
     if (e != hipSuccess) {

@@ -20,6 +20,7 @@ import torch
 
 from . import ops
 from . import params as P
+from .determinism import is_deterministic
 
 LN_EPS = 1e-6
 
@@ -33,6 +34,12 @@ def _no_dbias(o, N, hd):
     bias gradient is a kernel of its own (window_attn_big.hip), which such a caller leaves out.  Passed only where it changes something
     and to an ops module that knows it (the CPU restatement of the kernels computes the slabs in passing and has no such switch)"""
     return {"want_dbias": False} if N > 64 and hd == 64 and getattr(o, "ATTN_BWD_OPTIONAL_DBIAS", False) else {}
+
+
+def _relpos_kw(o):
+    """keyword of o.relpos_bias_bwd in the deterministic mode (esvit_amd.set_deterministic): the fixed-order table gradient without
+    atomics.  Passed only when the mode is on and to an ops module that knows it (the CPU restatement is deterministic anyway)"""
+    return {"ordered": True} if is_deterministic() and getattr(o, "RELPOS_BWD_ORDERED", False) else {}
 
 
 # ------------------------------------------------------------------------------------------------
@@ -403,7 +410,7 @@ class SwinBlockFn(torch.autograd.Function):
         dao = o.linear_dgrad(dyw, Wproj)
         dqkv, dbias_ws, dpad_ws = o.window_attn_bwd(qkv, bqkv, geom.win2tok, L, dao, ao, lse, None, geom.ws, geom.region_ids,
                                                     geom.nW, geom.N, nH, scale, bias_frag=frag)
-        dtable = o.relpos_bias_bwd(dbias_ws, index, geom.N, table.shape[0])
+        dtable = o.relpos_bias_bwd(dbias_ws, index, geom.N, table.shape[0], **_relpos_kw(o))
         dWqkv, dbqkv = _wgrad(dqkv, xw, Wqkv_p, want_bias=True)
         o.colsum(dpad_ws, out=dbqkv[C:], accumulate=True)  # k/v bias gradient from the zero-pad slots
         dxw = o.linear_dgrad(dqkv, Wqkv)
@@ -586,7 +593,7 @@ class SwinBlockMultiFn(torch.autograd.Function):
             _, _, dpad_ws = o.window_attn_bwd(qkv[r0:r1], bqkv, geom.win2tok, L, dao[r0:r1], ao[r0:r1], lse, None, geom.ws, geom.region_ids,
                                               geom.nW, geom.N, nH, scale, dqkv_out=dqkv[r0:r1], bias_frag=frag, dbias_out=dslab)
             pads.append(dpad_ws)
-        dtable = o.relpos_bias_bwd(dbuf, index, N, table.shape[0], out=tsink, accumulate=False if tsink is not None else None)
+        dtable = o.relpos_bias_bwd(dbuf, index, N, table.shape[0], out=tsink, accumulate=False if tsink is not None else None, **_relpos_kw(o))
         dtable = _alias(dtable, tsink)
         wsink, bsink = P.grad_out(Wqkv_p), P.grad_out(bqkv_p)
 
@@ -1392,7 +1399,7 @@ class CvtAttnFn(torch.autograd.Function):
         regions = geometry(Hp, Wp, w, w // 2, x.device).region_ids if shift else None
         dqkv, dbias_ws, _ = o.window_attn_bwd(qkv, pw_b, geom.win2tok, Hp * Wp, dao, ao, lse, table, w, regions, geom.nW, geom.N, nH, scale,
                                               **({} if has_table else _no_dbias(o, geom.N, C // nH)))
-        dtable = o.relpos_bias_bwd(dbias_ws, index, geom.N, table.shape[0]) if has_table else None
+        dtable = o.relpos_bias_bwd(dbias_ws, index, geom.N, table.shape[0], **_relpos_kw(o)) if has_table else None
         dWpw, dbpw = _side_run(lambda: o.linear_wgrad(dqkv, bnout, want_bias=True), dqkv, bnout)
         dbn = o.linear_dgrad(dqkv, Wpw)
         # BatchNorm backward: d(d) = gamma rstd (dy - mean(dy) - xhat mean(dy xhat)), xhat = (d - mean) rstd
@@ -1622,9 +1629,10 @@ class CvtAttnMultiFn(torch.autograd.Function):
                                                nH, scale, dqkv_out=dqkv[p0:p1], **({} if has_table else _no_dbias(o, geom.N, C // nH)))
             if has_table:  # the first group writes the table gradient (its bucket slot when there is one), later groups add to it
                 if i == 0:
-                    dtable = o.relpos_bias_bwd(dbias_ws, index, geom.N, tables[i].shape[0], out=tsink, accumulate=False if tsink is not None else None)
+                    dtable = o.relpos_bias_bwd(dbias_ws, index, geom.N, tables[i].shape[0], out=tsink, accumulate=False if tsink is not None else None,
+                                                  **_relpos_kw(o))
                 else:
-                    o.relpos_bias_bwd(dbias_ws, index, geom.N, tables[i].shape[0], out=dtable, accumulate=True)
+                    o.relpos_bias_bwd(dbias_ws, index, geom.N, tables[i].shape[0], out=dtable, accumulate=True, **_relpos_kw(o))
         if has_table:
             dtable = _alias(dtable, tsink)
         dWpw, dbpw = _side_run(lambda: _wgrad(dqkv, bnout, pw_Wp, (3 * C, C), want_bias=True, bias_param=pw_b_p), dqkv, bnout)
@@ -1820,13 +1828,15 @@ _VIT_POS = {}
 _CUBIC_A = -0.75
 
 
-def vit_pos_axis_matrix(S, n_base, g):
+def vit_pos_axis_matrix(S, n_base, g, sf=None):
     """one axis of torch's F.interpolate(mode="bicubic", scale_factor=g / sqrt(n_base)) from S lines to g, as a matrix: fp64 [g, S].
+    sf: the scale factor where the caller computes it another way (the square call's sqrt(g * g / n_base)).
     Output line d < floor(S * sf) reads the source coordinate x = s (d + 0.5) - 0.5 with s the FLOAT32 value of 1 / sf (torch hands the
     kernel the scale factor, not the size ratio; align_corners False), four taps around floor(x) weighted by the cubic convolution
     kernel with A = -0.75, taps outside the grid clamped to the border.  Lines floor(S * sf) .. g - 1 are zero rows."""
     import numpy as np
-    sf = g / math.sqrt(n_base)
+    if sf is None:
+        sf = g / math.sqrt(n_base)
     n_out = min(g, int(math.floor(S * sf)))
     s = float(np.float32(1.0 / sf))
     R = np.zeros((g, S), dtype=np.float64)
@@ -1844,17 +1854,19 @@ def vit_pos_axis_matrix(S, n_base, g):
     return R
 
 
-def vit_pos_matrices(n_base, gh, gw, device):
-    """(Ry fp32 [gh, S], Rx fp32 [gw, S]) of vit_pos_resample, built on the host in fp64 once per (S, gh, gw, device)"""
+def vit_pos_matrices(n_base, gh, gw, device, square=False):
+    """(Ry fp32 [gh, S], Rx fp32 [gw, S]) of vit_pos_resample, built on the host in fp64 once per (S, gh, gw, device).
+    square: gh == gw and both axes take the scale factor of the square call, sqrt(gh * gw / n_base) (interpolate_pos_encoding)"""
     S = int(math.sqrt(n_base))
-    key = (S, n_base, gh, gw, str(device))
+    key = (S, n_base, gh, gw, str(device), bool(square))
     m = _VIT_POS.get(key)
     if m is None:
-        m = _VIT_POS[key] = tuple(torch.from_numpy(vit_pos_axis_matrix(S, n_base, g)).float().to(device) for g in (gh, gw))
+        sf = math.sqrt(gh * gw / n_base) if square else None
+        m = _VIT_POS[key] = tuple(torch.from_numpy(vit_pos_axis_matrix(S, n_base, g, sf)).float().to(device) for g in (gh, gw))
     return m
 
 
-def vit_pos_resample(pos_embed, gh, gw):
+def vit_pos_resample(pos_embed, gh, gw, square=False):
     """the position embedding [1, 1 + N, C] of an S x S patch grid (S = int(sqrt(N))) on a gh x gw grid -> [1, 1 + gh * gw, C], patch
     rows first, the class-token entry passed through.  The reference's forward_selfattention (vision_transformer.py:296-312): bicubic
     F.interpolate with the scale-factor tuple (gh / sqrt(N), gw / sqrt(N)), then zero rows / columns where floor(S * sf) falls short of
@@ -1862,10 +1874,14 @@ def vit_pos_resample(pos_embed, gh, gw):
     its result to a name nobody reads and then fails in the add; what it evidently means, zero columns, is built here.
 
     The map is separable, pos_r = Ry pos Rx^T per channel, so forward and backward are two small fp32 matrix products each, without
-    atomics: the gradient of pos_embed comes out with the same bits on every pass."""
+    atomics: the gradient of pos_embed comes out with the same bits on every pass.
+
+    square (gh == gw): the scalar-scale call of a square crop instead, F.interpolate(scale_factor=sqrt(gh * gw / N)), which the
+    deterministic mode routes here (torch's bicubic backward scatters with atomics)."""
     N, C = pos_embed.shape[1] - 1, pos_embed.shape[2]
     S = int(math.sqrt(N))
-    Ry, Rx = vit_pos_matrices(N, gh, gw, pos_embed.device)
+    assert not square or gh == gw, (gh, gw)
+    Ry, Rx = vit_pos_matrices(N, gh, gw, pos_embed.device, square=square)
     rows = torch.matmul(Ry, pos_embed[0, 1:].reshape(S, S * C)).view(gh, S, C)   # [gh, S, C]
     grid = torch.matmul(Rx, rows)                                                # [gw, S] @ [gh, S, C] -> [gh, gw, C]
     return torch.cat((pos_embed[:, :1], grid.reshape(1, gh * gw, C)), dim=1)

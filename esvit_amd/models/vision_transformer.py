@@ -15,6 +15,7 @@ import torch
 import torch.nn as nn
 
 from .. import functional as Fn
+from ..determinism import is_deterministic
 from ..head import DINOHead  # noqa: F401  (the reference exports it from this module)
 from .swin_transformer import DropPath, Mlp, _trunc_normal_
 
@@ -144,13 +145,17 @@ class VisionTransformer(nn.Module):
 
     def _tokens(self, x):
         """patches -> [class token | patch tokens] + position embedding (vision_transformer.py:236-243).  Square images take the
-        reference's scalar-scale interpolation above; any other shape its (w0, h0) resampling (vision_transformer.py:296-312)."""
+        reference's scalar-scale interpolation above -- in the deterministic mode (esvit_amd.set_deterministic) the same interpolation as
+        matrix products, whose backward has no atomics; any other shape its (w0, h0) resampling (vision_transformer.py:296-312)."""
         H, W = x.shape[-2:]
         patches = self.patch_embed(x)
         x = torch.cat((self.cls_token.expand(patches.shape[0], -1, -1), patches), dim=1)
-        if H == W:
-            return Fn.ApeAddFn.apply(x, self.interpolate_pos_encoding(x, self.pos_embed).contiguous())
         P = self.patch_embed.patch_size
+        if H == W:
+            if is_deterministic() and x.shape[1] != self.pos_embed.shape[1]:
+                # torch's bicubic backward scatters with float atomics: the same interpolation as two small matrix products
+                return Fn.ApeAddFn.apply(x, Fn.vit_pos_resample(self.pos_embed, H // P, W // P, square=True).contiguous())
+            return Fn.ApeAddFn.apply(x, self.interpolate_pos_encoding(x, self.pos_embed).contiguous())
         return Fn.ApeAddFn.apply(x, Fn.vit_pos_resample(self.pos_embed, H // P, W // P).contiguous())
 
     def _normed(self, x):

@@ -853,7 +853,7 @@ def attn_branch_bwd(x, gin, gamma, beta, eps, weights, bqkv, win2tok, L, ws, reg
     gradients to (each or any None).  workspaces = (partials_ws, dbias_ws) of attn_branch_bwd_workspaces with this call's first_partial;
     finish=False leaves the reduce to a later call of the same block (the gradients are then not yet written), finish=True sums every
     partial up to and including this call's.  index (the relative-position index) with table_rows, or a dtable fp32 [table_rows, nH] to write
-    to: the finishing call also sums the slabs and gathers the table's gradient, without atomics (bit-reproducible, unlike relpos_bias_bwd,
+    to: the finishing call also sums the slabs and gathers the table's gradient, without atomics (bit-reproducible, unlike relpos_bias_bwd without ordered=True,
     which the slabs may go to instead).  gx_out / gx_act_out: row slices of a block's matrices
     to write gx / gx_act to."""
     x, gin = _f32c(x), _f32c(gin)
@@ -950,17 +950,24 @@ def window_attn_bwd(qkv, qkv_bias, win2tok, L, dout, fwd_out, lse, rel_table, ws
     return dqkv, dbias_ws, pad
 
 
-def relpos_bias_bwd(dbias_ws, index, N, table_rows, out=None, accumulate=None):
+RELPOS_ORDERED = 0x100  # ESVIT_RELPOS_ORDERED: OR'd into accumulate of esvit_relpos_bias_bwd
+RELPOS_BWD_ORDERED = True  # relpos_bias_bwd takes ordered (functional._relpos_kw)
+
+
+def relpos_bias_bwd(dbias_ws, index, N, table_rows, out=None, accumulate=None, ordered=False):
     """out: optional fp32 [table_rows, nH]; accumulate (default: True when out is given -- the second resolution group of a
-    ragged block) adds to it, False overwrites it (a gradient-bucket slot written for the first time)"""
+    ragged block) adds to it, False overwrites it (a gradient-bucket slot written for the first time).
+    ordered: the fixed-order form without atomics (bit-reproducible); it leaves the slabs' sum in dbias_ws[0]"""
     parts, nH, _ = dbias_ws.shape
     if index.shape[-1] != N:  # N < ws^2 (a ViT crop on the first N positions of the grid): the kernel reads index[q * N + key]
         index = index[:N, :N].contiguous()
     assert index.dtype == torch.int64 and index.is_contiguous() and tuple(index.shape) == (N, N), (index.dtype, index.shape, N)
     dtable = torch.empty((table_rows, nH), dtype=torch.float32, device=dbias_ws.device) if out is None else _f32c(out)
     acc = (out is not None) if accumulate is None else (bool(accumulate) and out is not None)
-    check(lib.esvit_relpos_bias_bwd(_p(dbias_ws), parts, _p(index), N, nH, table_rows, _p(dtable), int(acc), _stream()),
-          "relpos_bias_bwd")
+    if ordered:
+        _f32c(dbias_ws)
+    check(lib.esvit_relpos_bias_bwd(_p(dbias_ws), parts, _p(index), N, nH, table_rows, _p(dtable), int(acc) | (RELPOS_ORDERED if ordered else 0),
+                                    _stream()), "relpos_bias_bwd")
     return dtable
 
 
@@ -1118,8 +1125,16 @@ def update_chunk_elems():
 RULE_ADAMW, RULE_SGD, RULE_LARS, RULE_SGD_MEMBERS = 0, 1, 2, 3
 
 
-def grad_sqnorm(tensors, ntensors, chunks, nchunks, sqnorms, stats=1):
-    check(lib.esvit_grad_sqnorm(_p(tensors), ntensors, _p(chunks), nchunks, int(stats), _p(sqnorms), _stream()), "grad_sqnorm")
+SQNORM_ORDERED = 0x100  # ESVIT_SQNORM_ORDERED: OR'd into stats of esvit_grad_sqnorm
+
+
+def grad_sqnorm(tensors, ntensors, chunks, nchunks, sqnorms, stats=1, ordered=False):
+    """ordered: the fixed-order form without atomics (bit-reproducible); sqnorms is then fp32 [ntensors * stats + nchunks * stats],
+    the statistics in its head, per-chunk partials behind them"""
+    if ordered:
+        assert sqnorms.dtype == torch.float32 and sqnorms.is_contiguous() and sqnorms.numel() >= (ntensors + nchunks) * int(stats), sqnorms.shape
+    check(lib.esvit_grad_sqnorm(_p(tensors), ntensors, _p(chunks), nchunks, int(stats) | (SQNORM_ORDERED if ordered else 0), _p(sqnorms), _stream()),
+          "grad_sqnorm")
 
 
 def fused_clip_update_ema(rule, tensors, ntensors, chunks, nchunks, sqnorms, clip, lr, wd, beta1, beta2, eps, ema_m, skipped=None):

@@ -12,6 +12,7 @@ import torch
 
 from . import ops
 from . import params as P
+from .determinism import is_deterministic
 
 TFIELDS = 12
 
@@ -82,7 +83,9 @@ class FusedClipAdamWEMA:
                 chunks.append((ti, ci))
         self.nchunks = len(chunks)
         self.chunks = torch.tensor(chunks, dtype=torch.int32).to(dev)
-        self.sqnorms = torch.zeros(len(self.params) * (3 if rule == "lars" else 1), dtype=torch.float32, device=dev)
+        # (the deterministic mode appends nchunks * stats per-chunk partials: esvit_grad_sqnorm | ESVIT_SQNORM_ORDERED)
+        self.sqnorms = torch.zeros((len(self.params) + (self.nchunks if is_deterministic() else 0)) * (3 if rule == "lars" else 1), dtype=torch.float32,
+                                   device=dev)
         # updates the kernel refused (a non-finite gradient statistic): counted on the device, collected by take_skipped()
         self.skipped = torch.zeros(1, dtype=torch.int32, device=dev)
         self._skipped_seen = 0
@@ -160,7 +163,14 @@ class FusedClipAdamWEMA:
         ev.record()
         self._ring_ev[slot] = ev
         n = len(self.params)
-        ops.grad_sqnorm(self._table_dev, n, self.chunks, self.nchunks, self.sqnorms, stats=3 if self.rule == "lars" else 1)
+        stats = 3 if self.rule == "lars" else 1
+        if is_deterministic():
+            # fixed-order statistics (no float atomics): the per-chunk partials live behind the statistics, which keep their layout
+            if self.sqnorms.numel() < (n + self.nchunks) * stats:
+                self.sqnorms = torch.zeros((n + self.nchunks) * stats, dtype=torch.float32, device=self.device)
+            ops.grad_sqnorm(self._table_dev, n, self.chunks, self.nchunks, self.sqnorms, stats=stats, ordered=True)
+        else:
+            ops.grad_sqnorm(self._table_dev, n, self.chunks, self.nchunks, self.sqnorms, stats=stats)
         if self.rule == "adamw":
             rule, h1, h2 = ops.RULE_ADAMW, b1, b2
         else:

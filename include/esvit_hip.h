@@ -356,7 +356,7 @@ int esvit_token_mean_bwd(const float* g_mean, const float* g_tok, int nB, int T,
  *   112 index          int64 [N*N] relative-position index, 120 dtable fp32 [table_rows, nH], 128 table_rows: optional, all or none.  With
  *                      them the finishing call also writes the table's gradient (overwritten) WITHOUT atomics: the slabs [0, n) are
  *                      summed in index order into slab 0, whose sum the table's rows then gather in query order -- identical launches give
- *                      identical bits, which esvit_relpos_bias_bwd (an atomicAdd scatter) does not.  dtable = NULL: the slabs are left for
+ *                      identical bits, which esvit_relpos_bias_bwd (an atomicAdd scatter) does only with ESVIT_RELPOS_ORDERED.  dtable = NULL: the slabs are left for
  *                      esvit_relpos_bias_bwd(dbias_ws, n, ...)
  * Every misuse returns ESVIT_ERR_ARG before any launch. */
 typedef struct esvit_attn_bwd_desc {
@@ -483,8 +483,18 @@ int esvit_window_attn_bwd(int dtype, const void* qkv, const float* qkv_bias, con
                           float* bias_frag_ws, const int32_t* region_ids, int nW, int nB, int N, int nH, int hd,
                           float scale, void* dqkv, float* dbias_ws, float* dpad_ws, esvit_stream_t stream);
 /* dtable fp32 [table_rows, nH] (overwritten, or added to when accumulate != 0: the second resolution group of a ragged
- * multi-crop block) = scatter-add over index of sum_parts dbias_ws */
-int esvit_relpos_bias_bwd(const float* dbias_ws, int parts, const int64_t* index, int N, int nH,
+ * multi-crop block) = scatter-add over index of sum_parts dbias_ws.  The scatter is one float atomicAdd per (query, key, head): the
+ * same slabs give sums that differ in the last bits from launch to launch, and dbias_ws is left as it was.
+ * accumulate | ESVIT_RELPOS_ORDERED (the remaining bits keep their meaning: non-zero adds to dtable): every table element has ONE
+ * writer and ONE summation order, for N <= 64 and for 64 < N <= 224 alike, no atomics, no memset, no dependence on the grid's
+ * schedule -- identical launches give identical bits.  The order: (1) the slabs [0, parts) are summed per frag-layout element in
+ * slab order, s = (((0 + slab_0) + slab_1) + ...), INTO slab 0 of dbias_ws: afterwards slab 0 holds the sum and slabs 1.. are
+ * untouched (so the call cannot be repeated on the same slabs unless parts = 1); (2) table row t, head h adds its (query, key)
+ * pairs {index[q * N + key] == t} to one accumulator that starts at 0, in ascending (query, key) order; (3) the element is written,
+ * or added ONCE to dtable's value.  index may hold anything: a row without pairs gets 0 (or keeps its value), entries outside
+ * [0, table_rows) are ignored. */
+#define ESVIT_RELPOS_ORDERED 0x100
+int esvit_relpos_bias_bwd(float* dbias_ws, int parts, const int64_t* index, int N, int nH,
                           int table_rows, float* dtable, int accumulate, esvit_stream_t stream);
 
 /* ---- DINOHead pieces (vision_transformer.py:414-418) -------------------- */
@@ -573,7 +583,18 @@ int esvit_center_ema(float* center, const float* colsum, float momentum, float d
  * chunk table (device, int32[nchunks*2]): [tensor_id, chunk_index], chunk =
  * esvit_query(ESVIT_Q_UPDATE_CHUNK_ELEMS, 0, 0, 0) elements.
  * esvit_grad_sqnorm: stats = 1: sqnorms fp32 [ntensors] = sum g^2;  stats = 3 (LARS): fp32 [ntensors*3] =
- * (sum g^2, sum p^2, sum g p) per tensor.  esvit_fused_clip_update_ema reads the layout its rule needs.
+ * (sum g^2, sum p^2, sum g p) per tensor.  esvit_fused_clip_update_ema reads the layout its rule needs.  Every chunk adds its
+ * partial with a float atomicAdd: the statistic differs in the last bits from launch to launch.
+ * stats | ESVIT_SQNORM_ORDERED (stats & 0xff in {1, 3} as above; any other value is ESVIT_ERR_ARG): no atomics and no memset --
+ * sqnorms is then fp32 [ntensors * stats + nchunks * stats]: the head has the layout above (esvit_fused_clip_update_ema reads it
+ * unchanged), the tail is scratch: chunk-table entry i writes its partial to tail[i * stats ..].  The chunk table must be sorted
+ * by (tensor_id, chunk_index), which is how it is built anyway.  Summation order of one statistic: a thread adds its 16 products
+ * in address order (four float4 of four), the 256 threads of the chunk are summed by a butterfly over the 64 lanes and then over the
+ * four waves in wave order; a second launch (one workgroup per tensor) folds the tensor's partials: thread j of 256 adds the
+ * partials j, j + 256, ... in chunk order, then the same butterfly and wave sum.  A chain of at most 16 + 6 + 4 additions in
+ * the chunk and min(chunks - 1, ceil(chunks / 256) + 9) in the fold (absent partials enter as exact zeros), whatever the grid's
+ * schedule: within the sequential bound (32 + chunks) * 2^-24 relative to the sum of the absolute terms.  A tensor without the
+ * has-gradient bit gets 0.
  * Non-finite guard: if ANY statistic is NaN / inf (a non-finite loss poisons every gradient) the update launch is a no-op --
  * student, moments, teacher and weight copies keep their values (the reference exits before its update, main_esvit.py:546-551);
  * `skipped` (device int32, may be NULL) is then incremented by one, so that a host that looks at the loss only now and then can still
@@ -586,6 +607,7 @@ int esvit_center_ema(float* center, const float* colsum, float momentum, float d
 #define ESVIT_RULE_SGD 1
 #define ESVIT_RULE_LARS 2
 #define ESVIT_RULE_SGD_MEMBERS 3
+#define ESVIT_SQNORM_ORDERED 0x100
 int esvit_grad_sqnorm(const int64_t* tensors, int ntensors, const int32_t* chunks, int nchunks, int stats,
                       float* sqnorms, esvit_stream_t stream);
 int esvit_fused_clip_update_ema(int rule, const int64_t* tensors, int ntensors, const int32_t* chunks, int nchunks,
