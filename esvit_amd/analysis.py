@@ -54,12 +54,13 @@ def attention_entropy(model, images, queries=None, unit="bits"):
     VisionTransformer: -> fp32 [depth, B, nH, N], or [depth, B, nH, len(queries)] for a list of query tokens (token 0 is the class
     token).  One backbone pass without gradients; the entropy is accumulated beside the running softmax statistics, no N x N tensor
     exists at any point.  SwinTransformer: -> a list with one tensor [B * nW, nH, ws^2] (or [..., len(queries)]) per block, from the
-    window maps of `forward_selfattention(images, n=2)`.  Any other backbone: TypeError.
+    window maps of `forward_selfattention(images, n=2)`; `swin_window_to_grid` puts such a tensor back on the token grid of its block
+    (`model.feature_grid(H, W)` lists the grids).  Any other backbone: TypeError.
 
     unit: "bits" (the reference's log2) or "nats".  Convention 0 log 0 = 0: a probability that underflowed to zero contributes nothing.
     The reference's `(-p * torch.log2(p)).sum(-1)` (analyze_models.py:116-135) evaluates 0 * -inf there and returns NaN for the row.
 
-    images: one batch [B, 3, H, W] (H and W need not be equal for a VisionTransformer), or a list of batches of different shapes --
+    images: one batch [B, 3, H, W] (H and W need not be equal), or a list of batches of different shapes --
     then a list of results in the same order, one pass per batch (the reference's loop feeds one picture at a time)."""
     if unit not in _UNITS:
         raise ValueError("unit: bits or nats, not %r" % (unit,))
@@ -84,6 +85,21 @@ def attention_entropy(model, images, queries=None, unit="bits"):
         return out
     raise TypeError("attention_entropy: VisionTransformer and SwinTransformer backbones only, not %s (its attention is neither one global "
                     "softmax per image nor Swin's window maps)" % type(model).__name__)
+
+
+def swin_window_to_grid(values, H, W, window, shift):
+    """a per-window-slot tensor of one Swin block, [B * nW, nH, ws^2] (the window-ordered entropies of `attention_entropy`, one query
+    row or column of an attention map), back on the block's H x W token grid -> [B, nH, H, W], through the slot -> token map the
+    kernels walk (Fn.geometry: zero padding to a multiple of the window, the cyclic shift and the partition in one table).  The slots
+    of the padding are dropped.  window, shift: the block's own (`blk.window_size`, `blk.shift_size`)."""
+    geom = Fn.geometry(int(H), int(W), int(window), int(shift), values.device)
+    N, nW = geom.N, geom.nW
+    if values.dim() != 3 or values.shape[2] != N or values.shape[0] % nW:
+        raise ValueError("swin_window_to_grid: expected [B * %d, nH, %d] for a %d x %d grid in %d x %d windows, got %s"
+                         % (nW, N, H, W, window, window, tuple(values.shape)))
+    B, nH = values.shape[0] // nW, values.shape[1]
+    slots = values.reshape(B, nW, nH, N).permute(0, 2, 1, 3).reshape(B, nH, nW * N)
+    return slots.index_select(2, geom.tok2win.long()).reshape(B, nH, H, W)  # (tok2win: the slot of every token)
 
 
 def attention_rows(model, images, queries, blocks=None):

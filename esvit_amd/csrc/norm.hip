@@ -42,9 +42,12 @@ struct RowSrc {
     int C;         // channels of the normalised row (4*Cin for merge)
     int merge;     // 0/1
     int H, W, Cin; // merge geometry (input grid)
+    // PAD (ESVIT_MERGE_PAD): H x W is the true grid of any parity, the merged grid is ceil(H/2) x ceil(W/2) and the quadrants past
+    // the bottom / right edge do not exist: ask live() first, ptr() / off() / dst_row() are for tokens that do
+    template <int PAD = 0>
     __device__ __forceinline__ const float* ptr(long r, int c4) const {
         if (!merge) return x + r * (long)C + c4 * 4;
-        const int Ho = H / 2, Wo = W / 2;
+        const int Ho = PAD ? (H + 1) / 2 : H / 2, Wo = PAD ? (W + 1) / 2 : W / 2;
         const long b = r / (Ho * Wo);
         const int rem = (int)(r % (Ho * Wo));
         const int i = rem / Wo, j = rem % Wo;
@@ -53,14 +56,22 @@ struct RowSrc {
         const int di = blk & 1, dj = blk >> 1;
         return x + ((b * H + (2 * i + di)) * W + (2 * j + dj)) * (long)Cin + cc;
     }
-    __device__ __forceinline__ float* dptr(float* dx, long r, int c4) const {
-        return dx + (ptr(r, c4) - x);
+    template <int PAD>
+    __device__ __forceinline__ bool live(long r, int c4) const {  // does the token of (merged row r, vector c4) lie inside the grid?
+        if (!PAD) return true;
+        const int Ho = (H + 1) / 2, Wo = (W + 1) / 2;
+        const int rem = (int)(r % (Ho * Wo));
+        const int i = rem / Wo, j = rem % Wo;
+        const int blk = (c4 * 4) / Cin;
+        return 2 * i + (blk & 1) < H && 2 * j + (blk >> 1) < W;
     }
     // element offset of (row r, vector c4) in the un-gathered [.., C or Cin] layout, and the token row it belongs to
-    __device__ __forceinline__ long off(long r, int c4) const { return ptr(r, c4) - x; }
+    template <int PAD = 0>
+    __device__ __forceinline__ long off(long r, int c4) const { return ptr<PAD>(r, c4) - x; }
+    template <int PAD = 0>
     __device__ __forceinline__ long dst_row(long r, int c4) const {  // (the same sub-expressions as ptr(): folded by the compiler)
         if (!merge) return r;
-        const int Ho = H / 2, Wo = W / 2;
+        const int Ho = PAD ? (H + 1) / 2 : H / 2, Wo = PAD ? (W + 1) / 2 : W / 2;
         const long b = r / (Ho * Wo);
         const int rem = (int)(r % (Ho * Wo));
         const int i = rem / Wo, j = rem % Wo;
@@ -69,7 +80,7 @@ struct RowSrc {
     }
 };
 
-template <typename T, int G, int ITERS>
+template <typename T, int G, int ITERS, int PAD = 0>
 __global__ __launch_bounds__(LN_THREADS) void ln_fwd_kernel(RowSrc src, const float* __restrict__ gamma,
                                                              const float* __restrict__ beta, float eps, long rows,
                                                              T* __restrict__ y, float* __restrict__ y_f32,
@@ -86,7 +97,7 @@ __global__ __launch_bounds__(LN_THREADS) void ln_fwd_kernel(RowSrc src, const fl
     for (int it = 0; it < ITERS; ++it) {
         const int c4 = gl + it * G;
         v[it] = f32x4{0.f, 0.f, 0.f, 0.f};
-        if (c4 < C4) v[it] = *reinterpret_cast<const f32x4*>(src.ptr(r, c4));
+        if (c4 < C4 && src.live<PAD>(r, c4)) v[it] = *reinterpret_cast<const f32x4*>(src.ptr<PAD>(r, c4));  // (a pad quadrant stays zero and enters the statistics)
         s += hsum4(v[it]);
     }
     s = group_sum<G>(s);
@@ -122,7 +133,7 @@ __global__ __launch_bounds__(LN_THREADS) void ln_fwd_kernel(RowSrc src, const fl
 }
 
 // backward: dx = rstd * (gdy - mean(gdy) - xhat * mean(gdy*xhat)), gdy = gamma*dy
-template <typename T, int G, int ITERS, typename TA = T>  // TA: type of dx_act (bf16 from an fp32 upstream gradient: the patch-embedding norm)
+template <typename T, int G, int ITERS, typename TA = T, int PAD = 0>  // TA: type of dx_act (bf16 from an fp32 upstream gradient: the patch-embedding norm)
 __global__ __launch_bounds__(LN_THREADS) void ln_bwd_kernel(RowSrc src, const T* __restrict__ dy,
                                                              const float* __restrict__ mean,
                                                              const float* __restrict__ rstd,
@@ -155,7 +166,8 @@ __global__ __launch_bounds__(LN_THREADS) void ln_bwd_kernel(RowSrc src, const T*
             xh[it] = f32x4{0.f, 0.f, 0.f, 0.f};
             gd[it] = f32x4{0.f, 0.f, 0.f, 0.f};
             if (c4 < C4) {
-                const f32x4 xv = *reinterpret_cast<const f32x4*>(src.ptr(r, c4));
+                f32x4 xv = f32x4{0.f, 0.f, 0.f, 0.f};
+                if (src.live<PAD>(r, c4)) xv = *reinterpret_cast<const f32x4*>(src.ptr<PAD>(r, c4));
                 const f32x4 d = load4<T>(dy + ri * C + c4 * 4);
                 xh[it] = (xv - mu) * rs;
                 gd[it] = d * gm[it];
@@ -170,13 +182,13 @@ __global__ __launch_bounds__(LN_THREADS) void ln_bwd_kernel(RowSrc src, const T*
 #pragma unroll
         for (int it = 0; it < ITERS; ++it) {
             const int c4 = gl + it * G;
-            if (c4 < C4) {
+            if (c4 < C4 && src.live<PAD>(r, c4)) {  // (a pad quadrant has no dx: its terms are in dgamma / dbeta only)
                 f32x4 o = (gd[it] - s1 - xh[it] * s2) * rs;
-                const long off = src.off(r, c4);  // (the 2x2 merge scatters a row over four token rows)
+                const long off = src.off<PAD>(r, c4);  // (the 2x2 merge scatters a row over four token rows)
                 if (g_in) o += *reinterpret_cast<const f32x4*>(g_in + off);
                 if (dx) *reinterpret_cast<f32x4*>(dx + off) = o;  // (NULL: only the activation-dtype copy is wanted)
                 if (dx_act) {  // the activation-dtype, DropPath-scaled copy the next GEMMs of the backward read (saves a cast pass)
-                    const float sc = rowscale ? rowscale[src.dst_row(r, c4) / rows_per_sample] : 1.f;
+                    const float sc = rowscale ? rowscale[src.dst_row<PAD>(r, c4) / rows_per_sample] : 1.f;
                     store4<TA>(dx_act + off, o * sc);
                 }
             }
@@ -266,7 +278,7 @@ inline int ln_bwd_nblk(long rows, int C) {
     return (int)nb;
 }
 
-template <typename T>
+template <typename T, int PAD = 0>
 int ln_fwd_launch(RowSrc src, const float* gamma, const float* beta, float eps, long rows, void* y, float* y_f32,
                   float* mean, float* rstd, const int* rowmap, int tokens, int period_out, hipStream_t stream) {
     LnCfg cfg;
@@ -275,14 +287,14 @@ int ln_fwd_launch(RowSrc src, const float* gamma, const float* beta, float eps, 
     const int grid = ceil_div(rows, rpb);
     ln_dispatch(cfg, [&](auto shp) {
         using S = decltype(shp);
-        hipLaunchKernelGGL((ln_fwd_kernel<T, S::G, S::ITERS>), dim3(grid), dim3(LN_THREADS), 0, stream, src, gamma, beta, eps,
+        hipLaunchKernelGGL((ln_fwd_kernel<T, S::G, S::ITERS, PAD>), dim3(grid), dim3(LN_THREADS), 0, stream, src, gamma, beta, eps,
                            rows, reinterpret_cast<T*>(y), y_f32, mean, rstd, rowmap, tokens, period_out);
     });
     ESVIT_CHECK_LAUNCH("layernorm_fwd");
     return ESVIT_OK;
 }
 
-template <typename T, typename TA = T>
+template <typename T, typename TA = T, int PAD = 0>
 int ln_bwd_launch(RowSrc src, const void* dy, const float* mean, const float* rstd, const float* gamma,
                   const float* g_in, long rows, float* dx, float* dgamma, float* dbeta, float* ws, const int* rowmap,
                   int tokens, int period_in, hipStream_t stream, void* dx_act = nullptr, const float* rowscale = nullptr,
@@ -295,7 +307,7 @@ int ln_bwd_launch(RowSrc src, const void* dy, const float* mean, const float* rs
     ESVIT_CHECK_ARG(lds <= 160 * 1024, "layernorm_bwd: C=%d too large", src.C);
     ln_dispatch(cfg, [&](auto shp) {
         using S = decltype(shp);
-        auto kern = ln_bwd_kernel<T, S::G, S::ITERS, TA>;
+        auto kern = ln_bwd_kernel<T, S::G, S::ITERS, TA, PAD>;
         if (lds > 48 * 1024)
             (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
                                       (int)lds);
@@ -506,10 +518,30 @@ extern "C" int esvit_layernorm_bwd(int dtype, const void* dy, const float* x, co
     return ESVIT_ERR_ARG;
 }
 
+// ESVIT_MERGE_PAD in H: the true grid (any parity) travels in the low 16 bits; -> false (error set) unless both sides are in [1, 32767]
+static bool merge_pad_grid(const char* who, int Hflag, int W, int* H) {
+    *H = Hflag & 0xffff;
+    if ((Hflag & ~(ESVIT_MERGE_PAD | 0xffff)) != 0 || *H < 1 || *H >= 32768 || W < 1 || W >= 32768) {
+        esvit_set_error("%s: ESVIT_MERGE_PAD takes 1 <= H, W < 32768 (H=%d W=%d)", who, *H, W);
+        return false;
+    }
+    return true;
+}
+
 extern "C" int esvit_merge_ln_fwd(int dtype, const float* x, const float* gamma, const float* beta, float eps, int nB,
                                   int H, int W, int C, void* y, float* mean, float* rstd, esvit_stream_t s_) {
     hipStream_t stream = reinterpret_cast<hipStream_t>(s_);
     ESVIT_CHECK_ARG(x && gamma && beta && y && mean && rstd, "esvit_merge_ln_fwd: null pointer");
+    if (H & ESVIT_MERGE_PAD) {
+        int Ht;
+        if (!merge_pad_grid("esvit_merge_ln_fwd", H, W, &Ht)) return ESVIT_ERR_ARG;
+        ESVIT_CHECK_ARG(C > 0 && C % 4 == 0 && nB > 0, "esvit_merge_ln_fwd: bad geometry (C=%d nB=%d)", C, nB);
+        ESVIT_CHECK_ARG(dtype == ESVIT_BF16 || dtype == ESVIT_F32, "esvit_merge_ln_fwd: bad dtype");
+        RowSrc src{x, 4 * C, 1, Ht, W, C};
+        const long rows = (long)nB * ((Ht + 1) / 2) * ((W + 1) / 2);
+        if (dtype == ESVIT_BF16) return ln_fwd_launch<bf16, 1>(src, gamma, beta, eps, rows, y, nullptr, mean, rstd, nullptr, 0, 0, stream);
+        return ln_fwd_launch<float, 1>(src, gamma, beta, eps, rows, y, nullptr, mean, rstd, nullptr, 0, 0, stream);
+    }
     ESVIT_CHECK_ARG(H % 2 == 0 && W % 2 == 0 && C % 4 == 0 && nB > 0, "esvit_merge_ln_fwd: H,W must be even (H=%d W=%d)", H, W);
     RowSrc src{x, 4 * C, 1, H, W, C};
     const long rows = (long)nB * (H / 2) * (W / 2);
@@ -525,6 +557,21 @@ extern "C" int esvit_merge_ln_bwd(int dtype, const void* dy, const float* x, con
                                   esvit_stream_t s_) {
     hipStream_t stream = reinterpret_cast<hipStream_t>(s_);
     ESVIT_CHECK_ARG(dy && x && mean && rstd && gamma && dx && dgamma && dbeta && ws, "esvit_merge_ln_bwd: null pointer");
+    if (H & ESVIT_MERGE_PAD) {
+        int Ht;
+        if (!merge_pad_grid("esvit_merge_ln_bwd", H, W, &Ht)) return ESVIT_ERR_ARG;
+        ESVIT_CHECK_ARG(C > 0 && C % 4 == 0 && nB > 0, "esvit_merge_ln_bwd: bad geometry (C=%d nB=%d)", C, nB);
+        ESVIT_CHECK_ARG(dtype == ESVIT_BF16 || dtype == ESVIT_F32, "esvit_merge_ln_bwd: bad dtype");
+        if (rowscale) ESVIT_CHECK_ARG(dx_act && rows_per_sample > 0, "esvit_merge_ln_bwd: rowscale scales dx_act and needs rows_per_sample");
+        const int rps_ = rows_per_sample > 0 ? rows_per_sample : 1;
+        RowSrc src{x, 4 * C, 1, Ht, W, C};
+        const long rows = (long)nB * ((Ht + 1) / 2) * ((W + 1) / 2);
+        if (dtype == ESVIT_BF16)
+            return ln_bwd_launch<bf16, bf16, 1>(src, dy, mean, rstd, gamma, nullptr, rows, dx, dgamma, dbeta, ws, nullptr, 0, 0, stream, dx_act,
+                                                rowscale, rps_, accumulate);
+        return ln_bwd_launch<float, float, 1>(src, dy, mean, rstd, gamma, nullptr, rows, dx, dgamma, dbeta, ws, nullptr, 0, 0, stream, dx_act,
+                                              rowscale, rps_, accumulate);
+    }
     ESVIT_CHECK_ARG(H % 2 == 0 && W % 2 == 0 && C % 4 == 0 && nB > 0, "esvit_merge_ln_bwd: bad geometry");
     if (rowscale) ESVIT_CHECK_ARG(dx_act && rows_per_sample > 0, "esvit_merge_ln_bwd: rowscale scales dx_act and needs rows_per_sample");
     const int rps = rows_per_sample > 0 ? rows_per_sample : 1;

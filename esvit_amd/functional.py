@@ -29,6 +29,29 @@ def ops_module():
     return ops
 
 
+# PatchMerging on an odd feature map (swin_transformer.py:406-408): "copy" pads the token grid with a pass of its own (PadTokensFn) and
+# keeps such crops off the ragged multi-crop route; "kernel" lets the merge kernel read the missing row / column as zeros
+# (ops.merge_ln_fwd(pad=True), ESVIT_MERGE_PAD of include/esvit_hip.h) on both routes.  Neither setting has been timed: the default is
+# what the code did before the switch existed.  Environment: ESVIT_MERGE_PAD=copy|kernel; anything else raises.
+_MERGE_PAD_MODES = ("copy", "kernel")
+MERGE_PAD = os.environ.get("ESVIT_MERGE_PAD", "copy")
+if MERGE_PAD not in _MERGE_PAD_MODES:
+    raise ValueError("ESVIT_MERGE_PAD: copy or kernel, not %r" % MERGE_PAD)
+
+
+def merge_pad_in_kernel():
+    """True: odd feature maps are padded inside the merge kernel (MERGE_PAD == "kernel" and an ops module that offers the mode -- the
+    CPU restatement of the kernels does not and keeps the copy route)"""
+    if MERGE_PAD not in _MERGE_PAD_MODES:
+        raise ValueError("functional.MERGE_PAD: copy or kernel, not %r" % (MERGE_PAD,))
+    return MERGE_PAD == "kernel" and bool(getattr(ops_module(), "MERGE_LN_PAD", False))
+
+
+def merged_grid(H, W):
+    """grid after one PatchMerging: odd sides are padded up first (swin_transformer.py:406-408)"""
+    return (H + 1) // 2, (W + 1) // 2
+
+
 def _no_dbias(o, N, hd):
     """keyword of o.window_attn_bwd for a caller WITHOUT a relative-position table: on windows of more than 64 tokens at head_dim 64 the
     bias gradient is a kernel of its own (window_attn_big.hip), which such a caller leaves out.  Passed only where it changes something
@@ -658,23 +681,35 @@ def swin_block_attention(x, geom, nH, index, prm_list):
 # ------------------------------------------------------------------------------------------------
 # PatchEmbed / PatchMerging / final norm / pooling
 # ------------------------------------------------------------------------------------------------
+def _patch_cols(o, img, patch, Kc, out=None):
+    """im2col of [nB, 3, H, W] for the patch projection.  An ops module whose patch_im2col takes square images only (the CPU restatement)
+    gets the columns of a rectangle from F.unfold, which has the same (c, ph, pw) order (as VitPatchEmbedFn)"""
+    H, Wd = img.shape[-2:]
+    if H == Wd or getattr(o, "PATCH_IM2COL_RECT", False):
+        return o.patch_im2col(img.contiguous(), patch, Kc) if out is None else o.patch_im2col(img.contiguous(), patch, Kc, out=out)
+    if H % patch or Wd % patch:
+        raise ValueError("patch embedding: image %dx%d is not made of whole %d-pixel patches" % (H, Wd, patch))
+    cols = o.cast_to_act(torch.nn.functional.unfold(img.float(), patch, stride=patch).transpose(1, 2).reshape(-1, Kc).contiguous())
+    return cols if out is None else out.copy_(cols)
+
+
 class PatchEmbedFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, img, Wp, bp, g, b, patch):
         o = ops_module()
         E = Wp.shape[0]
         Kc = Wp.shape[1] * patch * patch
-        nB, _, S, _ = img.shape
-        cols = o.patch_im2col(img.contiguous(), patch, Kc)
+        nB, _, S, Sw = img.shape
+        cols = _patch_cols(o, img, patch, Kc)
         W = _weight(Wp, (E, Kc))
         y = o.linear_fwd(cols, W, bp, out_f32=True)
         ctx.wshape = tuple(Wp.shape)
         if g is None:  # PATCH_NORM False (swin_transformer.py:476-477, 492-493): the projection is the embedding
             ctx.save_for_backward(cols)
-            return y.view(nB, (S // patch) ** 2, E)
+            return y.view(nB, (S // patch) * (Sw // patch), E)
         x, _, mean, rstd = o.layernorm_fwd(y, g, b, LN_EPS, dtype=torch.float32)
         ctx.save_for_backward(cols, y, mean, rstd, g)
-        return x.view(nB, (S // patch) ** 2, E)
+        return x.view(nB, (S // patch) * (Sw // patch), E)
 
     @staticmethod
     def backward(ctx, gx):
@@ -702,11 +737,11 @@ class PatchEmbedMultiFn(torch.autograd.Function):
         o = ops_module()
         E = Wp.shape[0]
         Kc = Wp.shape[1] * patch * patch
-        rows = [im.shape[0] * (im.shape[2] // patch) ** 2 for im in imgs]  # one entry per crop tensor, in crop order
+        rows = [im.shape[0] * (im.shape[2] // patch) * (im.shape[3] // patch) for im in imgs]  # one entry per crop tensor, in crop order
         cols = torch.empty((sum(rows), Kc), dtype=o.act_dtype(), device=imgs[0].device)
         r0 = 0
         for im, n in zip(imgs, rows):  # (the reference concatenates the crops of a resolution first, swin_transformer.py:741)
-            o.patch_im2col(im.contiguous(), patch, Kc, out=cols[r0:r0 + n])
+            _patch_cols(o, im, patch, Kc, out=cols[r0:r0 + n])
             r0 += n
         y = o.linear_fwd(cols, _weight(Wp, (E, Kc)), bp, out_f32=True)
         ctx.wshape, ctx.n_img = tuple(Wp.shape), len(imgs)
@@ -736,7 +771,8 @@ class PatchEmbedMultiFn(torch.autograd.Function):
 class PatchMergeMultiFn(torch.autograd.Function):
     """PatchMerging over the token rows of several resolution groups: the 2x2 gather + LayerNorm(4C) runs per group (it
     depends on the grid) into one shared row buffer; the reduction GEMM, its dgrad and wgrad run once over all rows.
-    X fp32 [M, C], groups: tuple of (row0, nB, H, W) -> fp32 [M/4, 2C] with the groups in the same order.
+    X fp32 [M, C], groups: tuple of (row0, nB, H, W) -> fp32 [sum nB*Ho*Wo, 2C] with the groups in the same order ((Ho, Wo) =
+    merged_grid(H, W): M/4 rows when every grid is even; an odd grid goes through the pad mode of the kernel, see MERGE_PAD).
 
     The node takes part in the shadow protocol of SwinBlockMultiFn on both sides.  Xsh / prev_scale: the shadow output and the
     MLP-branch DropPath row scale of the stage's last block -- the LayerNorm backward that produces dL/dX also emits
@@ -748,12 +784,13 @@ class PatchMergeMultiFn(torch.autograd.Function):
         o = ops_module()
         X = X.contiguous()
         M, C = X.shape
-        y = torch.empty((M // 4, 4 * C), dtype=o.act_dtype(), device=X.device)
-        mean = torch.empty((M // 4,), dtype=torch.float32, device=X.device)
+        qs, Q = merged_row_offsets(groups)
+        y = torch.empty((Q, 4 * C), dtype=o.act_dtype(), device=X.device)
+        mean = torch.empty((Q,), dtype=torch.float32, device=X.device)
         rstd = torch.empty_like(mean)
-        for (r0, nB, H, W) in groups:
-            q0, q1 = r0 // 4, (r0 + nB * H * W) // 4
-            o.merge_ln_fwd(X[r0:r0 + nB * H * W].view(nB, H * W, C), g, b, LN_EPS, H, W, out=(y[q0:q1], mean[q0:q1], rstd[q0:q1]))
+        for (r0, nB, H, W), (q0, q1) in zip(groups, qs):
+            o.merge_ln_fwd(X[r0:r0 + nB * H * W].view(nB, H * W, C), g, b, LN_EPS, H, W, out=(y[q0:q1], mean[q0:q1], rstd[q0:q1]),
+                           **_merge_pad_kw(H, W))
         Wc = _weight(Wr)
         out = o.linear_fwd(y, Wc, None, out_f32=True)
         ctx.save_for_backward(X, y, mean, rstd, g, Wc)
@@ -768,34 +805,55 @@ class PatchMergeMultiFn(torch.autograd.Function):
         o = ops_module()
         X, y, mean, rstd, g, Wc = ctx.saved_tensors
         M, C = X.shape
-        gob = gosh.contiguous() if gosh is not None else o.gather_cast(go.contiguous(), M // 4)
+        qs, Q = merged_row_offsets(ctx.groups)
+        gob = gosh.contiguous() if gosh is not None else o.gather_cast(go.contiguous(), Q)
         dWr = _side_run(lambda: _wgrad(gob, y, ctx.wparam), gob, y)
         dy = o.linear_dgrad(gob, Wc)
         dX = torch.empty_like(X)
         dXsh = torch.empty((M, C), dtype=y.dtype, device=X.device) if ctx.emit_shadow else None
         ps = ctx.prev_scale
         gb = torch.empty((2, 4 * C), dtype=torch.float32, device=X.device)  # dgamma | dbeta: the first group writes, later ones accumulate
-        for gi, (r0, nB, H, W) in enumerate(ctx.groups):
+        for gi, ((r0, nB, H, W), (q0, q1)) in enumerate(zip(ctx.groups, qs)):
             r1 = r0 + nB * H * W
-            q0, q1 = r0 // 4, r1 // 4
             o.merge_ln_bwd(dy[q0:q1], X[r0:r1].view(nB, H * W, C), mean[q0:q1], rstd[q0:q1], g, H, W, dx_out=dX[r0:r1], gb_out=gb,
-                           accumulate=gi > 0, act_out=None if dXsh is None else dXsh[r0:r1], rowscale=None if (ps is None or dXsh is None) else ps[r0:r1])
+                           accumulate=gi > 0, act_out=None if dXsh is None else dXsh[r0:r1], rowscale=None if (ps is None or dXsh is None) else ps[r0:r1],
+                           **_merge_pad_kw(H, W))
         _side_join()
         return dX, dXsh, None, None, gb[0], gb[1], dWr
 
 
+def merged_row_offsets(groups):
+    """groups (row0, nB, H, W) -> ([(q0, q1) merged-row range per group], total merged rows): cumulative, since a group with an odd
+    side has more than a quarter of its rows left"""
+    qs, q = [], 0
+    for (_, nB, H, W) in groups:
+        Ho, Wo = merged_grid(H, W)
+        qs.append((q, q + nB * Ho * Wo))
+        q += nB * Ho * Wo
+    return qs, q
+
+
+def _merge_pad_kw(H, W):
+    """keyword of o.merge_ln_fwd / _bwd: an odd grid asks for the pad mode of the kernel (an even one is called as ever)"""
+    return {"pad": True} if (H % 2 or W % 2) else {}
+
+
 class PatchMergeFn(torch.autograd.Function):
+    """x fp32 [nB, H*W, C] -> [nB, Ho*Wo, 2C], (Ho, Wo) = merged_grid(H, W); an odd H or W goes through the kernel's pad mode (the caller
+    has checked that the ops module offers it, or padded the grid itself)"""
+
     @staticmethod
     def forward(ctx, x, H, W, g, b, Wr):
         o = ops_module()
         x = x.contiguous()
         nB, L, C = x.shape
-        y, mean, rstd = o.merge_ln_fwd(x, g, b, LN_EPS, H, W)
+        Ho, Wo = merged_grid(H, W)
+        y, mean, rstd = o.merge_ln_fwd(x, g, b, LN_EPS, H, W, **_merge_pad_kw(H, W))
         Wc = _weight(Wr)
         out = o.linear_fwd(y, Wc, None, out_f32=True)
         ctx.save_for_backward(x, y, mean, rstd, g, Wc)
         ctx.hw, ctx.wparam = (H, W), Wr
-        return out.view(nB, L // 4, 2 * C)
+        return out.view(nB, Ho * Wo, 2 * C)
 
     @staticmethod
     def backward(ctx, go):
@@ -806,7 +864,7 @@ class PatchMergeFn(torch.autograd.Function):
         gb = o.gather_cast(go.contiguous().view(rows, -1), rows)
         dWr = _wgrad(gb, y, ctx.wparam)
         dy = o.linear_dgrad(gb, Wc)
-        dx, dg, db = o.merge_ln_bwd(dy, x, mean, rstd, g, H, W)
+        dx, dg, db = o.merge_ln_bwd(dy, x, mean, rstd, g, H, W, **_merge_pad_kw(H, W))
         return dx, None, None, dg, db, dWr
 
 

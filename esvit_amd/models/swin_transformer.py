@@ -27,6 +27,17 @@ def _pair(x):
     return tuple(x) if isinstance(x, (tuple, list)) else (x, x)
 
 
+def _grid(L, hw):
+    """token grid of [B, L, C]: the caller's (H, W), or the reference's square guess (swin_transformer.py:279, :400)"""
+    if hw is None:
+        H = W = int(sqrt(L))
+        return H, W
+    H, W = int(hw[0]), int(hw[1])
+    if H * W != L:
+        raise ValueError("token grid %d x %d does not hold %d tokens" % (H, W, L))
+    return H, W
+
+
 class DropPath(nn.Module):
     """holder for the stochastic-depth rate; the per-sample factors are drawn in the block (vision_transformer.py:30-38)"""
 
@@ -92,9 +103,11 @@ class SwinTransformerBlock(nn.Module):
         return [self.norm1.weight, self.norm1.bias, a.relative_position_bias_table, a.qkv.weight, a.qkv.bias, a.proj.weight,
                 a.proj.bias, self.norm2.weight, self.norm2.bias, m.fc1.weight, m.fc1.bias, m.fc2.weight, m.fc2.bias]
 
-    def forward(self, x, return_attention=False):
+    def forward(self, x, return_attention=False, hw=None):
+        """hw: the (H, W) token grid of x; None = the square grid of int(sqrt(L)) a side.  Window size and shift stay what the constructor
+        fixed from input_resolution; a grid that is no multiple of the window is padded inside Fn.geometry's maps"""
         B, L, C = x.shape
-        H = W = int(sqrt(L))
+        H, W = _grid(L, hw)
         geom = Fn.geometry(H, W, self.window_size, self.shift_size, x.device)
         dp = None
         if isinstance(self.drop_path, DropPath):
@@ -131,24 +144,27 @@ class PatchMerging(nn.Module):
         self.reduction = nn.Linear(4 * dim, 2 * dim, bias=False)
         self.norm = norm_layer(4 * dim)
 
-    def forward(self, x):
+    def forward(self, x, hw=None):
+        """hw: the (H, W) token grid of x (None: square).  The merged grid is recorded in self.out_hw (Fn.merged_grid(H, W))"""
         B, L, C = x.shape
-        H = W = int(sqrt(L))
-        if H % 2 or W % 2:  # odd feature map: zero row / column appended first (swin_transformer.py:406-408)
+        H, W = _grid(L, hw)
+        self.__dict__["out_hw"] = Fn.merged_grid(H, W)
+        if (H % 2 or W % 2) and not Fn.merge_pad_in_kernel():  # odd feature map: zero row / column appended first (swin_transformer.py:406-408)
             x = Fn.PadTokensFn.apply(x, H, W, H + H % 2, W + W % 2)
             H, W = H + H % 2, W + W % 2
         return Fn.PatchMergeFn.apply(x, H, W, self.norm.weight, self.norm.bias, self.reduction.weight)
 
     def forward_ragged(self, X, groups, shadow=None, prev_scale=None):
-        """X fp32 [M, C] token rows of several resolution groups ((row0, nB, H, W) each) -> ([M/4, 2C], merged groups, shadow of the
-        output).  shadow / prev_scale: the stage's last block's shadow output and MLP-branch DropPath row scale -- the merge's
+        """X fp32 [M, C] token rows of several resolution groups ((row0, nB, H, W) each) -> ([sum nB*Ho*Wo, 2C], merged groups
+        (row0', nB, Ho, Wo), shadow of the output).  shadow / prev_scale: the stage's last block's shadow output and MLP-branch DropPath row scale -- the merge's
         backward then emits that block's cast gradient; the returned shadow is for the next stage's first block, which hands this
         node the cast dL/dY its GEMMs read (Fn.SwinBlockMultiFn)"""
-        if any(H % 2 or W % 2 for (_, _, H, W) in groups):
+        if any(H % 2 or W % 2 for (_, _, H, W) in groups) and not Fn.merge_pad_in_kernel():
             raise NotImplementedError("odd feature maps on the ragged multi-crop route: set model.ragged_multi_crop = False "
-                                      "(the per-group schedule pads them, swin_transformer.py:406-408)")
+                                      "(the per-group schedule pads them, swin_transformer.py:406-408) or functional.MERGE_PAD = 'kernel'")
         Y, Ysh = Fn.PatchMergeMultiFn.apply(X, shadow, prev_scale, tuple(groups), self.norm.weight, self.norm.bias, self.reduction.weight)
-        return Y, [(r0 // 4, nB, H // 2, W // 2) for (r0, nB, H, W) in groups], Ysh
+        qs, _ = Fn.merged_row_offsets(groups)
+        return Y, [(q0, nB) + Fn.merged_grid(H, W) for (_, nB, H, W), (q0, _) in zip(groups, qs)], Ysh
 
 
 def _sample_offsets(groups):
@@ -170,10 +186,19 @@ class BasicLayer(nn.Module):
                                  norm_layer=norm_layer) for i in range(depth)])
         self.downsample = downsample(input_resolution, dim=dim, norm_layer=norm_layer) if downsample is not None else None
 
-    def forward(self, x):
+    def forward(self, x, hw=None):
+        """hw: the (H, W) token grid of x (None: square); the grid of the result is self.out_hw when hw was given"""
         for blk in self.blocks:
-            x, _ = blk(x)
-        return self.downsample(x) if self.downsample is not None else x
+            x, _ = blk(x, hw=hw)
+        return self._down(x, hw)
+
+    def _down(self, x, hw):
+        if self.downsample is None:
+            self.__dict__["out_hw"] = None if hw is None else (int(hw[0]), int(hw[1]))
+            return x
+        x = self.downsample(x, hw=hw)
+        self.__dict__["out_hw"] = None if hw is None else self.downsample.out_hw
+        return x
 
     def forward_ragged(self, X, groups, shadow=None):
         """X: fp32 token rows [M, C] of several resolution groups, groups: list of (row0, nB, H, W).  The blocks of this
@@ -217,19 +242,19 @@ class BasicLayer(nn.Module):
             return self.downsample.forward_ragged(X, groups, shadow, prev_scale)
         return X, groups, None
 
-    def forward_with_features(self, x):
+    def forward_with_features(self, x, hw=None):
         fea = []
         for blk in self.blocks:
-            x, _ = blk(x)
+            x, _ = blk(x, hw=hw)
             fea.append(x)
-        return (self.downsample(x) if self.downsample is not None else x), fea
+        return self._down(x, hw), fea
 
-    def forward_with_attention(self, x):
+    def forward_with_attention(self, x, hw=None):
         attns = []
         for blk in self.blocks:
-            x, a = blk(x, return_attention=True)
+            x, a = blk(x, return_attention=True, hw=hw)
             attns.append(a)
-        return (self.downsample(x) if self.downsample is not None else x), attns
+        return self._down(x, hw), attns
 
 
 class PatchEmbed(nn.Module):
@@ -243,9 +268,26 @@ class PatchEmbed(nn.Module):
         self.proj = nn.Conv2d(in_chans, embed_dim, kernel_size=patch_size, stride=patch_size)
         self.norm = norm_layer(embed_dim) if norm_layer is not None else None
 
+    def whole_patches(self, x):
+        """an image side that is no multiple of the patch size loses the remainder rows / columns, as under the reference's strided
+        convolution (swin_transformer.py:531)"""
+        H, W = x.shape[-2:]
+        P = self.patch_size[0]
+        return x[..., :H // P * P, :W // P * P] if (H % P or W % P) else x
+
+    def grid(self, x):
+        """(H, W) token grid of an image batch [B, 3, H, W]"""
+        return x.shape[-2] // self.patch_size[0], x.shape[-1] // self.patch_size[0]
+
     def forward(self, x):
         g, b = (self.norm.weight, self.norm.bias) if self.norm is not None else (None, None)  # (PATCH_NORM False: no norm)
+        x = self.whole_patches(x)
         return Fn.PatchEmbedFn.apply(x, self.proj.weight, self.proj.bias, g, b, self.patch_size[0])
+
+
+def _hw_of(layer, hw):
+    """the grid a stage handed on: what it recorded, or None on the square route"""
+    return None if hw is None else layer.out_hw
 
 
 class SwinTransformer(nn.Module):
@@ -311,11 +353,36 @@ class SwinTransformer(nn.Module):
 
     # ---- forward paths -----------------------------------------------------------------------
     def _tokens(self, x):
+        """[B, 3, H, W] -> tokens [B, (H / P) * (W / P), C]; their grid is self._image_grid(x)"""
         self._draw_drop_path(x.shape[0], x.device)
+        hw = self.patch_embed.grid(x)
+        if self.ape:
+            self._check_ape(hw)
         x = self.patch_embed(x)
         if self.ape:
             x = Fn.ApeAddFn.apply(x, self.absolute_pos_embed)
         return x
+
+    def _image_grid(self, x):
+        """the (H, W) token grid the stages are told about: None for a square image, whose grid every stage recovers from L as ever"""
+        hw = self.patch_embed.grid(x)
+        return None if hw[0] == hw[1] else hw
+
+    def _check_ape(self, hw):
+        if tuple(hw) != tuple(self.patches_resolution):
+            raise ValueError("absolute_pos_embed was built for a %d x %d token grid, the image gives %d x %d (USE_APE: no resampling, "
+                             "swin_transformer.py:683)" % (self.patches_resolution[0], self.patches_resolution[1], hw[0], hw[1]))
+
+    def feature_grid(self, H, W):
+        """image height and width -> [(h, w) token grid of every stage]: the shapes of the region tokens forward_feature_maps and
+        forward_return_n_last_blocks produce (odd grids are padded up at each PatchMerging)"""
+        P = self.patch_embed.patch_size[0]
+        h, w = H // P, W // P
+        out = []
+        for i in range(self.num_layers):
+            out.append((h, w))
+            h, w = Fn.merged_grid(h, w)
+        return out
 
     def _draw_drop_path(self, nB, device):
         """Stochastic-depth factors floor(keep + U[0,1)) / keep (vision_transformer.py:30-38) for BOTH residual branches
@@ -332,9 +399,10 @@ class SwinTransformer(nn.Module):
             b.__dict__["_dp_pending"] = (f[2 * i], f[2 * i + 1])
 
     def forward_feature_maps(self, x):
-        x = self._tokens(x)
+        x, hw = self._tokens(x), self._image_grid(x)
         for layer in self.layers:
-            x = layer(x)
+            x = layer(x, hw=hw)
+            hw = _hw_of(layer, hw)
         x_grid = Fn.FinalNormFn.apply(x, self.norm.weight, self.norm.bias)
         return Fn.TokenMeanFn.apply(x_grid), x_grid
 
@@ -349,12 +417,12 @@ class SwinTransformer(nn.Module):
         pe = self.patch_embed
         P = pe.patch_size[0]
         g, b = (pe.norm.weight, pe.norm.bias) if pe.norm is not None else (None, None)
-        X = Fn.PatchEmbedMultiFn.apply(pe.proj.weight, pe.proj.bias, g, b, P, *flat)
+        X = Fn.PatchEmbedMultiFn.apply(pe.proj.weight, pe.proj.bias, g, b, P, *[pe.whole_patches(c) for c in flat])
         groups, r0 = [], 0
         for grp in crop_groups:
-            nB, G = sum(c.shape[0] for c in grp), grp[0].shape[-1] // P
-            groups.append((r0, nB, G, G))
-            r0 += nB * G * G
+            nB, Gh, Gw = sum(c.shape[0] for c in grp), grp[0].shape[-2] // P, grp[0].shape[-1] // P
+            groups.append((r0, nB, Gh, Gw))
+            r0 += nB * Gh * Gw
         shadow = None
         for layer in self.layers:
             X, groups, shadow = layer.forward_ragged(X, groups, shadow)
@@ -383,14 +451,15 @@ class SwinTransformer(nn.Module):
         # group consecutive crops of equal resolution (swin_transformer.py:729-732)
         bounds, start = [], 0
         for i in range(1, len(x) + 1):
-            if i == len(x) or x[i].shape[-1] != x[start].shape[-1]:
+            if i == len(x) or x[i].shape[-2:] != x[start].shape[-2:]:
                 bounds.append((start, i))
                 start = i
         if self.use_dense_prediction:
             cls_parts, fea_parts, npatch = [], [], []
             all_fea = None
             several = len(bounds) > 1 or bounds[0][1] - bounds[0][0] > 1  # (one group of several crops -- the teacher's two global views -- is read where it lies too)
-            if self.ragged_multi_crop and several and not self.ape and self._even_maps([x[a].shape[-1] for a, _ in bounds]):
+            if self.ragged_multi_crop and several and not self.ape and \
+                    (Fn.merge_pad_in_kernel() or self._even_maps([tuple(x[a].shape[-2:]) for a, _ in bounds])):
                 # every resolution group through the backbone at once (row-wise kernels see all rows, attention runs per group)
                 maps, all_fea = self.forward_feature_maps_multi([x[a:b] for a, b in bounds])
             else:
@@ -411,32 +480,35 @@ class SwinTransformer(nn.Module):
         """the ragged route merges 2 x 2 patches of every group in one launch and has no padding step: crops whose feature map is odd
         at some PatchMerging (e.g. 112^2 at four stages: 28, 14, 7) take the per-group schedule, which pads them as the reference
         does (swin_transformer.py:406-408)"""
-        for S in sizes:
-            G = S // self.patch_embed.patch_size[0]
-            for _ in range(self.num_layers - 1):
-                if G % 2:
-                    return False
-                G //= 2
+        for S in sizes:  # an image side, or an (H, W) pair
+            for side in (S if isinstance(S, (tuple, list, torch.Size)) else (S,)):
+                G = side // self.patch_embed.patch_size[0]
+                for _ in range(self.num_layers - 1):
+                    if G % 2:
+                        return False
+                    G //= 2
         return True
 
     def forward_selfattention(self, x, n=1):
-        x = self._tokens(x)
+        x, hw = self._tokens(x), self._image_grid(x)
         if n == 1:
-            return self.forward_last_selfattention(x)
-        return self.forward_all_selfattention(x)
+            return self.forward_last_selfattention(x, hw)
+        return self.forward_all_selfattention(x, hw)
 
-    def forward_last_selfattention(self, x):
+    def forward_last_selfattention(self, x, hw=None):
         for i, layer in enumerate(self.layers):
             if i < len(self.layers) - 1:
-                x = layer(x)
+                x = layer(x, hw=hw)
+                hw = _hw_of(layer, hw)
             else:
-                x, attns = layer.forward_with_attention(x)
+                x, attns = layer.forward_with_attention(x, hw=hw)
                 return attns[-1]
 
-    def forward_all_selfattention(self, x):
+    def forward_all_selfattention(self, x, hw=None):
         out = []
         for layer in self.layers:
-            x, attns = layer.forward_with_attention(x)
+            x, attns = layer.forward_with_attention(x, hw=hw)
+            hw = _hw_of(layer, hw)
             out += attns
         return out
 
@@ -448,10 +520,11 @@ class SwinTransformer(nn.Module):
             if acc <= start_idx < acc + d:
                 start_stage, start_blk = i, start_idx - acc
             acc += d
-        x = self._tokens(x)
+        x, hw = self._tokens(x), self._image_grid(x)
         output = []
         for i, layer in enumerate(self.layers):
-            x, fea = layer.forward_with_features(x)
+            x, fea = layer.forward_with_features(x, hw=hw)
+            hw = _hw_of(layer, hw)
             if i >= start_stage:
                 for x_ in fea[start_blk:]:
                     if i == len(self.layers) - 1:

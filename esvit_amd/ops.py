@@ -610,13 +610,26 @@ def layernorm_bwd_to_act(dy, x, mean, rstd, gamma, *, gb_out=None):
     return dxa, dgamma, dbeta
 
 
-def merge_ln_fwd(x, gamma, beta, eps, H, W, dtype=None, out=None):
+MERGE_LN_PAD = True  # merge_ln_fwd / merge_ln_bwd take pad=True: odd grids padded inside the kernel (ESVIT_MERGE_PAD, include/esvit_hip.h)
+MERGE_PAD_FLAG = 0x40000000  # ESVIT_MERGE_PAD: OR'd into H, selects the pad mode of esvit_merge_ln_fwd / _bwd
+
+
+def _merge_grid(H, W, pad):
+    """-> (the H argument of the library call, merged rows per sample)"""
+    if pad:
+        return min(max(H, 0), 0xffff) | MERGE_PAD_FLAG, ((H + 1) // 2) * ((W + 1) // 2)  # (a side the low 16 bits cannot hold: one the library refuses)
+    return H, (H // 2) * (W // 2)
+
+
+def merge_ln_fwd(x, gamma, beta, eps, H, W, dtype=None, out=None, pad=False):
     """x fp32 [nB, H*W, C] -> (y act [nB*H/2*W/2, 4C], mean, rstd).  out: optional preallocated (y, mean, rstd) -- e.g.
-    row slices of buffers shared by several resolution groups."""
+    row slices of buffers shared by several resolution groups.  pad: H x W of any parity, the missing bottom row / right column
+    read as zeros inside the kernel -> ceil(H/2)*ceil(W/2) rows per sample (F.pad + merge, swin_transformer.py:406-414)."""
     x = _f32c(x)
     nB, L, Cc = x.shape
     assert L == H * W
-    rows = nB * (H // 2) * (W // 2)
+    Harg, rps = _merge_grid(H, W, pad)
+    rows = nB * rps
     dt = dtype or _ACT_DTYPE
     if out is not None:
         y, mean, rstd = out
@@ -625,13 +638,13 @@ def merge_ln_fwd(x, gamma, beta, eps, H, W, dtype=None, out=None):
         y = torch.empty((rows, 4 * Cc), dtype=dt, device=x.device)
         mean = torch.empty((rows,), dtype=torch.float32, device=x.device)
         rstd = torch.empty_like(mean)
-    check(lib.esvit_merge_ln_fwd(_code(dt), _p(x), _p(gamma), _p(beta), eps, nB, H, W, Cc, _p(y), _p(mean), _p(rstd), _stream()),
+    check(lib.esvit_merge_ln_fwd(_code(dt), _p(x), _p(gamma), _p(beta), eps, nB, Harg, W, Cc, _p(y), _p(mean), _p(rstd), _stream()),
           "merge_ln_fwd")
     return y, mean, rstd
 
 
-def merge_ln_bwd(dy, x, mean, rstd, gamma, H, W, dx_out=None, gb_out=None, accumulate=False, act_out=None, rowscale=None):
-    """gb_out: optional fp32 [2, 4C] receiving (dgamma | dbeta); accumulate: add to it instead of overwriting (further
+def merge_ln_bwd(dy, x, mean, rstd, gamma, H, W, dx_out=None, gb_out=None, accumulate=False, act_out=None, rowscale=None, pad=False):
+    """pad: as in merge_ln_fwd; dx / act_out keep the true [nB, H*W, C] grid, pad positions receive nothing.  gb_out: optional fp32 [2, 4C] receiving (dgamma | dbeta); accumulate: add to it instead of overwriting (further
     resolution groups sharing the parameters).  act_out: optional activation-dtype [nB*H*W, C] receiving cast(rowscale * dx)
     (rowscale: per token row, or None) -- the MLP-branch operand of the block whose dL/dy this dx is (SwinBlockMultiFn's shadow)"""
     x, dy = _f32c(x), _actc(dy)
@@ -650,9 +663,11 @@ def merge_ln_bwd(dy, x, mean, rstd, gamma, H, W, dx_out=None, gb_out=None, accum
     gb = gb_out if gb_out is not None else torch.empty((2, 4 * Cc), dtype=torch.float32, device=x.device)
     assert gb.shape == (2, 4 * Cc) and gb.is_contiguous()
     dgamma, dbeta = gb[0], gb[1]
-    rows = nB * (H // 2) * (W // 2)
+    Harg, rps = _merge_grid(H, W, pad)
+    rows = nB * rps
+    assert not pad or (L == H * W and dy.numel() == rows * 4 * Cc and mean.numel() == rows and rstd.numel() == rows)
     ws = workspace(query(Q_LN_BWD_BLOCKS, rows, 4 * Cc) * 8 * Cc, x.device, slot=1)
-    check(lib.esvit_merge_ln_bwd(_code(dy.dtype), _p(dy), _p(x), _p(mean), _p(rstd), _p(gamma), nB, H, W, Cc, _p(dx), _p(dgamma),
+    check(lib.esvit_merge_ln_bwd(_code(dy.dtype), _p(dy), _p(x), _p(mean), _p(rstd), _p(gamma), nB, Harg, W, Cc, _p(dx), _p(dgamma),
                                  _p(dbeta), _p(ws), _p(act_out), _p(rowscale), 1, int(acc), _stream()), "merge_ln_bwd")
     return dx, dgamma, dbeta
 

@@ -303,14 +303,25 @@ int esvit_colsum(int dtype, const void* x, int64_t rows, int N, int64_t ld, floa
 int esvit_patch_im2col(int dtype, const float* img, void* cols, int nB, int S, int P, int Kpad,
                        esvit_stream_t stream);
 /* PatchMerging gather + LayerNorm(4C) (swin_transformer.py:410-417): x fp32 [nB,H,W,C] ->
- * y dtype [nB*(H/2)*(W/2), 4C]; channel blocks [x(2i,2j), x(2i+1,2j), x(2i,2j+1), x(2i+1,2j+1)]. */
+ * y dtype [nB*(H/2)*(W/2), 4C]; channel blocks [x(2i,2j), x(2i+1,2j), x(2i,2j+1), x(2i+1,2j+1)].  H and W even.
+ * PAD MODE: H = true height | ESVIT_MERGE_PAD.  H x W is then the true grid, any sides in [1, 32767] of any parity, and the
+ * merged grid is Ho x Wo = (H+1)/2 x (W+1)/2: y, mean and rstd have nB*Ho*Wo rows.  A quadrant whose token (2i+di, 2j+dj) lies
+ * outside the grid contributes zeros to the 4C row BEFORE the LayerNorm -- F.pad followed by the concatenation
+ * (swin_transformer.py:406-414): the zeros enter the row statistics and those channels come out as (0 - mean)*rstd*gamma + beta.
+ * No address is formed for such a quadrant (the load is predicated).  On an even grid the flag changes no bit of the result.
+ * ESVIT_ERR_ARG before any launch for a null pointer, a side outside [1, 32767], other bits set in H, C % 4 != 0 or nB < 1. */
+#define ESVIT_MERGE_PAD 0x40000000
 int esvit_merge_ln_fwd(int dtype, const float* x, const float* gamma, const float* beta, float eps,
                        int nB, int H, int W, int C, void* y, float* mean, float* rstd,
                        esvit_stream_t stream);
 /* backward of the above: dy dtype [nB*(H/2)*(W/2), 4C] -> dx fp32 [nB,H,W,C] (overwritten); dgamma / dbeta overwritten, or
  * added to when accumulate != 0 (further resolution groups sharing the parameters).  dx_act (optional, `dtype`, [nB,H,W,C]) =
  * rowscale[token row / rows_per_sample] * dx as in esvit_layernorm_bwd: the MLP-branch operand of the stage's LAST block, whose
- * dL/dy this is. */
+ * dL/dy this is.
+ * PAD MODE (H = true height | ESVIT_MERGE_PAD, as in the forward): dy, mean, rstd have nB*Ho*Wo rows; dx and dx_act stay
+ * [nB,H,W,C] and receive every live token exactly once -- nothing is written for a pad position.  dgamma / dbeta include the pad
+ * quadrants' terms (their x-hat is -mean*rstd, not zero).  rowscale is indexed by the live token row (b*H + i)*W + j over
+ * rows_per_sample.  accumulate keeps its meaning.  Refusals as in the forward. */
 int esvit_merge_ln_bwd(int dtype, const void* dy, const float* x, const float* mean, const float* rstd,
                        const float* gamma, int nB, int H, int W, int C, float* dx, float* dgamma,
                        float* dbeta, float* ws, void* dx_act, const float* rowscale, int rows_per_sample, int accumulate,
