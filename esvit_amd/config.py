@@ -33,6 +33,9 @@ SWIN_SPECS = {
                           QKV_BIAS=True, DROP_RATE=0, ATTN_DROP_RATE=0, DROP_PATH_RATE=0.2, USE_APE=False, PATCH_NORM=True),
     "swin_base_w7": dict(PATCH_SIZE=4, DIM_EMBED=128, DEPTHS=[2, 2, 18, 2], NUM_HEADS=[4, 8, 16, 32], WINDOW_SIZE=7, MLP_RATIO=4,
                          QKV_BIAS=True, DROP_RATE=0, ATTN_DROP_RATE=0, DROP_PATH_RATE=0.2, USE_APE=False, PATCH_NORM=True),
+    # swin_large_patch4_window7_224.yaml: the PatchMerging in front of the last stage normalises rows of 4 * 768 = 3072 channels
+    "swin_large_w7": dict(PATCH_SIZE=4, DIM_EMBED=192, DEPTHS=[2, 2, 18, 2], NUM_HEADS=[6, 12, 24, 48], WINDOW_SIZE=7, MLP_RATIO=4,
+                          QKV_BIAS=True, DROP_RATE=0, ATTN_DROP_RATE=0, DROP_PATH_RATE=0.2, USE_APE=False, PATCH_NORM=True),
 }
 
 

@@ -2,7 +2,8 @@
 // block folded into the store / load), PatchMerging gather+LayerNorm, row L2-normalise and the
 // legacy weight_norm of DINOHead.last_layer.  All are HBM-bound: one pass over the row held in
 // registers, 16-byte accesses, wave-shuffle reductions (no LDS except for the dgamma/dbeta
-// block reduction).
+// block reduction; rows beyond 2048 channels are held by a whole workgroup and cross its waves
+// through 16 bytes of LDS: ln_wide_*).
 #include "common.h"
 #include "../../include/esvit_hip.h"
 
@@ -213,6 +214,139 @@ __global__ __launch_bounds__(LN_THREADS) void ln_bwd_kernel(RowSrc src, const T*
     }
 }
 
+// ---------------------------------------------------------------------------------------------
+// Wide rows: 2048 < C <= 8192, C % 1024 == 0 (the PatchMerging norm in front of Swin-L's last stage is 4 * 768 = 3072 wide).
+// One 256-thread workgroup per row, NV = C / 1024 16-byte vectors per lane (vector c4 = threadIdx.x + it * 256: every lane is
+// busy at every width, a wave reads 1 KiB runs); the row reductions cross the four waves through LDS (block_sum).  The backward
+// walks rows blockIdx.x, blockIdx.x + gridDim.x, ... with the dgamma / dbeta terms of its columns in registers and writes them
+// to ws[block][2][C] as they are: one row at a time per workgroup, so nothing is left to fold in LDS.  Same arguments, options
+// and outputs as ln_fwd_kernel / ln_bwd_kernel.  No atomics: the bits depend on (rows, C) only.
+// ---------------------------------------------------------------------------------------------
+constexpr int LN_WIDE_MAX_BLOCKS = 1024;
+
+template <typename T, int NV, int PAD = 0>
+__global__ __launch_bounds__(LN_THREADS) void ln_wide_fwd_kernel(RowSrc src, const float* __restrict__ gamma,
+                                                                  const float* __restrict__ beta, float eps, long rows,
+                                                                  T* __restrict__ y, float* __restrict__ y_f32,
+                                                                  float* __restrict__ mean, float* __restrict__ rstd,
+                                                                  const int* __restrict__ rowmap, int tokens, int period_out) {
+    __shared__ float red[LN_THREADS / 64];
+    const int C = src.C;
+    const long r = blockIdx.x;
+    if (r >= rows) return;  // (the grid is `rows` blocks: never taken, and uniform over the block if it were)
+    f32x4 v[NV];
+    float s = 0.f;
+#pragma unroll
+    for (int it = 0; it < NV; ++it) {
+        const int c4 = threadIdx.x + it * LN_THREADS;
+        v[it] = f32x4{0.f, 0.f, 0.f, 0.f};
+        if (src.live<PAD>(r, c4)) v[it] = *reinterpret_cast<const f32x4*>(src.ptr<PAD>(r, c4));  // (a pad quadrant stays zero and enters the statistics)
+        s += hsum4(v[it]);
+    }
+    const float mu = block_sum<LN_THREADS>(s, red) / C;
+    float q = 0.f;
+#pragma unroll
+    for (int it = 0; it < NV; ++it) {
+        const f32x4 d = v[it] - mu;
+        q += hsum4(d * d);
+    }
+    const float rs = rsqrtf(block_sum<LN_THREADS>(q, red) / C + eps);
+    if (threadIdx.x == 0) {
+        mean[r] = mu;
+        rstd[r] = rs;
+    }
+    long ro = r;
+    if (rowmap) ro = (r / tokens) * (long)period_out + rowmap[r % tokens];
+#pragma unroll
+    for (int it = 0; it < NV; ++it) {
+        const int c4 = threadIdx.x + it * LN_THREADS;
+        const f32x4 gm = *reinterpret_cast<const f32x4*>(gamma + c4 * 4);
+        const f32x4 bt = *reinterpret_cast<const f32x4*>(beta + c4 * 4);
+        const f32x4 o = (v[it] - mu) * rs * gm + bt;
+        store4<T>(y + ro * C + c4 * 4, o);
+        if (y_f32) *reinterpret_cast<f32x4*>(y_f32 + r * C + c4 * 4) = o;
+    }
+}
+
+template <typename T, int NV, typename TA = T, int PAD = 0>
+__global__ __launch_bounds__(LN_THREADS) void ln_wide_bwd_kernel(RowSrc src, const T* __restrict__ dy,
+                                                                  const float* __restrict__ mean,
+                                                                  const float* __restrict__ rstd,
+                                                                  const float* __restrict__ gamma,
+                                                                  const float* __restrict__ g_in, long rows,
+                                                                  float* __restrict__ dx, float* __restrict__ ws,
+                                                                  const int* __restrict__ rowmap, int tokens, int period_in,
+                                                                  TA* __restrict__ dx_act, const float* __restrict__ rowscale,
+                                                                  int rows_per_sample) {
+    __shared__ float red[LN_THREADS / 64];
+    const int C = src.C;
+    f32x4 dgam[NV], dbet[NV];
+#pragma unroll
+    for (int it = 0; it < NV; ++it) {
+        dgam[it] = f32x4{0.f, 0.f, 0.f, 0.f};
+        dbet[it] = f32x4{0.f, 0.f, 0.f, 0.f};
+    }
+    for (long r = blockIdx.x; r < rows; r += gridDim.x) {  // (the trip count is the block's: the barriers of block_sum are met by every lane)
+        const float mu = mean[r], rs = rstd[r];
+        long ri = r;
+        if (rowmap) ri = (r / tokens) * (long)period_in + rowmap[r % tokens];
+        f32x4 xh[NV], gd[NV];
+        float s1 = 0.f, s2 = 0.f;
+#pragma unroll
+        for (int it = 0; it < NV; ++it) {
+            const int c4 = threadIdx.x + it * LN_THREADS;
+            f32x4 xv = f32x4{0.f, 0.f, 0.f, 0.f};
+            if (src.live<PAD>(r, c4)) xv = *reinterpret_cast<const f32x4*>(src.ptr<PAD>(r, c4));
+            const f32x4 d = load4<T>(dy + ri * C + c4 * 4);
+            xh[it] = (xv - mu) * rs;
+            gd[it] = d * *reinterpret_cast<const f32x4*>(gamma + c4 * 4);  // (gamma is re-read per row from L2: 32 registers less at C = 8192)
+            dgam[it] += d * xh[it];
+            dbet[it] += d;
+            s1 += hsum4(gd[it]);
+            s2 += hsum4(gd[it] * xh[it]);
+        }
+        s1 = block_sum<LN_THREADS>(s1, red) / C;
+        s2 = block_sum<LN_THREADS>(s2, red) / C;
+#pragma unroll
+        for (int it = 0; it < NV; ++it) {
+            const int c4 = threadIdx.x + it * LN_THREADS;
+            if (src.live<PAD>(r, c4)) {  // (a pad quadrant has no dx: its terms are in dgamma / dbeta only)
+                f32x4 o = (gd[it] - s1 - xh[it] * s2) * rs;
+                const long off = src.off<PAD>(r, c4);
+                if (g_in) o += *reinterpret_cast<const f32x4*>(g_in + off);
+                if (dx) *reinterpret_cast<f32x4*>(dx + off) = o;
+                if (dx_act) {
+                    const float sc = rowscale ? rowscale[src.dst_row<PAD>(r, c4) / rows_per_sample] : 1.f;
+                    store4<TA>(dx_act + off, o * sc);
+                }
+            }
+        }
+    }
+    // ws[blk][2][C]: every block of the grid has walked at least one row (the grid is min(rows, LN_WIDE_MAX_BLOCKS))
+#pragma unroll
+    for (int it = 0; it < NV; ++it) {
+        const int c4 = threadIdx.x + it * LN_THREADS;
+        *reinterpret_cast<f32x4*>(ws + ((long)blockIdx.x * 2 + 0) * C + c4 * 4) = dgam[it];
+        *reinterpret_cast<f32x4*>(ws + ((long)blockIdx.x * 2 + 1) * C + c4 * 4) = dbet[it];
+    }
+}
+
+inline int ln_wide_nv(int C) { return (C > 2048 && C <= 8192 && C % 1024 == 0) ? C / 1024 : 0; }  // 3 .. 8, or 0: not a wide row
+template <int NV_>
+struct LnWide {
+    static constexpr int NV = NV_;
+};
+template <typename F>
+inline void ln_wide_dispatch(int nv, F&& f) {
+    if (nv == 3) f(LnWide<3>{});
+    else if (nv == 4) f(LnWide<4>{});
+    else if (nv == 5) f(LnWide<5>{});
+    else if (nv == 6) f(LnWide<6>{});
+    else if (nv == 7) f(LnWide<7>{});
+    else f(LnWide<8>{});
+}
+inline int ln_wide_bwd_nblk(long rows) { return (int)(rows < 1 ? 1 : (rows > LN_WIDE_MAX_BLOCKS ? LN_WIDE_MAX_BLOCKS : rows)); }
+
 struct LnCfg {
     int G, ITERS;
 };
@@ -269,6 +403,7 @@ inline void ln_dispatch(const LnCfg& cfg, F&& f) {
 }
 
 inline int ln_bwd_nblk(long rows, int C) {
+    if (ln_wide_nv(C)) return ln_wide_bwd_nblk(rows);
     LnCfg cfg;
     if (!ln_cfg(C, &cfg)) return 0;
     const int rpb = LN_THREADS / cfg.G;
@@ -281,6 +416,15 @@ inline int ln_bwd_nblk(long rows, int C) {
 template <typename T, int PAD = 0>
 int ln_fwd_launch(RowSrc src, const float* gamma, const float* beta, float eps, long rows, void* y, float* y_f32,
                   float* mean, float* rstd, const int* rowmap, int tokens, int period_out, hipStream_t stream) {
+    if (const int nv = ln_wide_nv(src.C)) {
+        ESVIT_CHECK_ARG(rows <= 0x7fffffffL, "layernorm: %ld rows of %d channels exceed the grid", rows, src.C);
+        ln_wide_dispatch(nv, [&](auto w) {
+            hipLaunchKernelGGL((ln_wide_fwd_kernel<T, decltype(w)::NV, PAD>), dim3((unsigned)rows), dim3(LN_THREADS), 0, stream, src, gamma,
+                               beta, eps, rows, reinterpret_cast<T*>(y), y_f32, mean, rstd, rowmap, tokens, period_out);
+        });
+        ESVIT_CHECK_LAUNCH("layernorm_fwd(wide)");
+        return ESVIT_OK;
+    }
     LnCfg cfg;
     ESVIT_CHECK_ARG(ln_cfg(src.C, &cfg), "layernorm: unsupported channel count %d", src.C);
     const int rpb = LN_THREADS / cfg.G;
@@ -299,22 +443,30 @@ int ln_bwd_launch(RowSrc src, const void* dy, const float* mean, const float* rs
                   const float* g_in, long rows, float* dx, float* dgamma, float* dbeta, float* ws, const int* rowmap,
                   int tokens, int period_in, hipStream_t stream, void* dx_act = nullptr, const float* rowscale = nullptr,
                   int rows_per_sample = 1, int accumulate = 0) {
-    LnCfg cfg;
-    ESVIT_CHECK_ARG(ln_cfg(src.C, &cfg), "layernorm: unsupported channel count %d", src.C);
-    const int nblk = ln_bwd_nblk(rows, src.C);
-    const int rpb = LN_THREADS / cfg.G;
-    const size_t lds = (size_t)rpb * 2 * (src.C / 4) * sizeof(f32x4);
-    ESVIT_CHECK_ARG(lds <= 160 * 1024, "layernorm_bwd: C=%d too large", src.C);
-    ln_dispatch(cfg, [&](auto shp) {
-        using S = decltype(shp);
-        auto kern = ln_bwd_kernel<T, S::G, S::ITERS, TA, PAD>;
-        if (lds > 48 * 1024)
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                      (int)lds);
-        hipLaunchKernelGGL(kern, dim3(nblk), dim3(LN_THREADS), lds, stream, src, reinterpret_cast<const T*>(dy), mean,
-                           rstd, gamma, g_in, rows, dx, ws, rowmap, tokens, period_in, reinterpret_cast<TA*>(dx_act), rowscale,
-                           rows_per_sample);
-    });
+    const int nblk = ln_bwd_nblk(rows, src.C);  // (what ESVIT_Q_LN_BWD_BLOCKS answered for the caller's ws; 0: no kernel for this width)
+    if (const int nv = ln_wide_nv(src.C)) {
+        ln_wide_dispatch(nv, [&](auto w) {
+            hipLaunchKernelGGL((ln_wide_bwd_kernel<T, decltype(w)::NV, TA, PAD>), dim3(nblk), dim3(LN_THREADS), 0, stream, src,
+                               reinterpret_cast<const T*>(dy), mean, rstd, gamma, g_in, rows, dx, ws, rowmap, tokens, period_in,
+                               reinterpret_cast<TA*>(dx_act), rowscale, rows_per_sample);
+        });
+    } else {
+        LnCfg cfg;
+        ESVIT_CHECK_ARG(ln_cfg(src.C, &cfg), "layernorm: unsupported channel count %d", src.C);
+        const int rpb = LN_THREADS / cfg.G;
+        const size_t lds = (size_t)rpb * 2 * (src.C / 4) * sizeof(f32x4);
+        ESVIT_CHECK_ARG(lds <= 160 * 1024, "layernorm_bwd: C=%d too large", src.C);
+        ln_dispatch(cfg, [&](auto shp) {
+            using S = decltype(shp);
+            auto kern = ln_bwd_kernel<T, S::G, S::ITERS, TA, PAD>;
+            if (lds > 48 * 1024)
+                (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                          (int)lds);
+            hipLaunchKernelGGL(kern, dim3(nblk), dim3(LN_THREADS), lds, stream, src, reinterpret_cast<const T*>(dy), mean,
+                               rstd, gamma, g_in, rows, dx, ws, rowmap, tokens, period_in, reinterpret_cast<TA*>(dx_act), rowscale,
+                               rows_per_sample);
+        });
+    }
     ESVIT_CHECK_LAUNCH("layernorm_bwd");
     // ws rows are [dgamma(C) | dbeta(C)]; reduce both halves (dgamma and dbeta may be separate allocations)
     const int C = src.C;
