@@ -4,18 +4,36 @@ attention masks, and the correspondence score between two views -- batched, on t
 For a VisionTransformer nothing here forms an attention matrix: the entropy of every softmax row and the probability rows of a few
 queries come from the statistics mode of the flash-attention kernels (csrc/flash_attn.hip, ops.global_attn_stats), on every
 block in one backbone pass.  The reference loops over images at batch size 1 because `forward_selfattention` returns [B, nH, N, N] per
-block.  Swin backbones keep their 7 x 7 window maps (they are small) and reduce them in torch.  Plotting, the two augmented views and
-the per-head ordering of the figures stay with the caller."""
+block.  Swin backbones have two routes (SWIN_STATS): "maps", the default, keeps the window maps of `forward_selfattention` and reduces
+them in torch; "fused" takes the statistics mode of the window kernels (csrc/window_attn.hip, window_attn_big.hip,
+ops.window_attn_stats) block by block in one backbone pass and forms no map.  `swin_attention_rows` puts the attention of
+chosen pixel positions back on the token grid of any block.  Plotting, the two augmented views and the per-head ordering of the figures
+stay with the caller."""
 import math
+import os
 
 import torch
 
 from . import functional as Fn
-from .models.swin_transformer import SwinTransformer
+from .models.swin_transformer import SwinTransformer, _grid, _hw_of
 from .models.vision_transformer import VisionTransformer
 
 _LOG2E = 1.0 / math.log(2.0)
 _UNITS = {"bits": _LOG2E, "nats": 1.0}
+
+# how attention_entropy (and AttentionEntropyMeter through it) measures a SwinTransformer: "maps" reduces the maps of
+# forward_selfattention(n=2), all blocks' [B * nW, nH, N, N] alive at once; "fused" asks every block for its statistics and forms no map
+_SWIN_STATS_ROUTES = ("maps", "fused")
+SWIN_STATS = os.environ.get("ESVIT_SWIN_ATTN_STATS", "maps")
+
+
+def _swin_stats_route():
+    if SWIN_STATS not in _SWIN_STATS_ROUTES:
+        raise ValueError("ESVIT_SWIN_ATTN_STATS / analysis.SWIN_STATS: maps or fused, not %r" % (SWIN_STATS,))
+    return SWIN_STATS
+
+
+_swin_stats_route()
 
 
 def _is_vit(model):
@@ -48,6 +66,30 @@ def _query_index(queries, N, device):
     return idx.to(device)
 
 
+def _swin_block_stats(model, images, blocks, slots_of=None):
+    """one backbone pass under no_grad that stops after the last chosen block: per chosen block (flat index over all stages, ascending)
+    the statistics call on the block's input, then the block's ordinary forward -> {block: (entropy, rows, geometry)}.
+    slots_of(block index, stage, geometry) -> the listed window slots of that block, or None"""
+    want, out, i = set(blocks), {}, 0
+    with torch.no_grad():
+        x, hw = model._tokens(images), model._image_grid(images)
+        for li, layer in enumerate(model.layers):
+            for blk in layer.blocks:
+                if i in want:
+                    H, W = _grid(x.shape[1], hw)
+                    geom = Fn.geometry(H, W, blk.window_size, blk.shift_size, x.device)
+                    slots = None if slots_of is None else slots_of(i, li, geom)
+                    ent, rows = Fn.swin_block_attention_stats(x, geom, blk.num_heads, blk.attn.relative_position_index, blk._params(), slots)
+                    out[i] = (ent, rows, geom)
+                if i == max(want):
+                    return out
+                x, _ = blk(x, hw=hw)
+                i += 1
+            x = layer._down(x, hw)
+            hw = _hw_of(layer, hw)
+    return out
+
+
 def attention_entropy(model, images, queries=None, unit="bits"):
     """Shannon entropy of the attention distribution of every query token, block by block.
 
@@ -73,6 +115,16 @@ def attention_entropy(model, images, queries=None, unit="bits"):
         if queries is not None:
             ent = ent.index_select(3, _query_index(queries, ent.shape[3], ent.device))
         return ent * k if k != 1.0 else ent
+    if isinstance(model, SwinTransformer) and _swin_stats_route() == "fused":
+        depth = sum(len(layer.blocks) for layer in model.layers)
+        stats = _swin_block_stats(model, images, range(depth))
+        out = []
+        for i in range(depth):
+            e = stats[i][0]
+            if queries is not None:
+                e = e.index_select(2, _query_index(queries, e.shape[2], e.device))
+            out.append(e * k if k != 1.0 else e)
+        return out
     if isinstance(model, SwinTransformer):
         with torch.no_grad():
             maps = model.forward_selfattention(images, n=2)
@@ -115,6 +167,58 @@ def attention_rows(model, images, queries, blocks=None):
     blocks = [len(model.blocks) - 1] if blocks is None else list(blocks)
     _, rows = _vit_block_stats(model, images, queries, blocks, True)
     return torch.stack(rows)
+
+
+def swin_attention_rows(model, images, points, blocks=None):
+    """what the pixel positions `points` = [(y, x), ...] attend to in the chosen blocks of a SwinTransformer, on each block's own token
+    grid.  In stage l a point is the token (y // s, x // s), s = patch_size * 2^l, of the grid model.feature_grid(H, W)[l]; a point
+    outside it is a ValueError.  blocks: flat block indices over all stages, negatives allowed (default: the last block).  One backbone
+    pass that stops after the last chosen block; no attention map is formed where the window kernels have their statistics mode.
+    -> one (rows, pad_mass) pair per chosen block, in the given order: rows fp32 [B, nH, nq, H_l, W_l], the probabilities of the query's
+    window on the block's token grid (shift and padding undone through Fn.geometry's maps; zero outside the window), and pad_mass fp32
+    [B, nH, nq], the probability on the zero-pad key slots of that window: rows.sum((-1, -2)) + pad_mass = 1.
+    attention_mass_masks(rows.flatten(-2)) thresholds them.  images: a batch of any (H, W), or a list of batches -> a list of results."""
+    if isinstance(images, (list, tuple)):
+        return [swin_attention_rows(model, im, points, blocks) for im in images]
+    if not isinstance(model, SwinTransformer):
+        raise TypeError("swin_attention_rows: SwinTransformer backbones only, not %s" % type(model).__name__)
+    pts = [(int(y), int(x)) for y, x in points]
+    if not pts:
+        raise ValueError("swin_attention_rows: at least one point")
+    stage_of = [li for li, layer in enumerate(model.layers) for _ in layer.blocks]
+    depth = len(stage_of)
+    chosen = [depth - 1] if blocks is None else [int(b) for b in blocks]
+    if not chosen or any(not -depth <= b < depth for b in chosen):
+        raise ValueError("swin_attention_rows: block indices must lie in [%d, %d), got %r" % (-depth, depth, chosen))
+    chosen = [b % depth for b in chosen]
+    grids = model.feature_grid(images.shape[2], images.shape[3])
+    P = model.patch_embed.patch_size[0]
+    tokens = {}
+    for li in sorted(set(stage_of[b] for b in chosen)):
+        (gh, gw), s = grids[li], P << li
+        for y, x in pts:
+            if not (0 <= y // s < gh and 0 <= x // s < gw):
+                raise ValueError("swin_attention_rows: point (%d, %d) lies outside the %d x %d token grid of stage %d (cell side %d)"
+                                 % (y, x, gh, gw, li, s))
+        tokens[li] = torch.tensor([(y // s) * gw + x // s for y, x in pts])
+
+    def slots_of(i, li, geom):
+        assert (geom.H, geom.W) == tuple(grids[li]), ((geom.H, geom.W), grids[li])
+        return geom.tok2win.long()[tokens[li].to(geom.tok2win.device)]  # (tok2win: the slot of every token)
+
+    stats = _swin_block_stats(model, images, chosen, slots_of)
+    out = []
+    for b in chosen:
+        _, win_rows, geom = stats[b]
+        B, nH, nq, N = win_rows.shape
+        T = geom.tokens
+        slots = slots_of(b, stage_of[b], geom)
+        tok = geom.win2tok.long().view(geom.nW, N)[slots // N]  # [nq, N]: the token of every key slot of the query's window, -1 = pad
+        pad = tok < 0
+        dst = torch.where(pad, torch.full_like(tok, T), tok).view(1, 1, nq, N).expand(B, nH, nq, N)  # (pad slots: a column that is dropped)
+        grid = win_rows.new_zeros(B, nH, nq, T + 1).scatter_(-1, dst, win_rows)[..., :T]
+        out.append((grid.reshape(B, nH, nq, geom.H, geom.W), (win_rows * pad.view(1, 1, nq, N)).sum(-1)))
+    return out
 
 
 def attention_mass_masks(rows, threshold=0.6):

@@ -293,6 +293,205 @@ __global__ __launch_bounds__(128, (HDIM == 32 ? 3 : 2)) void attn_fwd4_kernel(co
     }
 }
 
+// Statistics of the window softmax (ws | ESVIT_ATTN_WINDOW_STATS, esvit_hip.h): attn_fwd4_kernel up to its probabilities -- the same walk
+// over the windows, the same staged scale * q and pad slots, the same score tiles, maximum, exponentials and sum -- and then, where the
+// forward stores P and multiplies by V, the entropy of every query row (H = ln l - sum_k e_k x_k / l with x = s - m, e = exp(x): a key
+// whose e is zero, the -1e30 columns beyond N among them, adds nothing) and the probability rows of the listed slots.  V is neither
+// loaded nor staged: two [NP][LDQ] images per wave pair.  Every element has one writer (the wave pair of the window, the lanes of the
+// query column); a listed slot outside [0, nW * N) matches no window and is skipped.
+template <typename T, int HDIM>
+__global__ __launch_bounds__(128, (HDIM == 32 ? 3 : 2)) void attn_stats4_kernel(const T* __restrict__ qkv, const float* __restrict__ qkv_bias,
+                                                            const int* __restrict__ win2tok, int L, const float* __restrict__ bias_frag,
+                                                            const int* __restrict__ region_ids, int nW, int Bw, int N, int nH, float scale,
+                                                            int parts, const int* __restrict__ slots, int nq, float* __restrict__ ent,
+                                                            float* __restrict__ rows) {
+    using Cfg = AttnCfgH<T, HDIM>;
+    constexpr int KS = HDIM / 32;
+    constexpr int LDQ = Cfg::LDQ, VEC = Cfg::VEC, ES = sizeof(T);
+    constexpr int VPR = HDIM / VEC, NV = NP * VPR / 128, LSTEP = 128 / VPR;
+    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int c = lane & 15, g = lane >> 4;
+    T* base = reinterpret_cast<T*>(smem_raw);
+    T* Qs = base;                  // [NP][LDQ]
+    T* Ks = base + Cfg::QK_ELEMS;  // [NP][LDQ]
+
+    const long unit = xcd_contiguous_id(blockIdx.x, gridDim.x);
+    const bool unit_ok = unit < (long)parts * nH;
+    const int h = (int)(unit % nH);
+    const int part = (int)(unit / nH);
+    const int C = nH * HDIM;
+    const bool masked = region_ids != nullptr;
+    const int lrow0 = tid / VPR, dv = tid % VPR;
+    const float* bias_f = bias_frag + (long)h * FRAG_ELEMS;
+
+    Vec16<T> padq, padk_v;
+#pragma unroll
+    for (int e = 0; e < VEC; ++e) {
+        padq.set(e, qkv_bias[h * HDIM + dv * VEC + e]);
+        padq.set(e, padq.get(e) * scale);
+        padk_v.set(e, qkv_bias[C + h * HDIM + dv * VEC + e]);
+    }
+
+    const int iters = (Bw + parts - 1) / parts;
+    auto win_of = [&](int it, bool& act) -> int {
+        const int bw = part + it * parts;
+        act = unit_ok && it < iters && bw < Bw;
+        return act ? bw : 0;
+    };
+    auto load_map = [&](int it, int& tok, int& reg) {
+        bool act;
+        const int bw = win_of(it, act);
+        tok = (act && lane < N) ? win2tok[(long)(bw % nW) * N + lane] : -1;
+        reg = (masked && act && lane < N) ? region_ids[(long)(bw % nW) * N + lane] : -1;
+    };
+    struct Win {
+        u32x4 q[NV], k[NV];
+        int ltok[NV];
+        int myreg, bw;
+        bool active;
+    };
+    auto issue_rows = [&](int it, int mytok, int myreg, Win& x) {
+        x.bw = win_of(it, x.active);
+        x.myreg = myreg;
+        const long tok_base = (long)(x.bw / nW) * L;
+        const __amdgpu_buffer_rsrc_t rq = __builtin_amdgcn_make_buffer_rsrc(const_cast<T*>(qkv + tok_base * 3L * C), 0, (int)(L * 3L * C * ES), 0x00020000);
+#pragma unroll
+        for (int i = 0; i < NV; ++i) {
+            const int tok = __shfl(mytok, lrow0 + LSTEP * i, 64);
+            x.ltok[i] = tok;
+            const int vq = tok >= 0 ? tok * 3 * C * ES + dv * 16 : BUF_OOB;
+            x.q[i] = __builtin_amdgcn_raw_buffer_load_b128(rq, vq, h * HDIM * ES, 0);
+            x.k[i] = __builtin_amdgcn_raw_buffer_load_b128(rq, vq, (C + h * HDIM) * ES, 0);
+        }
+    };
+
+    Win cur, nxt;
+    int tok1, reg1, tok2 = -1, reg2 = -1;
+    load_map(0, tok1, reg1);
+    issue_rows(0, tok1, reg1, cur);
+    load_map(1, tok1, reg1);
+
+    for (int it = 0; it < iters; ++it) {
+        __syncthreads();  // the other wave is done with the previous window's images
+#pragma unroll
+        for (int i = 0; i < NV; ++i) {
+            const int t = lrow0 + LSTEP * i;
+            const bool padslot = cur.active && t < N && cur.ltok[i] < 0;
+            Vec16<T> xq, xk;
+            xq.v = __builtin_bit_cast(decltype(xq.v), cur.q[i]);
+            xk.v = __builtin_bit_cast(decltype(xk.v), cur.k[i]);
+#pragma unroll
+            for (int e = 0; e < VEC; ++e) xq.set(e, xq.get(e) * scale);
+            if (padslot) {
+                xq = padq;
+                xk = padk_v;
+            }
+            st16<T>(Qs + t * LDQ + dv * VEC, xq);
+            st16<T>(Ks + t * LDQ + dv * VEC, xk);
+        }
+        const bool active = cur.active;
+        const int myreg = cur.myreg;
+        const int bw = cur.bw;
+        const long unit_wh = (long)bw * nH + h;
+        __syncthreads();  // images complete
+        issue_rows(it + 1, tok1, reg1, nxt);
+        load_map(it + 2, tok2, reg2);
+
+        f32x4 p[4][2];
+        float hq[2];  // entropy of query column 16 (2w + jl) + c
+        {
+            Frag<T> kf[4][KS], qf[2][KS];
+#pragma unroll
+            for (int ks = 0; ks < KS; ++ks) {
+#pragma unroll
+                for (int i = 0; i < 4; ++i) kf[i][ks] = frag_kc<T>(Ks, LDQ, 16 * i, 32 * ks, c, g);
+#pragma unroll
+                for (int jl = 0; jl < 2; ++jl) qf[jl][ks] = frag_kc<T>(Qs, LDQ, 16 * (2 * w + jl), 32 * ks, c, g);
+            }
+            int rq[2];
+#pragma unroll
+            for (int jl = 0; jl < 2; ++jl) rq[jl] = __shfl(myreg, 16 * (2 * w + jl) + c, 64);
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                int rk[4];
+#pragma unroll
+                for (int r = 0; r < 4; ++r) rk[r] = __shfl(myreg, 16 * i + 4 * g + r, 64);
+#pragma unroll
+                for (int jl = 0; jl < 2; ++jl) {
+                    f32x4 b = *reinterpret_cast<const f32x4*>(bias_f + ((i * 4 + 2 * w + jl) * 64 + lane) * 4);
+                    if (masked) {
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) b[r] += (rk[r] != rq[jl]) ? -100.f : 0.f;
+                    }
+                    p[i][jl] = b;
+#pragma unroll
+                    for (int ks = 0; ks < KS; ++ks) mma(kf[i][ks], qf[jl][ks], p[i][jl]);
+                }
+            }
+#pragma unroll
+            for (int jl = 0; jl < 2; ++jl) {
+                float m = -3.0e38f;
+#pragma unroll
+                for (int i = 0; i < 4; ++i)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) m = fmaxf(m, p[i][jl][r]);
+                m = fmaxf(m, __shfl_xor(m, 16, 64));
+                m = fmaxf(m, __shfl_xor(m, 32, 64));
+                float sum = 0.f, ex = 0.f;
+#pragma unroll
+                for (int i = 0; i < 4; ++i)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        const float x = p[i][jl][r] - m;
+                        const float e = __expf(x);
+                        p[i][jl][r] = e;
+                        sum += e;
+                        ex += e * x;
+                    }
+                sum += __shfl_xor(sum, 16, 64);
+                sum += __shfl_xor(sum, 32, 64);
+                ex += __shfl_xor(ex, 16, 64);
+                ex += __shfl_xor(ex, 32, 64);
+                const float inv = 1.f / sum;
+#pragma unroll
+                for (int i = 0; i < 4; ++i) p[i][jl] *= inv;
+                hq[jl] = __logf(sum) - ex * inv;
+            }
+        }
+        if (active && g == 0) {
+#pragma unroll
+            for (int jl = 0; jl < 2; ++jl) {
+                const int q = 16 * (2 * w + jl) + c;
+                if (q < N) ent[unit_wh * N + q] = hq[jl];
+            }
+        }
+        if (active) {
+            const int wi = bw % nW;
+            for (int n = 0; n < nq; ++n) {
+                const int slot = slots[n];
+                if ((unsigned)slot >= (unsigned)(nW * N) || slot / N != wi) continue;  // (wave-uniform)
+                const int qi = slot % N;
+                float* row = rows + ((((long)(bw / nW) * nH + h) * nq + n) * N);
+#pragma unroll
+                for (int jl = 0; jl < 2; ++jl) {
+                    if (qi != 16 * (2 * w + jl) + c) continue;
+#pragma unroll
+                    for (int i = 0; i < 4; ++i)
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) {
+                            const int key = 16 * i + 4 * g + r;
+                            if (key < N) row[key] = p[i][jl][r];
+                        }
+                }
+            }
+        }
+        cur = nxt;
+        tok1 = tok2;
+        reg1 = reg2;
+    }
+}
+
 
 // -------------------------------------------------------------------------------------------------
 // Backward: a wave pair (one 128-thread workgroup) owns one head and a strided set of windows.  The rows of window it+1
@@ -828,10 +1027,71 @@ int esvit_i_fill_bias_frag(const float* rel_table, int ws, int N, int nH, float*
     return fill_bias_frag(rel_table, ws, N, nH, bias_frag_ws, stream);
 }
 
+int esvit_big_attn_stats(int dtype, const void* qkv, const float* qkv_bias, const int32_t* win2tok, int L, const float* rel_table, int ws,
+                         float* bias_frag_ws, const int32_t* region_ids, int nW, int nB, int N, int nH, int hd, float scale,
+                         const int32_t* slots, int nq, float* ent, float* rows, hipStream_t stream);
+
+// the window-statistics mode of the forward entry (ws | ESVIT_ATTN_WINDOW_STATS, include/esvit_hip.h): every check before any launch
+static int window_attn_stats(int dtype, const void* qkv, const float* qkv_bias, const int32_t* win2tok, int L, const float* rel_table, int ws,
+                             float* bias_frag_ws, const int32_t* region_ids, int nW, int nB, int Nq, int nH, int hd, float scale,
+                             const void* out, float* lse, float* attn_out, hipStream_t stream) {
+    const char* who = "esvit_window_attn_fwd (window stats)";
+    ESVIT_CHECK_ARG(!(ws & ESVIT_ATTN_SLIDING_CHUNK), "%s: ESVIT_ATTN_WINDOW_STATS together with ESVIT_ATTN_SLIDING_CHUNK (ws = 0x%x)", who, (unsigned)ws);
+    ESVIT_CHECK_ARG(!(ws & ESVIT_ATTN_GLOBAL), "%s: ESVIT_ATTN_WINDOW_STATS together with ESVIT_ATTN_GLOBAL (ws = 0x%x)", who, (unsigned)ws);
+    ESVIT_CHECK_ARG(!(ws & ESVIT_ATTN_STATS), "%s: ESVIT_ATTN_WINDOW_STATS together with ESVIT_ATTN_STATS (ws = 0x%x)", who, (unsigned)ws);
+    ESVIT_CHECK_ARG(!(ws & ESVIT_ATTN_SPLIT_DBIAS), "%s: ESVIT_ATTN_WINDOW_STATS together with ESVIT_ATTN_SPLIT_DBIAS (ws = 0x%x)", who, (unsigned)ws);
+    ws &= ~ESVIT_ATTN_WINDOW_STATS;
+    const int N = Nq & 0xffff, nq = Nq > 0 ? Nq >> 16 : -1;
+    ESVIT_CHECK_ARG(qkv && qkv_bias && win2tok && nB > 0 && nW > 0 && nH > 0 && L > 0 && ws > 0 && N > 0 && nq >= 0 &&
+                        (N == ws * ws || (N < ws * ws && N <= esvit_big_npb())),
+                    "%s: bad args (ws=%d N=%d nq=%d nW=%d nB=%d nH=%d L=%d)", who, ws, N, nq, nW, nB, nH, L);
+    ESVIT_CHECK_ARG(attn_out != nullptr, "%s: attn_out (the entropies, fp32 [nB*nW, nH, N]) is required", who);
+    ESVIT_CHECK_ARG(nq == 0 || out != nullptr, "%s: nq = %d listed slots without the list (out: int32 [nq] on the device)", who, nq);
+    ESVIT_CHECK_ARG(nq == 0 || lse != nullptr, "%s: nq = %d listed slots without the rows output (lse: fp32 [nB, nH, nq, N])", who, nq);
+    ESVIT_CHECK_ARG(nq > 0 || !out, "%s: out must be NULL when no slot is listed (nq = 0)", who);
+    ESVIT_CHECK_ARG(nq > 0 || !lse, "%s: lse must be NULL when no slot is listed (nq = 0)", who);
+    ESVIT_CHECK_ARG(dtype == ESVIT_BF16 || dtype == ESVIT_F32, "%s: bad dtype %d", who, dtype);
+    ESVIT_CHECK_ARG((hd == 32 || hd == 64) && N <= esvit_big_npb() && (N <= NP || hd == 32 || dtype == ESVIT_BF16),
+                    "%s: %d tokens at head_dim %d unsupported (N <= 64: head_dim 32 or 64; 64 < N <= 224: 32, or 64 in bf16)", who, N, hd);
+    ESVIT_CHECK_ARG(bias_frag_ws != nullptr, "%s: the bias_frag_ws scratch is required", who);
+    const int32_t* slots = static_cast<const int32_t*>(out);
+    if (N > NP)
+        return esvit_big_attn_stats(dtype, qkv, qkv_bias, win2tok, L, rel_table, ws, bias_frag_ws, region_ids, nW, nB, N, nH, hd, scale, slots, nq,
+                                    attn_out, lse, stream);
+    ESVIT_CHECK_ARG((long)L * 3 * nH * hd * 4 < 0x7fff0000L, "%s: one image's qkv rows must fit a 2 GiB buffer descriptor", who);
+    if (rel_table) {  // NULL: bias_frag_ws still holds the fragment-order bias an earlier call put there
+        int rc = fill_bias_frag(rel_table, ws, N, nH, bias_frag_ws, stream);
+        if (rc != ESVIT_OK) return rc;
+    }
+    const int Bw = nB * nW;
+    int parts = (hd == HD ? 1536 : 1024) / nH;  // the forward's walk (two images instead of three: no more than its registers)
+    if (parts < 1) parts = 1;
+    if (parts > Bw) parts = Bw;
+#define LAUNCH_STATS(TT, HH)                                                                                                    \
+    {                                                                                                                           \
+        const size_t lds = (size_t)2 * AttnCfgH<TT, HH>::QK_ELEMS * sizeof(TT);                                                 \
+        auto kern = attn_stats4_kernel<TT, HH>;                                                                                 \
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);   \
+        hipLaunchKernelGGL(kern, dim3(parts * nH), dim3(128), lds, stream, (const TT*)qkv, qkv_bias, win2tok, L,                \
+                           (const float*)bias_frag_ws, region_ids, nW, Bw, N, nH, scale, parts, slots, nq, attn_out, lse);      \
+    }
+    if (dtype == ESVIT_BF16) {
+        if (hd == HD) LAUNCH_STATS(bf16, 32) else LAUNCH_STATS(bf16, 64)
+    } else {
+        if (hd == HD) LAUNCH_STATS(float, 32) else LAUNCH_STATS(float, 64)
+    }
+#undef LAUNCH_STATS
+    ESVIT_CHECK_LAUNCH("window_attn_fwd(window stats)");
+    return ESVIT_OK;
+}
+
 extern "C" int esvit_window_attn_fwd(int dtype, const void* qkv, const float* qkv_bias, const int32_t* win2tok, int L,
                                      const float* rel_table, int ws, float* bias_frag_ws, const int32_t* region_ids, int nW, int nB, int N,
                                      int nH, int hd, float scale, void* out, float* lse, float* attn_out, esvit_stream_t s_) {
     STREAM(s_);
+    if (ws > 0 && (ws & ESVIT_ATTN_WINDOW_STATS))  // entropy and listed rows of the window softmax
+        return window_attn_stats(dtype, qkv, qkv_bias, win2tok, L, rel_table, ws, bias_frag_ws, region_ids, nW, nB, N, nH, hd, scale, out, lse,
+                                 attn_out, stream);
     ESVIT_CHECK_ARG(!(ws > 0 && (ws & ESVIT_ATTN_STATS)) || (ws & ESVIT_ATTN_GLOBAL),
                     "esvit_window_attn_fwd: ESVIT_ATTN_STATS is valid only together with ESVIT_ATTN_GLOBAL (ws = 0x%x)", (unsigned)ws);
     if (ws > 0 && (ws & ESVIT_ATTN_GLOBAL) && (ws & ESVIT_ATTN_STATS) && !(ws & ESVIT_ATTN_SLIDING_CHUNK))  // entropy and listed rows of P
@@ -887,8 +1147,10 @@ extern "C" int esvit_window_attn_bwd(int dtype, const void* qkv, const float* qk
                                      const int32_t* region_ids, int nW, int nB, int N, int nH, int hd, float scale, void* dqkv,
                                      float* dbias_ws, float* dpad_ws, esvit_stream_t s_) {
     STREAM(s_);
+    ESVIT_CHECK_ARG(!(ws > 0 && (ws & ESVIT_ATTN_WINDOW_STATS)),
+                    "esvit_window_attn_bwd: ESVIT_ATTN_WINDOW_STATS is valid in esvit_window_attn_fwd only (ws = 0x%x)", (unsigned)ws);
     ESVIT_CHECK_ARG(!(ws > 0 && (ws & ESVIT_ATTN_STATS)) || (ws & ESVIT_ATTN_GLOBAL),
-                    "esvit_window_attn_bwd: ESVIT_ATTN_STATS is valid only together with ESVIT_ATTN_GLOBAL, in esvit_window_attn_fwd (ws = 0x%x)", (unsigned)ws);
+                    "esvit_window_attn_bwd:ESVIT_ATTN_STATS is valid only together with ESVIT_ATTN_GLOBAL, in esvit_window_attn_fwd (ws = 0x%x)", (unsigned)ws);
     if (ws > 0 && (ws & ESVIT_ATTN_GLOBAL))
         return esvit_flash_attn_bwd(dtype, qkv, L, dout, fwd_out, lse, ws, bias_frag_ws, nW, nB, N, nH, hd, scale, dqkv, stream);
     if (ws > 0 && (ws & ESVIT_ATTN_SLIDING_CHUNK))

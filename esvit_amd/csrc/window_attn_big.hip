@@ -374,6 +374,118 @@ __global__ __launch_bounds__(FWD3_WAVES * 64, sizeof(T) == 2 ? (HD == 32 ? 4 : 2
     }
 }
 
+// Statistics of the window softmax (ws | ESVIT_ATTN_WINDOW_STATS, esvit_hip.h): the probability variant of attn_big_fwd3_kernel up to its
+// probabilities -- the same tables, staged K and scale * Q tiles, score tiles, maximum, exponentials and sum, every query tile computed
+// -- and then, where it stores P and multiplies by V, the entropy of every query row (H = ln l - sum_k e_k x_k / l, x = s - m,
+// e = exp(x); a key whose e is zero, the -1e30 columns beyond N among them, adds nothing) and the probability rows of the listed
+// slots.  No V image: the workgroup holds K and the seven Q tiles.  One writer per element; a listed slot outside [0, nW * N) matches
+// no window and is skipped.
+template <typename T, int HD>
+__global__ __launch_bounds__(FWD3_WAVES * 64, sizeof(T) == 2 ? (HD == 32 ? 4 : 2) : 1) void attn_big_stats_kernel(
+    const T* __restrict__ qkv, const float* __restrict__ qkv_bias, const int* __restrict__ win2tok, int L,
+    const float* __restrict__ bias_frag, int ws, const int* __restrict__ region_ids, int nW, int Bw, int N, int nH,
+    float scale, const int* __restrict__ slots, int nq, float* __restrict__ ent, float* __restrict__ rows) {
+    using Cfg = BigCfg<T, HD>;
+    constexpr int LDQ = Cfg::LDQ;
+    constexpr int KS = HD / 32;
+    constexpr int TILE = 16 * LDQ;
+    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+    const BigTables tb = carve_tables(smem_raw);
+    T* Ks = reinterpret_cast<T*>(smem_raw + Cfg::TABLE_BYTES);
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int c = lane & 15, g = lane >> 4;
+    T* Qs = Ks + Cfg::FULL + wave * TILE;  // this wave's [16][LDQ] image of its Q tile
+
+    const int unit = xcd_contiguous_id(blockIdx.x, gridDim.x);  // (bw, h); the heads of a window share an XCD
+    const int bw = unit / nH, h = unit % nH;
+    const int C = nH * HD;
+    const long tok_base = (long)(bw / nW) * L;
+    const T* src = qkv + h * HD;
+    const bool masked = region_ids != nullptr;
+    const float* bias_h = bias_frag + (long)h * (NT * NT * 256);
+
+    load_window_tables(tb, win2tok, region_ids, bw % nW, N, ws, true);
+    __syncthreads();
+    SlotStage<T, 16, 64, HD> sq;
+    const Vec16<T> padq = SlotStage<T, 16, 64, HD>::pad_piece(qkv_bias + h * HD, lane);
+    {
+        SlotStage<T, NPB, FWD3_WAVES * 64, HD> sk;
+        const Vec16<T> padk = SlotStage<T, NPB, FWD3_WAVES * 64, HD>::pad_piece(qkv_bias + C + h * HD, threadIdx.x);
+        sk.load(src + C, 3L * C, tb.tok, tok_base, 0, N, &padk, threadIdx.x);
+        sq.load(src, 3L * C, tb.tok, tok_base, 16 * wave, N, &padq, lane);
+        sk.store(Ks, 1.f, threadIdx.x);
+        sq.store(Qs, scale, lane);
+    }
+    __syncthreads();  // K complete (whole workgroup); everything below is private to the wave
+
+#pragma unroll
+    for (int pass = 0; pass < 2; ++pass) {
+        const int q0 = 16 * (wave + pass * FWD3_WAVES);
+        if (pass > 0) {
+            __builtin_amdgcn_wave_barrier();
+            sq.store(Qs, scale, lane);
+            __builtin_amdgcn_wave_barrier();
+        }
+        Frag<T> qf[KS];
+#pragma unroll
+        for (int ks = 0; ks < KS; ++ks) qf[ks] = frag_kc<T>(Qs, LDQ, 0, 32 * ks, c, g);
+        if (pass == 0) sq.load(src, 3L * C, tb.tok, tok_base, 16 * (wave + FWD3_WAVES), N, &padq, lane);
+        const int rq = masked ? ((tb.pk[q0 + c] >> 16) & 0xff) : 0;
+        f32x4 p[NT];
+#pragma unroll
+        for (int i = 0; i < NT; ++i) {
+            f32x4 b = *reinterpret_cast<const f32x4*>(bias_h + ((i * NT + (q0 >> 4)) * 64 + lane) * 4);
+            if (masked) {
+                const i32x4 pk4 = *reinterpret_cast<const i32x4*>(tb.pk + 16 * i + 4 * g);
+#pragma unroll
+                for (int r = 0; r < 4; ++r) b[r] += (((pk4[r] >> 16) & 0xff) != rq) ? -100.f : 0.f;
+            }
+            p[i] = b;
+#pragma unroll
+            for (int ks = 0; ks < KS; ++ks) mma(frag_kc<T>(Ks, LDQ, 16 * i, 32 * ks, c, g), qf[ks], p[i]);
+        }
+        float m = -3.0e38f;
+#pragma unroll
+        for (int i = 0; i < NT; ++i)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) m = fmaxf(m, p[i][r]);
+        m = fmaxf(m, __shfl_xor(m, 16, 64));
+        m = fmaxf(m, __shfl_xor(m, 32, 64));
+        float sum = 0.f, ex = 0.f;
+#pragma unroll
+        for (int i = 0; i < NT; ++i)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const float x = p[i][r] - m;
+                const float e = __expf(x);
+                p[i][r] = e;
+                sum += e;
+                ex += e * x;
+            }
+        sum += __shfl_xor(sum, 16, 64);
+        sum += __shfl_xor(sum, 32, 64);
+        ex += __shfl_xor(ex, 16, 64);
+        ex += __shfl_xor(ex, 32, 64);
+        const float inv = 1.f / sum;
+#pragma unroll
+        for (int i = 0; i < NT; ++i) p[i] *= inv;
+        if (g == 0 && q0 + c < N) ent[(long)unit * N + q0 + c] = __logf(sum) - ex * inv;
+        for (int n = 0; n < nq; ++n) {
+            const int slot = slots[n];
+            if ((unsigned)slot >= (unsigned)(nW * N) || slot / N != bw % nW) continue;  // (workgroup-uniform)
+            if (slot % N != q0 + c) continue;
+            float* row = rows + ((((long)(bw / nW) * nH + h) * nq + n) * N);
+#pragma unroll
+            for (int i = 0; i < NT; ++i)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const int key = 16 * i + 4 * g + r;
+                    if (key < N) row[key] = p[i][r];
+                }
+        }
+    }
+}
+
 // -------------------------------------------------------------------------------------------------------------
 // backward, second generation (default).  Same split (dQ + bias gradient | dK, dV) and the same mathematics; changes:
 //   * dS / P never go through LDS: a score tile leaves its 4 accumulator rows per lane in exactly the k-slots an MFMA A
@@ -962,6 +1074,37 @@ int esvit_big_attn_fwd(int dtype, const void* qkv, const float* qkv_bias, const 
     if (dtype == ESVIT_BF16)
         return big_fwd_launch<bf16, 32>(qkv, qkv_bias, win2tok, L, bias_frag_ws, ws, region_ids, nW, Bw, N, nH, scale, out, lse, attn_out, stream);
     return big_fwd_launch<float, 32>(qkv, qkv_bias, win2tok, L, bias_frag_ws, ws, region_ids, nW, Bw, N, nH, scale, out, lse, attn_out, stream);
+}
+
+template <typename T, int HD>
+static int big_stats_launch(const void* qkv, const float* qkv_bias, const int32_t* win2tok, int L, const float* bias_frag, int ws,
+                            const int32_t* region_ids, int nW, int Bw, int N, int nH, float scale, const int32_t* slots, int nq, float* ent,
+                            float* rows, hipStream_t stream) {
+    using Cfg = BigCfg<T, HD>;
+    const size_t lds = Cfg::TABLE_BYTES + (size_t)(Cfg::FULL + FWD3_WAVES * 16 * Cfg::LDQ) * sizeof(T);
+    auto kern = attn_big_stats_kernel<T, HD>;
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    hipLaunchKernelGGL(kern, dim3(Bw * nH), dim3(FWD3_WAVES * 64), lds, stream, (const T*)qkv, qkv_bias, win2tok, L, bias_frag, ws, region_ids,
+                       nW, Bw, N, nH, scale, slots, nq, ent, rows);
+    ESVIT_CHECK_LAUNCH("window_attn_fwd(window stats, 14x14)");
+    return ESVIT_OK;
+}
+
+// the window-statistics mode for 64 < N <= 224 (the caller, window_attn.hip, has checked the arguments)
+int esvit_big_attn_stats(int dtype, const void* qkv, const float* qkv_bias, const int32_t* win2tok, int L, const float* rel_table, int ws,
+                         float* bias_frag_ws, const int32_t* region_ids, int nW, int nB, int N, int nH, int hd, float scale,
+                         const int32_t* slots, int nq, float* ent, float* rows, hipStream_t stream) {
+    ESVIT_CHECK_ARG(N <= NPB && (hd == 32 || (hd == 64 && dtype == ESVIT_BF16)), "window_attn (window stats): %d tokens at head_dim %d", N, hd);
+    {
+        int rc = rel_table ? fill_bias_frag_big(rel_table, ws, N, nH, bias_frag_ws, stream) : ESVIT_OK;
+        if (rc != ESVIT_OK) return rc;
+    }
+    const int Bw = nB * nW;
+    if (hd == 64)
+        return big_stats_launch<bf16, 64>(qkv, qkv_bias, win2tok, L, bias_frag_ws, ws, region_ids, nW, Bw, N, nH, scale, slots, nq, ent, rows, stream);
+    if (dtype == ESVIT_BF16)
+        return big_stats_launch<bf16, 32>(qkv, qkv_bias, win2tok, L, bias_frag_ws, ws, region_ids, nW, Bw, N, nH, scale, slots, nq, ent, rows, stream);
+    return big_stats_launch<float, 32>(qkv, qkv_bias, win2tok, L, bias_frag_ws, ws, region_ids, nW, Bw, N, nH, scale, slots, nq, ent, rows, stream);
 }
 
 template <typename T, int HD>

@@ -359,6 +359,8 @@ def _block_forward(x, geom, nH, index, dp, prm, wts, save, w1p=None, wattn=None)
         qkv = o.linear_fwd(xw, Wqkv, bqkv)
         ao, lse = o.window_attn_fwd(qkv, bqkv, geom.win2tok, L, table, geom.ws, geom.region_ids, geom.nW, geom.N, nH, scale, bias_frag=frag)
         x1 = o.linear_fwd(ao, Wproj, bproj, residual=x2d, rowscale=dp1, rows_per_sample=L, out_f32=True)
+    if not save:  # inference keeps nothing for a backward: the attention branch's intermediates go before the MLP allocates its own
+        xw = qkv = ao = None
     if (not save and _mlp_fused_infer(W1, C)) or (save and _mlp_fused_train(W1, C)):
         rs2 = None if dp2 is None else dp2.repeat_interleave(L)  # (the fused kernels take per-row DropPath factors)
         x2 = o.mlp_fused_fwd(x1, g2, b2, LN_EPS, W1 if C == 384 else _mlp_w(w1p, "MLP_W1_FWD"), bfc1, W2, bfc2, rowscale=rs2)
@@ -373,6 +375,7 @@ def _block_forward(x, geom, nH, index, dp, prm, wts, save, w1p=None, wattn=None)
             a1g, a1 = o.linear_fwd(h, W1, bfc1, gelu=True, want_preact=True)
         else:
             a1g, a1 = o.linear_fwd(h, W1, bfc1, gelu=True), None
+            h = None
         x2 = o.linear_fwd(a1g, W2, bfc2, residual=x1, rowscale=dp2, rows_per_sample=L, out_f32=True)
     saved = (mean1, rstd1, xw, qkv, ao, x1, mean2, rstd2, h, a1, a1g, lse, frag) if save else None
     return x2.view(nB, L, C), saved
@@ -676,6 +679,54 @@ def swin_block_attention(x, geom, nH, index, prm_list):
     _, _, attn = o.window_attn_fwd(qkv, bqkv, geom.win2tok, L, table, geom.ws, geom.region_ids, geom.nW, geom.N, nH, (C // nH) ** -0.5,
                                    want_attn=True)
     return attn
+
+
+def _window_stats_route(o, dtype, N, hd):
+    """do the window statistics take the kernels (ops.window_attn_stats)?  When the ops module has the entry and supports the shape; an
+    ops module without it (the CPU restatement, oracle/ops_ref.py) or an unsupported shape reduces the maps of window_attn_fwd"""
+    if not hasattr(o, "window_attn_stats"):
+        return False
+    sup = getattr(o, "window_attn_stats_supported", None)
+    return sup is not None and bool(sup(dtype, N, hd))
+
+
+def window_attention_stats(o, qkv, qkv_bias, geom, L, table, nH, scale, slots=None):
+    """what an attention analysis reads of a block's window softmax, token-ordered qkv [nB * L, 3C] -> (entropy fp32 [nB * nW, nH, N] in
+    nats with 0 log 0 = 0, window-slot order; rows fp32 [nB, nH, nq, N] of the listed slots w * N + i over their own windows, or None).
+    The statistics mode of the window kernels never forms a map; the fall-back forms the maps of o.window_attn_fwd(want_attn=True) for a
+    slice of the batch at a time and reduces them in torch."""
+    nW, N = geom.nW, geom.N
+    hd = qkv.shape[1] // 3 // nH
+    if _window_stats_route(o, qkv.dtype, N, hd):
+        return o.window_attn_stats(qkv, qkv_bias, geom.win2tok, L, table, geom.ws, geom.region_ids, nW, N, nH, scale, slots=slots)
+    idx = None
+    if slots is not None:
+        idx = torch.as_tensor(list(slots) if isinstance(slots, range) else slots, device=qkv.device).reshape(-1).long()
+        if idx.numel() and not (0 <= int(idx.min()) and int(idx.max()) < nW * N):
+            raise ValueError("window_attention_stats: slot indices must lie in [0, %d)" % (nW * N))
+    nB = qkv.shape[0] // L
+    step = max(1, _STATS_SLICE_ELEMS // (nW * nH * N * N))
+    ents, rows = [], []
+    for b0 in range(0, nB, step):
+        nb = min(step, nB - b0)
+        p = o.window_attn_fwd(qkv[b0 * L:(b0 + nb) * L], qkv_bias, geom.win2tok, L, table, geom.ws, geom.region_ids, nW, N, nH, scale,
+                              want_attn=True)[2].float()
+        ents.append(torch.special.entr(p).sum(-1))
+        if idx is not None:  # [nb, nW, nH, N, N] -> the rows (window, query) of the list: [nb, nH, nq, N]
+            rows.append(p.view(nb, nW, nH, N, N)[:, idx // N, :, idx % N].permute(1, 2, 0, 3) if idx.numel()
+                        else p.new_zeros(nb, nH, 0, N))
+    return torch.cat(ents), (torch.cat(rows) if idx is not None else None)
+
+
+def swin_block_attention_stats(x, geom, nH, index, prm_list, slots=None):
+    """window_attention_stats of a block's attention on its input x fp32 [nB, L, C] (LayerNorm and the qkv projection are recomputed, as
+    swin_block_attention does); inference only."""
+    o = ops_module()
+    g1, b1, table, Wqkv, bqkv = prm_list[:5]
+    nB, L, C = x.shape
+    xw, _, _, _ = o.layernorm_fwd(x.contiguous().view(nB * L, C), g1, b1, LN_EPS)
+    qkv = o.linear_fwd(xw, _weight(Wqkv), bqkv)
+    return window_attention_stats(o, qkv, bqkv, geom, L, table, nH, (C // nH) ** -0.5, slots)
 
 
 # ------------------------------------------------------------------------------------------------

@@ -781,6 +781,63 @@ def window_attn_fwd(qkv, qkv_bias, win2tok, L, rel_table, ws, region_ids, nW, N,
     return (out, lse, attn) if want_attn else (out, lse)
 
 
+# ---- statistics of the window softmax (csrc/window_attn.hip, window_attn_big.hip): entropy of every row and a few rows of P, without P --
+ATTN_WINDOW_STATS = 0x04000000  # ESVIT_ATTN_WINDOW_STATS: OR'd into a real window side, selects the statistics mode of esvit_window_attn_fwd
+
+
+def window_attn_stats_supported(dtype, N, hd):
+    """the statistics kernels exist for this shape: every instance the probability variant of window_attn_fwd has"""
+    if dtype not in (torch.bfloat16, torch.float32) or hd not in (32, 64) or not 0 < N <= 224:
+        return False
+    return N <= 64 or hd == 32 or dtype == torch.bfloat16
+
+
+def _stats_slots(slots, nslots, device):
+    """a list / range / int tensor of window slots w * N + i -> int32 device tensor, every index checked against [0, nW * N) here: the
+    library cannot read the array"""
+    if torch.is_tensor(slots):
+        s = slots.reshape(-1)
+        assert not s.dtype.is_floating_point and s.dtype != torch.bool, "slots: integer slot indices"
+        if s.numel():
+            lo, hi = int(s.min()), int(s.max())
+            if lo < 0 or hi >= nslots:
+                raise ValueError("window_attn_stats: slot indices must lie in [0, %d), got %d .. %d" % (nslots, lo, hi))
+        return s.to(device=device, dtype=torch.int32).contiguous()
+    idx = [int(i) for i in slots]
+    bad = [i for i in idx if not 0 <= i < nslots]
+    if bad:
+        raise ValueError("window_attn_stats: slot indices must lie in [0, %d), got %r" % (nslots, bad[:8]))
+    return torch.tensor(idx, dtype=torch.int32, device=device)
+
+
+def window_attn_stats(qkv, qkv_bias, win2tok, L, rel_table, ws, region_ids, nW, N, nH, scale, slots=None, bias_frag=None, ent_out=None,
+                      rows_out=None):
+    """what an attention analysis reads of the softmax window_attn_fwd computes, without the maps: token-ordered qkv [nB*L, 3C] ->
+    (entropy fp32 [nB*nW, nH, N] in nats, window-slot order, pad query slots included; rows fp32 [nB, nH, nq, N] or None: the
+    probability row, over the N slots of its own window, of every listed slot w * N + i in [0, nW * N) -- the same list for every image
+    and head, duplicates allowed).  ent_out / rows_out: optional contiguous fp32 destinations of those shapes."""
+    qkv = _actc(qkv)
+    rows_, C3 = qkv.shape
+    Cc = C3 // 3
+    nB = rows_ // L
+    sidx = None if slots is None else _stats_slots(slots, nW * N, qkv.device)
+    nq = 0 if sidx is None else sidx.numel()
+    if nq >= 1 << 15:
+        raise ValueError("window_attn_stats: at most %d listed slots, got %d" % ((1 << 15) - 1, nq))
+    ent = torch.empty((nB * nW, nH, N), dtype=torch.float32, device=qkv.device) if ent_out is None else ent_out
+    rows = None
+    if slots is not None:
+        rows = torch.empty((nB, nH, nq, N), dtype=torch.float32, device=qkv.device) if rows_out is None else rows_out
+    for t, shape in ((ent, (nB * nW, nH, N)), (rows, (nB, nH, nq, N))):
+        assert t is None or (t.shape == shape and t.dtype == torch.float32 and t.is_contiguous()), (shape, t.shape)
+    bias_ws = bias_frag if bias_frag is not None else workspace(2 * nH * attn_frag_elems(N), qkv.device, slot=2)
+    assert rel_table is not None or bias_frag is not None
+    check(lib.esvit_window_attn_fwd(_code(qkv.dtype), _p(qkv), _p(_f32c(qkv_bias)), _p(win2tok), L, _p(None if rel_table is None else _f32c(rel_table)),
+                                    ws | ATTN_WINDOW_STATS, _p(bias_ws), _p(region_ids), nW, nB, N | (nq << 16), nH, Cc // nH, scale,
+                                    _p(sidx) if nq else None, _p(rows) if nq else None, _p(ent), _stream()), "window_attn_fwd(window stats)")
+    return ent, rows
+
+
 def attn_branch_supported(dt, Cc, nH, N, rows=0, windows=0):
     """the fused attention branch (esvit_attn_branch_fwd) exists for this shape: bf16, head_dim 32, C in {96, 192}, <= 64-token windows,
     and -- when given -- a call of `rows` token rows / `windows` windows stays inside the kernel's 2 GiB buffer ranges and 2^22-window

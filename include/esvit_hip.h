@@ -474,11 +474,32 @@ int esvit_attn_branch_fwd(int dtype, const float* x, const float* gamma, const f
  *   hd, dtype, scale: as in the global mode
  *   out must be NULL;  qkv_bias, rel_table, region_ids, bias_frag_ws: not used, pass NULL
  * Every element has one writer; no atomics: two launches give identical bits.
+ *
+ * Statistics of the window softmax (ws | ESVIT_ATTN_WINDOW_STATS, a real window side with the flag OR'd in; esvit_window_attn_fwd only;
+ * window_attn.hip / window_attn_big.hip): the Swin counterpart of the mode above.  For every (image, window, head) exactly the
+ * softmax the forward computes -- staged scale * q with the forward's rounding, pad slots with q, k = qkv bias, the relative-position
+ * bias from rel_table / bias_frag_ws (rel_table = NULL: the fragment is already filled), the additive -100 of region_ids, one softmax
+ * over the N slots of the window, pad keys included -- and no v, no P V, no out, no N x N tensor.  The arguments mean:
+ *   qkv, qkv_bias, win2tok, L, rel_table, bias_frag_ws, region_ids, nW, nB, nH, hd, scale: as in the forward
+ *   N            tokens per window | nq << 16, nq >= 0 the number of listed slots (N <= 224 leaves the upper bits free)
+ *   attn_out     fp32 [nB*nW, nH, N] (required): the entropy of every query slot's row, pad query slots included, in window-slot order
+ *                (the rows the forward's attn_out would hold), in nats: H = ln l - sum_k e^(s_k - m) (s_k - m) / l, m and l the row's
+ *                maximum and sum; 0 log 0 = 0 by construction, the padded MFMA columns beyond N do not enter
+ *   out          int32 [nq] on the device: the listed query slots, w * N + i in [0, nW * N), the same for every image and head;
+ *                duplicates allowed.  The library cannot read the array: the caller checks the range (an index outside it is skipped,
+ *                its row stays unwritten, nothing is read or written out of bounds)
+ *   lse          fp32 [nB, nH, nq, N]: the probability row of every listed slot over the N slots of its own window, written by the
+ *                workgroup that owns the window (one writer per element)
+ *   nq = 0: out and lse must be NULL.  nq > 0: both are required.
+ * Instances: every one the probability variant has -- N <= 64 at head_dim 32 / 64 in bf16 and fp32, 64 < N <= 224 at head_dim 32 in both
+ * and at head_dim 64 in bf16, N < ws * ws as in the forward; anything else is ESVIT_ERR_ARG before any launch, as is the flag in
+ * esvit_window_attn_bwd or together with any of the other three flags.  No atomics: two launches give identical bits.
  */
 #define ESVIT_ATTN_SLIDING_CHUNK 0x40000000
 #define ESVIT_ATTN_GLOBAL 0x20000000
 #define ESVIT_ATTN_STATS 0x08000000
 #define ESVIT_ATTN_SPLIT_DBIAS 0x10000000
+#define ESVIT_ATTN_WINDOW_STATS 0x04000000
 int esvit_window_attn_fwd(int dtype, const void* qkv, const float* qkv_bias, const int32_t* win2tok, int L,
                           const float* rel_table, int ws, float* bias_frag_ws, const int32_t* region_ids, int nW, int nB,
                           int N, int nH, int hd, float scale, void* out, float* lse, float* attn_out,
