@@ -20,6 +20,7 @@
 #include "common.h"
 #include "mfma.h"
 #include "relpos_fold.h"
+#include "window_softmax.h"
 #include "../../include/esvit_hip.h"
 
 namespace {
@@ -65,14 +66,22 @@ __device__ __forceinline__ f32x4 load_frag4(const T* p) {
     }
 }
 
-// -------------------------------------------------------------------------------------------------
-// Forward, second generation (the default): the first-generation kernel above spent 64% of its wave cycles parked
-// on a serial chain (slot map -> row loads -> LDS -> compute -> store) with one window per wave.  Here a wave owns one
-// head and a strided set of windows, requests the q, k, v rows of window it+1 (and the slot map of window it+2) while
-// it computes window `it`, synchronises only with itself, and stores 16-byte rows.  Same math, same LDS images.
+// The shift mask on one bias tile of the 64-slot kernels: -100 where the region of the tile's key r (rk[r]) is not the region of the
+// lane's query (rq).  attn_stats4_kernel and attn_bwd3_kernel take it from here; attn_fwd4_kernel keeps its own score and softmax text:
+// through the shared functions its bf16 instances measured about 1 % slower on one row of tools/bench_attn.py
+// (profiles/window_attn_shared_ab.json).
+__device__ __forceinline__ f32x4 shift_masked(f32x4 b, bool masked, const int (&rk)[4], int rq) {
+    if (masked) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) b[r] += (rk[r] != rq) ? -100.f : 0.f;
+    }
+    return b;
+}
 
-// Forward (the fourth generation; its predecessors are gone): a wave pair per (window, head), P kept in registers and V staged in its natural [key][d]
-// layout -- no P image, no 2-byte transposed V stores (16 per thread and window), one block barrier less per window.
+// -------------------------------------------------------------------------------------------------
+// Forward: a wave pair per (window, head), persistent over a strided set of windows (the rows of window it + 1 and the slot map of
+// window it + 2 travel while window `it` is computed); P kept in registers and V staged in its natural [key][d] layout -- no P image,
+// no 2-byte transposed V stores.
 template <typename T, bool WANT_ATTN, int HDIM>
 __global__ __launch_bounds__(128, (HDIM == 32 ? 3 : 2)) void attn_fwd4_kernel(const T* __restrict__ qkv, const float* __restrict__ qkv_bias,
                                                           const int* __restrict__ win2tok, int L, const float* __restrict__ bias_frag,
@@ -419,45 +428,16 @@ __global__ __launch_bounds__(128, (HDIM == 32 ? 3 : 2)) void attn_stats4_kernel(
                 for (int r = 0; r < 4; ++r) rk[r] = __shfl(myreg, 16 * i + 4 * g + r, 64);
 #pragma unroll
                 for (int jl = 0; jl < 2; ++jl) {
-                    f32x4 b = *reinterpret_cast<const f32x4*>(bias_f + ((i * 4 + 2 * w + jl) * 64 + lane) * 4);
-                    if (masked) {
-#pragma unroll
-                        for (int r = 0; r < 4; ++r) b[r] += (rk[r] != rq[jl]) ? -100.f : 0.f;
-                    }
-                    p[i][jl] = b;
+                    p[i][jl] = shift_masked(*reinterpret_cast<const f32x4*>(bias_f + ((i * 4 + 2 * w + jl) * 64 + lane) * 4), masked, rk, rq[jl]);
 #pragma unroll
                     for (int ks = 0; ks < KS; ++ks) mma(kf[i][ks], qf[jl][ks], p[i][jl]);
                 }
             }
+        }
 #pragma unroll
-            for (int jl = 0; jl < 2; ++jl) {
-                float m = -3.0e38f;
-#pragma unroll
-                for (int i = 0; i < 4; ++i)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) m = fmaxf(m, p[i][jl][r]);
-                m = fmaxf(m, __shfl_xor(m, 16, 64));
-                m = fmaxf(m, __shfl_xor(m, 32, 64));
-                float sum = 0.f, ex = 0.f;
-#pragma unroll
-                for (int i = 0; i < 4; ++i)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        const float x = p[i][jl][r] - m;
-                        const float e = __expf(x);
-                        p[i][jl][r] = e;
-                        sum += e;
-                        ex += e * x;
-                    }
-                sum += __shfl_xor(sum, 16, 64);
-                sum += __shfl_xor(sum, 32, 64);
-                ex += __shfl_xor(ex, 16, 64);
-                ex += __shfl_xor(ex, 32, 64);
-                const float inv = 1.f / sum;
-#pragma unroll
-                for (int i = 0; i < 4; ++i) p[i][jl] *= inv;
-                hq[jl] = __logf(sum) - ex * inv;
-            }
+        for (int jl = 0; jl < 2; ++jl) {
+            const ColSoftmax sm = column_softmax<true>(p, jl);
+            hq[jl] = __logf(sm.sum) - sm.ex * sm.inv;
         }
         if (active && g == 0) {
 #pragma unroll
@@ -664,42 +644,16 @@ __global__ __launch_bounds__(128, (HDIM == 32 ? 2 : 1)) void attn_bwd3_kernel(co
                 for (int r = 0; r < 4; ++r) rk[r] = __shfl(myreg, 16 * i + 4 * g + r, 64);
 #pragma unroll
                 for (int jl = 0; jl < 2; ++jl) {
-                    f32x4 b = bias_r[i][jl];
-                    if (masked) {
-#pragma unroll
-                        for (int r = 0; r < 4; ++r) b[r] += (rk[r] != rq[jl]) ? -100.f : 0.f;
-                    }
-                    p[i][jl] = b;
+                    p[i][jl] = shift_masked(bias_r[i][jl], masked, rk, rq[jl]);
 #pragma unroll
                     for (int ks = 0; ks < KS; ++ks) mma(kf[i][ks], qf[jl][ks], p[i][jl]);
                 }
             }
 #pragma unroll
             for (int jl = 0; jl < 2; ++jl) {
-                float m = -3.0e38f;
+                column_softmax<false>(p, jl);
 #pragma unroll
-                for (int i = 0; i < 4; ++i)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) m = fmaxf(m, p[i][jl][r]);
-                m = fmaxf(m, __shfl_xor(m, 16, 64));
-                m = fmaxf(m, __shfl_xor(m, 32, 64));
-                float s = 0.f;
-#pragma unroll
-                for (int i = 0; i < 4; ++i)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        const float e = __expf(p[i][jl][r] - m);
-                        p[i][jl][r] = e;
-                        s += e;
-                    }
-                s += __shfl_xor(s, 16, 64);
-                s += __shfl_xor(s, 32, 64);
-                const float inv = 1.f / s;
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    p[i][jl] *= inv;
-                    store_frag4<T>(Ps + (16 * (2 * w + jl) + c) * LDP + 16 * i + 4 * g, p[i][jl]);
-                }
+                for (int i = 0; i < 4; ++i) store_frag4<T>(Ps + (16 * (2 * w + jl) + c) * LDP + 16 * i + 4 * g, p[i][jl]);
             }
         }
         __syncthreads();  // P complete (both waves' query tiles)
@@ -928,6 +882,16 @@ __global__ __launch_bounds__(256) void relpos_bias_bwd_fold_kernel(const float* 
     }
 }
 
+inline int fwd_parts(int hd, int nH, int Bw) {
+    // persistent wave pairs, one head each, at most one window per pair; exactly as many as the chip keeps resident (163
+    // registers -> three waves per SIMD -> six two-wave workgroups per CU x 256 CUs; 208 registers at head_dim 64 -> four): a
+    // larger grid runs a second, partly empty round (2560 workgroups were 5-12 % slower, tools/bench_attn.py)
+    int parts = (hd == HD ? 1536 : 1024) / nH;  // (rounded DOWN: one workgroup more than the chip holds costs a second round)
+    if (parts < 1) parts = 1;
+    if (parts > Bw) parts = Bw;
+    return parts;
+}
+
 inline int bwd_parts(int Bw, int nH) {
     // as many wave pairs as the chip keeps resident and NOT ONE MORE: 256 CUs x 4 two-wave workgroups (256 registers, 34.6 KB
     // of LDS each); parts * nH workgroups are launched, so round DOWN -- a 1025th workgroup would start only when another has
@@ -937,6 +901,21 @@ inline int bwd_parts(int Bw, int nH) {
     if (parts < 1) parts = 1;
     return parts;
 }
+
+// one of the three 128-thread kernels (a wave pair per (part, head): `units` workgroups) with `lds` bytes of dynamic LDS; the
+// arguments are converted to the kernel's parameter types (the entry points hold their tensors as void pointers)
+template <typename... P, typename... A>
+void launch_pairs(void (*kern)(P...), size_t lds, int units, hipStream_t stream, A... args) {
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    hipLaunchKernelGGL(kern, dim3(units), dim3(128), lds, stream, (P)args...);
+}
+// F(element type, head_dim) for the (dtype, hd) of a call: bf16 or fp32, 32 or 64
+#define FOR_DTYPE_HD(F)                      \
+    if (dtype == ESVIT_BF16) {               \
+        if (hd == HD) F(bf16, 32) else F(bf16, 64) \
+    } else {                                 \
+        if (hd == HD) F(float, 32) else F(float, 64) \
+    }
 
 }  // namespace
 
@@ -1064,23 +1043,12 @@ static int window_attn_stats(int dtype, const void* qkv, const float* qkv_bias, 
         if (rc != ESVIT_OK) return rc;
     }
     const int Bw = nB * nW;
-    int parts = (hd == HD ? 1536 : 1024) / nH;  // the forward's walk (two images instead of three: no more than its registers)
-    if (parts < 1) parts = 1;
-    if (parts > Bw) parts = Bw;
-#define LAUNCH_STATS(TT, HH)                                                                                                    \
-    {                                                                                                                           \
-        const size_t lds = (size_t)2 * AttnCfgH<TT, HH>::QK_ELEMS * sizeof(TT);                                                 \
-        auto kern = attn_stats4_kernel<TT, HH>;                                                                                 \
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);   \
-        hipLaunchKernelGGL(kern, dim3(parts * nH), dim3(128), lds, stream, (const TT*)qkv, qkv_bias, win2tok, L,                \
-                           (const float*)bias_frag_ws, region_ids, nW, Bw, N, nH, scale, parts, slots, nq, attn_out, lse);      \
-    }
-    if (dtype == ESVIT_BF16) {
-        if (hd == HD) LAUNCH_STATS(bf16, 32) else LAUNCH_STATS(bf16, 64)
-    } else {
-        if (hd == HD) LAUNCH_STATS(float, 32) else LAUNCH_STATS(float, 64)
-    }
-#undef LAUNCH_STATS
+    const int parts = fwd_parts(hd, nH, Bw);  // the forward's walk (two images instead of three: no more than its registers)
+#define LAUNCH(TT, HH)                                                                                                                   \
+    launch_pairs(attn_stats4_kernel<TT, HH>, 2 * AttnCfgH<TT, HH>::QK_ELEMS * sizeof(TT), parts * nH, stream, qkv, qkv_bias, win2tok, L, \
+                 bias_frag_ws, region_ids, nW, Bw, N, nH, scale, parts, slots, nq, attn_out, lse);
+    FOR_DTYPE_HD(LAUNCH)
+#undef LAUNCH
     ESVIT_CHECK_LAUNCH("window_attn_fwd(window stats)");
     return ESVIT_OK;
 }
@@ -1118,26 +1086,12 @@ extern "C" int esvit_window_attn_fwd(int dtype, const void* qkv, const float* qk
     }
     const int Bw = nB * nW;
     ESVIT_CHECK_ARG((long)L * 3 * nH * hd * 4 < 0x7fff0000L, "esvit_window_attn_fwd: one image's qkv rows must fit a 2 GiB buffer descriptor");
-    // persistent wave pairs, one head each, at most one window per pair; exactly as many as the chip keeps resident (163
-    // registers -> three waves per SIMD -> six two-wave workgroups per CU x 256 CUs; 208 registers at head_dim 64 -> four): a
-    // larger grid runs a second, partly empty round (2560 workgroups were 5-12 % slower, tools/bench_attn.py)
-    int parts = (hd == HD ? 1536 : 1024) / nH;  // (rounded DOWN: one workgroup more than the chip holds costs a second round)
-    if (parts < 1) parts = 1;
-    if (parts > Bw) parts = Bw;
-#define LAUNCH_FWD(TT, HH)                                                                                                      \
-    {                                                                                                                           \
-        const size_t lds = (size_t)3 * AttnCfgH<TT, HH>::QK_ELEMS * sizeof(TT);                                                 \
-        auto kern = attn_out ? attn_fwd4_kernel<TT, true, HH> : attn_fwd4_kernel<TT, false, HH>;                                \
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);   \
-        hipLaunchKernelGGL(kern, dim3(parts * nH), dim3(128), lds, stream, (const TT*)qkv, qkv_bias, win2tok, L,                \
-                           (const float*)bias_frag_ws, region_ids, nW, Bw, N, nH, scale, parts, (TT*)out, attn_out);            \
-    }
-    if (dtype == ESVIT_BF16) {
-        if (hd == HD) LAUNCH_FWD(bf16, 32) else LAUNCH_FWD(bf16, 64)
-    } else {
-        if (hd == HD) LAUNCH_FWD(float, 32) else LAUNCH_FWD(float, 64)
-    }
-#undef LAUNCH_FWD
+    const int parts = fwd_parts(hd, nH, Bw);
+#define LAUNCH(TT, HH)                                                                                                                 \
+    launch_pairs(attn_out ? attn_fwd4_kernel<TT, true, HH> : attn_fwd4_kernel<TT, false, HH>, 3 * AttnCfgH<TT, HH>::QK_ELEMS * sizeof(TT), \
+                 parts * nH, stream, qkv, qkv_bias, win2tok, L, bias_frag_ws, region_ids, nW, Bw, N, nH, scale, parts, out, attn_out);
+    FOR_DTYPE_HD(LAUNCH)
+#undef LAUNCH
     ESVIT_CHECK_LAUNCH("window_attn_fwd");
     return ESVIT_OK;
 }
@@ -1180,21 +1134,11 @@ extern "C" int esvit_window_attn_bwd(int dtype, const void* qkv, const float* qk
     const int Bw = nB * nW;
     const int parts = bwd_parts(Bw, nH);
     ESVIT_CHECK_ARG((long)L * 3 * nH * hd * 4 < 0x7fff0000L, "esvit_window_attn_bwd: one image's qkv rows must fit a 2 GiB buffer descriptor");
-#define LAUNCH_BWD(TT, TR, HH)                                                                                                  \
-    {                                                                                                                           \
-        const size_t lds = (size_t)AttnCfgH<TT, HH>::BWD3_PER_PAIR * sizeof(TT);                                                \
-        auto kern = attn_bwd3_kernel<TT, TR, HH>;                                                                               \
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);   \
-        hipLaunchKernelGGL(kern, dim3(parts * nH), dim3(128), lds, stream, (const TT*)qkv, qkv_bias, win2tok, L,                \
-                           (const TT*)dout, (const float*)bias_frag_ws, region_ids, nW, Bw, N, nH, scale, parts, (TT*)dqkv,     \
-                           dbias_ws, dpad_ws);                                                                                  \
-    }
-    if (dtype == ESVIT_BF16) {
-        if (hd == HD) LAUNCH_BWD(bf16, true, 32) else LAUNCH_BWD(bf16, true, 64)
-    } else {
-        if (hd == HD) LAUNCH_BWD(float, false, 32) else LAUNCH_BWD(float, false, 64)
-    }
-#undef LAUNCH_BWD
+#define LAUNCH(TT, HH)  /* (transpose reads of the LDS images: bf16 only) */                                                          \
+    launch_pairs(attn_bwd3_kernel<TT, sizeof(TT) == 2, HH>, AttnCfgH<TT, HH>::BWD3_PER_PAIR * sizeof(TT), parts * nH, stream, qkv, qkv_bias, \
+                 win2tok, L, dout, bias_frag_ws, region_ids, nW, Bw, N, nH, scale, parts, dqkv, dbias_ws, dpad_ws);
+    FOR_DTYPE_HD(LAUNCH)
+#undef LAUNCH
     ESVIT_CHECK_LAUNCH("window_attn_bwd");
     return ESVIT_OK;
 }

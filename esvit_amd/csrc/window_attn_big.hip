@@ -16,6 +16,7 @@
 // in MFMA fragment order (relpos_bias_frag_big_kernel), one 16-byte load per lane per 16x16 score tile.
 #include "common.h"
 #include "mfma.h"
+#include "window_softmax.h"
 #include "../../include/esvit_hip.h"
 
 namespace {
@@ -91,6 +92,19 @@ __device__ __forceinline__ unsigned live_query_tiles(const int* tok_lds, int lan
 #pragma unroll
     for (int j = 0; j < NT; ++j) m |= (((b >> (4 * j)) & 0xfull) != 0 ? 1u : 0u) << j;
     return m;
+}
+
+// Bias tile (key tile i, query tile qt) of a transposed score strip: the head's fragment-order bias (relpos_bias_frag_big_kernel, first
+// half) plus the shift mask: -100 where the region label of key 16 i + 4 g + r (pk: a(t) | region << 16, BigTables) is not rq, the
+// label of this lane's query.  The 224-slot forward, statistics, dQ and bias-gradient kernels start every S^T tile from it.
+__device__ __forceinline__ f32x4 masked_bias_tile(const float* bias_h, const int* pk, int i, int qt, int lane, int g, bool masked, int rq) {
+    f32x4 b = *reinterpret_cast<const f32x4*>(bias_h + ((i * NT + qt) * 64 + lane) * 4);
+    if (masked) {
+        const i32x4 pk4 = *reinterpret_cast<const i32x4*>(pk + 16 * i + 4 * g);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) b[r] += (((pk4[r] >> 16) & 0xff) != rq) ? -100.f : 0.f;
+    }
+    return b;
 }
 
 // stage NROWS window slots (first slot s0) of a token-ordered matrix into a [NROWS][LDQ] image; NTHR threads cooperate.
@@ -235,21 +249,15 @@ __device__ __forceinline__ void store_tile_rows_t(const f32x4 (&acc)[HD / 16], f
 }
 
 // -------------------------------------------------------------------------------------------------------------
-// forward, second generation (default).  Same mathematics; what changed is where the data waits:
+// forward.  One workgroup of seven waves per (window, head); wave w takes the 16-query tiles w and w + 7 (no idle wave in the second
+// pass): the score strip is 56 registers, so the kernel fits four waves per SIMD and two bf16 workgroups (14 waves) share a CU -- with
+// 32-query blocks and two waves per SIMD the SQ counters showed 59 % of the wave cycles parked on loads.
 //   * P never goes through LDS.  The S^T tiles leave lane (c, g) with, for query c, the keys 16i + 4g + r -- for a 32-key
 //     chunk that is 8 keys {32ks + 4g + e, 32ks + 16 + 4g + e}.  An MFMA only needs A and B to agree on which key sits in
 //     which k-slot, so those 8 values ARE the A fragment of P V if V's B fragment is read with the same key permutation
-//     (mfma.h: frag_p_regs / frag_v_perm, two transpose reads 16 key rows apart).  That removes 56 LDS stores + 14 LDS fragment reads + a wave
-//     barrier per query block and, more importantly, the 59 KB of per-wave P images: the workgroup needs 53 KB instead of
-//     112 KB, so two (bf16) workgroups share a CU and one's softmax overlaps the other's MFMAs and loads.
-//   * K, V and the first Q block are requested together (one round trip), the Q block of the second pass is requested
-//     before the first pass computes, and the shift-mask labels of the keys are packed into 14 registers once per window
-//     instead of being re-read from LDS for every score tile.
-// -------------------------------------------------------------------------------------------------------------
-// forward, third variant (default): the second generation with ONE 16-query tile per wave and pass.  A workgroup is seven
-// waves, wave w takes query tiles w and w + 7 (no idle wave in the second pass, the 32-query blocks left one of four idle);
-// the score strip is 56 registers instead of 112, so the kernel fits four waves per SIMD and two workgroups (14 waves) share
-// a CU -- the second generation's SQ counters still showed 59 % of the wave cycles parked on loads with two waves per SIMD.
+//     (mfma.h: frag_p_regs / frag_v_perm, two transpose reads 16 key rows apart): no per-wave P images, 53 KB of LDS per workgroup.
+//   * K, V and the first Q tile are requested together (one round trip), the Q tile of the second pass is requested
+//     before the first pass computes.
 constexpr int FWD3_WAVES = 7;
 
 template <typename T, bool WANT_ATTN, int HD>
@@ -317,48 +325,23 @@ __global__ __launch_bounds__(FWD3_WAVES * 64, sizeof(T) == 2 ? (HD == 32 ? 4 : 2
             continue;
         }
         const int rq = masked ? ((tb.pk[q0 + c] >> 16) & 0xff) : 0;
-        f32x4 p[NT];
+        f32x4 p[NT][1];  // S^T strip of the query tile: NT key tiles x one query column per lane (window_softmax.h)
 #pragma unroll
         for (int i = 0; i < NT; ++i) {
-            f32x4 b = *reinterpret_cast<const f32x4*>(bias_h + ((i * NT + (q0 >> 4)) * 64 + lane) * 4);
-            if (masked) {
-                const i32x4 pk4 = *reinterpret_cast<const i32x4*>(tb.pk + 16 * i + 4 * g);
+            f32x4 b = masked_bias_tile(bias_h, tb.pk, i, q0 >> 4, lane, g, masked, rq);
+            p[i][0] = b;
 #pragma unroll
-                for (int r = 0; r < 4; ++r) b[r] += (((pk4[r] >> 16) & 0xff) != rq) ? -100.f : 0.f;
-            }
-            p[i] = b;
-#pragma unroll
-            for (int ks = 0; ks < KS; ++ks) mma(frag_kc<T>(Ks, LDQ, 16 * i, 32 * ks, c, g), qf[ks], p[i]);
+            for (int ks = 0; ks < KS; ++ks) mma(frag_kc<T>(Ks, LDQ, 16 * i, 32 * ks, c, g), qf[ks], p[i][0]);
         }
-        float m = -3.0e38f;
-#pragma unroll
-        for (int i = 0; i < NT; ++i)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) m = fmaxf(m, p[i][r]);
-        m = fmaxf(m, __shfl_xor(m, 16, 64));
-        m = fmaxf(m, __shfl_xor(m, 32, 64));
-        float sum = 0.f;
-#pragma unroll
-        for (int i = 0; i < NT; ++i)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const float e = __expf(p[i][r] - m);
-                p[i][r] = e;
-                sum += e;
-            }
-        sum += __shfl_xor(sum, 16, 64);
-        sum += __shfl_xor(sum, 32, 64);
-        const float inv = 1.f / sum;
-#pragma unroll
-        for (int i = 0; i < NT; ++i) p[i] *= inv;
-        if (g == 0 && lse_out) lse_out[(long)unit * NPB + q0 + c] = m + __logf(sum);
+        const ColSoftmax sm = column_softmax<false>(p, 0);
+        if (g == 0 && lse_out) lse_out[(long)unit * NPB + q0 + c] = sm.m + __logf(sm.sum);
         if constexpr (WANT_ATTN) {
 #pragma unroll
             for (int i = 0; i < NT; ++i)
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     const int q = q0 + c, key = 16 * i + 4 * g + r;
-                    if (q < N && key < N) attn_out[((long)unit * N + q) * N + key] = p[i][r];
+                    if (q < N && key < N) attn_out[((long)unit * N + q) * N + key] = p[i][0][r];
                 }
         }
         f32x4 o[DT];
@@ -366,7 +349,7 @@ __global__ __launch_bounds__(FWD3_WAVES * 64, sizeof(T) == 2 ? (HD == 32 ? 4 : 2
         for (int j = 0; j < DT; ++j) o[j] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int ks = 0; ks < NPB / 32; ++ks) {
-            const Frag<T> pf = frag_p_regs<T>(p[2 * ks], p[2 * ks + 1]);
+            const Frag<T> pf = frag_p_regs<T>(p[2 * ks][0], p[2 * ks + 1][0]);
 #pragma unroll
             for (int j = 0; j < DT; ++j) mma(frag_v_perm<T>(Vs, LDQ, 16 * j, ks, c, g), pf, o[j]);  // O^T [d][query]: operands exchanged
         }
@@ -431,45 +414,16 @@ __global__ __launch_bounds__(FWD3_WAVES * 64, sizeof(T) == 2 ? (HD == 32 ? 4 : 2
         for (int ks = 0; ks < KS; ++ks) qf[ks] = frag_kc<T>(Qs, LDQ, 0, 32 * ks, c, g);
         if (pass == 0) sq.load(src, 3L * C, tb.tok, tok_base, 16 * (wave + FWD3_WAVES), N, &padq, lane);
         const int rq = masked ? ((tb.pk[q0 + c] >> 16) & 0xff) : 0;
-        f32x4 p[NT];
+        f32x4 p[NT][1];
 #pragma unroll
         for (int i = 0; i < NT; ++i) {
-            f32x4 b = *reinterpret_cast<const f32x4*>(bias_h + ((i * NT + (q0 >> 4)) * 64 + lane) * 4);
-            if (masked) {
-                const i32x4 pk4 = *reinterpret_cast<const i32x4*>(tb.pk + 16 * i + 4 * g);
+            f32x4 b = masked_bias_tile(bias_h, tb.pk, i, q0 >> 4, lane, g, masked, rq);
+            p[i][0] = b;
 #pragma unroll
-                for (int r = 0; r < 4; ++r) b[r] += (((pk4[r] >> 16) & 0xff) != rq) ? -100.f : 0.f;
-            }
-            p[i] = b;
-#pragma unroll
-            for (int ks = 0; ks < KS; ++ks) mma(frag_kc<T>(Ks, LDQ, 16 * i, 32 * ks, c, g), qf[ks], p[i]);
+            for (int ks = 0; ks < KS; ++ks) mma(frag_kc<T>(Ks, LDQ, 16 * i, 32 * ks, c, g), qf[ks], p[i][0]);
         }
-        float m = -3.0e38f;
-#pragma unroll
-        for (int i = 0; i < NT; ++i)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) m = fmaxf(m, p[i][r]);
-        m = fmaxf(m, __shfl_xor(m, 16, 64));
-        m = fmaxf(m, __shfl_xor(m, 32, 64));
-        float sum = 0.f, ex = 0.f;
-#pragma unroll
-        for (int i = 0; i < NT; ++i)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const float x = p[i][r] - m;
-                const float e = __expf(x);
-                p[i][r] = e;
-                sum += e;
-                ex += e * x;
-            }
-        sum += __shfl_xor(sum, 16, 64);
-        sum += __shfl_xor(sum, 32, 64);
-        ex += __shfl_xor(ex, 16, 64);
-        ex += __shfl_xor(ex, 32, 64);
-        const float inv = 1.f / sum;
-#pragma unroll
-        for (int i = 0; i < NT; ++i) p[i] *= inv;
-        if (g == 0 && q0 + c < N) ent[(long)unit * N + q0 + c] = __logf(sum) - ex * inv;
+        const ColSoftmax sm = column_softmax<true>(p, 0);
+        if (g == 0 && q0 + c < N) ent[(long)unit * N + q0 + c] = __logf(sm.sum) - sm.ex * sm.inv;
         for (int n = 0; n < nq; ++n) {
             const int slot = slots[n];
             if ((unsigned)slot >= (unsigned)(nW * N) || slot / N != bw % nW) continue;  // (workgroup-uniform)
@@ -480,32 +434,30 @@ __global__ __launch_bounds__(FWD3_WAVES * 64, sizeof(T) == 2 ? (HD == 32 ? 4 : 2
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     const int key = 16 * i + 4 * g + r;
-                    if (key < N) row[key] = p[i][r];
+                    if (key < N) row[key] = p[i][0][r];
                 }
         }
     }
 }
 
 // -------------------------------------------------------------------------------------------------------------
-// backward, second generation (default).  Same split (dQ + bias gradient | dK, dV) and the same mathematics; changes:
+// backward: dQ + bias gradient | dK, dV, two kernels (a third for the bias gradient alone, attn_big_bwd_dbias_kernel).
 //   * dS / P never go through LDS: a score tile leaves its 4 accumulator rows per lane in exactly the k-slots an MFMA A
 //     operand wants if the other operand is read with the matching row permutation (frag_v_perm) -- rows = keys for
 //     dQ = dS K (tiles oriented S^T as in the forward), rows = queries for dV = P^T dO and dK = dS^T Q (tiles oriented S;
-//     the bias arrives in a second fragment buffer with that orientation).  That frees the 59 / 72 KB of per-wave images
-//     and lets two workgroups share a CU.
+//     the bias arrives in a second fragment buffer with that orientation).  No per-wave images: two workgroups share a CU.
 //   * both kernels rebuild P from the saved log-sum-exp (no max / sum passes, no shuffles).
 //   * the relative-position-bias gradient stays in accumulator registers across the windows a wave visits (fragment
 //     layout, reduced over `parts` afterwards).  Reducing it into its (2ws-1)^2-entry table in LDS with ds_add_f32 instead
-//     (112 LDS atomics per wave and window) was tried and measured 3x slower -- the LDS atomic unit saturates
+//     (112 LDS atomics per wave and window) was measured 3x slower -- the LDS atomic unit saturates
 //     (profiles/r01_kernel_stats_w14_dq_ldsadd.csv) -- and a 32-query strip per wave needs > 256 registers with those
 //     accumulators, hence dq4 below: eight waves, one 16-query tile each.
 // -------------------------------------------------------------------------------------------------------------
 
-// dQ + bias gradient, fourth variant (default).  The bias gradient has to live in accumulator registers across the windows
-// a wave visits; with a 32-query strip per wave that is 112 registers and the kernel cannot run two waves per SIMD
-// (the first-generation dQ kernel: one wave per SIMD, every load round trip exposed).  Here a workgroup is EIGHT waves and a wave owns ONE
-// query tile (16 queries): 56 bias-gradient + 56 P + 28 packed-dS registers, two waves per SIMD, while K and V are still
-// staged once per 8 (6) query tiles.  Same fragment-layout bias-gradient workspace as the first generation.
+// dQ + bias gradient.  The bias gradient has to live in accumulator registers across the windows a wave visits; with a 32-query
+// strip per wave that is 112 registers and the kernel cannot run two waves per SIMD (one wave per SIMD: every load round trip
+// exposed).  Here a workgroup is EIGHT waves and a wave owns ONE query tile (16 queries): 56 bias-gradient + 56 P + 28 packed-dS
+// registers, two waves per SIMD, while K and V are still staged once per 8 (6) query tiles.
 constexpr int DQ4_WAVES = 8;
 constexpr int DQ4_GROUPS = (NT + DQ4_WAVES - 1) / DQ4_WAVES;
 
@@ -603,12 +555,7 @@ __global__ __launch_bounds__(DQ4_WAVES * 64) void attn_big_bwd_dq4_kernel(
         f32x4 pj[NT];
 #pragma unroll
         for (int i = 0; i < NT; ++i) {
-            f32x4 b = *reinterpret_cast<const f32x4*>(bias_h + ((i * NT + (q0 >> 4)) * 64 + lane) * 4);
-            if (masked) {
-                const i32x4 pk4 = *reinterpret_cast<const i32x4*>(tb.pk + 16 * i + 4 * g);
-#pragma unroll
-                for (int r = 0; r < 4; ++r) b[r] += (((pk4[r] >> 16) & 0xff) != rq) ? -100.f : 0.f;
-            }
+            f32x4 b = masked_bias_tile(bias_h, tb.pk, i, q0 >> 4, lane, g, masked, rq);
 #pragma unroll
             for (int ks = 0; ks < KS; ++ks) mma(frag_kc<T>(Ks, LDQ, 16 * i, 32 * ks, c, g), qf[ks], b);
 #pragma unroll
@@ -752,12 +699,7 @@ __global__ __launch_bounds__(DQ4_WAVES * 64) void attn_big_bwd_dbias_kernel(
         d += __shfl_xor(d, 32, 64);
 #pragma unroll
         for (int i = 0; i < NT; ++i) {
-            f32x4 b = *reinterpret_cast<const f32x4*>(bias_h + ((i * NT + (q0 >> 4)) * 64 + lane) * 4);
-            if (masked) {
-                const i32x4 pk4 = *reinterpret_cast<const i32x4*>(tb.pk + 16 * i + 4 * g);
-#pragma unroll
-                for (int r = 0; r < 4; ++r) b[r] += (((pk4[r] >> 16) & 0xff) != rq) ? -100.f : 0.f;
-            }
+            f32x4 b = masked_bias_tile(bias_h, tb.pk, i, q0 >> 4, lane, g, masked, rq);
             f32x4 dp = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
             for (int ks = 0; ks < KS; ++ks) {
@@ -1113,20 +1055,6 @@ static int big_bwd_launch(const void* qkv, const float* qkv_bias, const int32_t*
                           int nH, float scale, void* dqkv, float* dbias_ws, float* dpad_ws, bool split_db, hipStream_t stream) {
     using Cfg = BigCfg<T, HD>;
     const int parts = big_parts(Bw, nH);
-#ifdef ESVIT_BIG_BWD_FORK  // probe (its A/B script is gone; the measurement is profiles/r06_w14_dq_dkv_fork_ab.txt): the dK / dV kernel on a second stream beside the dQ kernel (disjoint outputs)
-    static hipStream_t s2 = nullptr;
-    static hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-    if (!s2) {
-        (void)hipStreamCreateWithFlags(&s2, hipStreamNonBlocking);
-        (void)hipEventCreateWithFlags(&ev_fork, hipEventDisableTiming);
-        (void)hipEventCreateWithFlags(&ev_join, hipEventDisableTiming);
-    }
-    (void)hipEventRecord(ev_fork, stream);
-    (void)hipStreamWaitEvent(s2, ev_fork, 0);
-    hipStream_t stream_kv = s2;
-#else
-    hipStream_t stream_kv = stream;
-#endif
     {
         auto kern = attn_big_bwd_dq4_kernel<T, HD>;
         const size_t lds = dq4_lds<T, HD>();
@@ -1151,14 +1079,10 @@ static int big_bwd_launch(const void* qkv, const float* qkv_bias, const int32_t*
         auto kern = attn_big_bwd_dkv2_kernel<T, HD>;
         const size_t lds = dkv2_lds<T, HD>();
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        hipLaunchKernelGGL(kern, dim3(Bw * nH), dim3(Cfg::WAVES * 64), lds, stream_kv, (const T*)qkv, qkv_bias, win2tok, L, (const T*)dout,
+        hipLaunchKernelGGL(kern, dim3(Bw * nH), dim3(Cfg::WAVES * 64), lds, stream, (const T*)qkv, qkv_bias, win2tok, L, (const T*)dout,
                            (const T*)fout, lse, rel_table + (long)nH * NT * NT * 256, ws, region_ids, nW, Bw, N, nH, scale, (T*)dqkv, dpad_ws);
         ESVIT_CHECK_LAUNCH("window_attn_bwd(14x14, dK dV)");
     }
-#ifdef ESVIT_BIG_BWD_FORK
-    (void)hipEventRecord(ev_join, s2);
-    (void)hipStreamWaitEvent(stream, ev_join, 0);
-#endif
     return ESVIT_OK;
 }
 
