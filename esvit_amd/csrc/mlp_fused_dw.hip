@@ -15,7 +15,8 @@
 //     reads) and, read through ds_read_tr16_b64, the A fragments of dxhat^T = W1^T dA^T.  The wave's 48 rows of W2^T are nine B
 //     fragments = 36 registers that do not fit beside the accumulators; the 12 of one hidden tile are re-read from L2 once per tile.
 // Per tile:
-//   L  512 threads (8 per token) read x and gy, LayerNorm in registers; LN(x), xhat and rowscale * gy go to LDS as bf16 [64][96]
+//   L  512 threads (8 per token) take x and gy (requested during phase D of the tile before: 25 registers, free there), LayerNorm in
+//      registers; LN(x), xhat and rowscale * gy go to LDS as bf16 [64][96]
 //   C  per 16-token sub-tile and 16-hidden tile, with the TOKENS as MFMA rows:  P = LN(x) W1_slice^T,  Q = dy W2_slice;  GELU and GELU'
 //      (gelu_both);  lane (c, g) then holds hidden unit c, tokens 4g + r -- two sub-tiles side by side ARE an A fragment of the two
 //      products that contract over the tokens (mfma.h: frag_p_regs), whose B fragments are transpose reads of the dy / xhat images with
@@ -45,24 +46,74 @@ static_assert(L_END <= 160 * 1024, "LDS budget");
 typedef short s16x8_ __attribute__((ext_vector_type(8)));
 
 // byte offset of channel ch of row `row` in a [rows][96] bf16 image
-__device__ __forceinline__ int img_off(int row, int ch) {
+__host__ __device__ constexpr int img_off(int row, int ch) {
     const int u = ch >> 3;
     return row * 192 + (((u & ~3) | ((u ^ (row >> 2)) & 3)) << 4) + ((ch & 7) << 1);
 }
+
+// Phases C and D address the images as a lane-dependent base plus a compile-time constant that goes into the 16-bit offset field of
+// the LDS instruction: a phase C trip forms its five bases (6 integer instructions, 77 before), phase D advances its seven bases once
+// per six k-steps.  The XOR of img_off sees (row >> 2) & 3 and the low two bits of the
+// 16-byte unit only, hence:  16 rows further is +3072 bytes;  32 channels further is +64 bytes;  of a 16-channel step only its parity
+// reaches the XOR (two bases, 32 bytes apart under XOR);  in phase D, where a transpose read's rows step by 4, the second row of a
+// pair has a base of its own and 32 rows further is +6144.  The images lie a constant apart, so one base serves all of them.
+constexpr int IMG_ROWS16 = 16 * 192, IMG_CH32 = 64;
+constexpr bool img_immediates_hold() {
+    for (int c = 0; c < 16; ++c)
+        for (int g = 0; g < 4; ++g) {
+            // A / B fragment reads of C: row 16 k + c, channels 32 ks + 8 g
+            for (int k = 0; k < 24; ++k)
+                for (int ks = 0; ks < 3; ++ks)
+                    if (img_off(16 * k + c, 32 * ks + 8 * g) != img_off(c, 8 * g) + IMG_ROWS16 * k + IMG_CH32 * ks) return false;
+            // transpose reads of C: rows 32 p + 4 g + (c >> 2) and 16 on, channels 16 n + 4 (c & 3)
+            for (int k = 0; k < 4; ++k)
+                for (int n = 0; n < 6; ++n)
+                    if (img_off(16 * k + 4 * g + (c >> 2), 16 * n + 4 * (c & 3)) !=
+                        img_off(4 * g + (c >> 2), 16 * (n & 1) + 4 * (c & 3)) + IMG_ROWS16 * k + IMG_CH32 * (n >> 1))
+                        return false;
+            if (img_off(4 * g + (c >> 2), 16 + 4 * (c & 3)) != (img_off(4 * g + (c >> 2), 4 * (c & 3)) ^ 32)) return false;
+            // transpose reads of D: rows 32 ks + 8 g + (c >> 2) and 4 on, channels 16 n + 4 (c & 3)
+            for (int ks = 0; ks < 12; ++ks)
+                for (int n = 0; n < 6; ++n)
+                    for (int rw = 0; rw < 2; ++rw)
+                        if (img_off(32 * ks + 8 * g + (c >> 2) + 4 * rw, 16 * n + 4 * (c & 3)) !=
+                            img_off(8 * g + (c >> 2) + 4 * rw, 16 * n + 4 * (c & 3)) + 2 * IMG_ROWS16 * ks)
+                            return false;
+        }
+    return true;
+}
+static_assert(img_immediates_hold(), "base + immediate addressing of the [*][96] images");
 
 __device__ __forceinline__ f32x4 mfma(bf16x8 a, bf16x8 b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0); }
 __device__ __forceinline__ void mfma_acc(const bf16x8& a, const bf16x8& b, f32x4& c) {
     c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
 }
 
-// two transpose reads 16 image rows apart: element j / 4 + j of the result is image[row0 + j][col + (lane & 15)] / image[row0 + 16 + j][..]
-// when every lane passes row = row0 + ((lane & 15) >> 2), col4 = col + 4 * (lane & 3) (mfma.h: frag_ks, frag_v_perm)
-__device__ __forceinline__ bf16x8 tr_pair(const char* img, int row, int col4, int row_step) {
+// two transpose reads: element j / 4 + j of the result is image[row0 + j][col + (lane & 15)] / image[row1 + j][..] when lo / hi
+// are the addresses of (row0 / row1 + ((lane & 15) >> 2), col + 4 * (lane & 3)) (mfma.h: frag_ks, frag_v_perm)
+__device__ __forceinline__ bf16x8 tr_pair(const char* lo_p, const char* hi_p) {
     typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
-    const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(img + img_off(row, col4)));
-    const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(img + img_off(row + row_step, col4)));
+    const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)lo_p);
+    const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)hi_p);
     const s16x8_ both = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
     return __builtin_bit_cast(bf16x8, both);
+}
+
+// the L phase's share of one tile: 12 channels of x and gy of token (t >> 3) and the token's DropPath factor; rows past M read row M - 1
+// (no address beyond the operands is formed) and get factor 0
+__device__ __forceinline__ void request_rows(const float* __restrict__ x, const float* __restrict__ gy, const float* __restrict__ rs_mlp, long M,
+                                             int tile, int t, f32x4 (&xv)[3], f32x4 (&gv)[3], float& sm) {
+    const long row = (long)tile * DW_T + (t >> 3);
+    const bool ok = row < M;
+    const long rrow = ok ? row : (M - 1);
+    const float* xr = x + rrow * DW_C + 12 * (t & 7);
+    const float* gr = gy + rrow * DW_C + 12 * (t & 7);
+#pragma unroll
+    for (int q = 0; q < 3; ++q) {
+        xv[q] = *reinterpret_cast<const f32x4*>(xr + 4 * q);
+        gv[q] = *reinterpret_cast<const f32x4*>(gr + 4 * q);
+    }
+    sm = ok ? (rs_mlp ? rs_mlp[rrow] : 1.f) : 0.f;  // (rows past M contribute nothing: dy = 0 gives dA = 0)
 }
 
 __global__ __launch_bounds__(DW_NW * 64, 1) void mlp_dw_kernel(const float* __restrict__ x, const float* __restrict__ gy, const float* __restrict__ rs_mlp,
@@ -90,7 +141,7 @@ __global__ __launch_bounds__(DW_NW * 64, 1) void mlp_dw_kernel(const float* __re
     // this wave's rows of W2^T as B fragments: hidden unit c of tile t, channels 32 ks + 8g .. + 7 = two 8-byte pieces of the permuted copy's
     // row.  Held for the whole loop their 36 registers do not fit beside the accumulators (the allocator spilled them, and address registers
     // with them), so a tile re-reads the 12 of one hidden tile from L2, where the 72 KiB copy that every workgroup reads stays resident.
-    const bf16* w2row = W2Tp + (hid0 + c) * DW_C + (g < 2 ? 16 * g : 16 * (g - 2) + 4);
+    // (The row pointer `w2row` itself is formed per tile, below: the pointers derived from it were spilled when it lived across the loop.)
     float b1v[3];
 #pragma unroll
     for (int t = 0; t < 3; ++t) b1v[t] = b1[hid0 + 16 * t + c];
@@ -106,6 +157,12 @@ __global__ __launch_bounds__(DW_NW * 64, 1) void mlp_dw_kernel(const float* __re
     float db1s[3] = {0.f, 0.f, 0.f};
     float db2s = 0.f;
 
+    // the rows of a tile are requested one trip ahead, at the start of phase D of the tile before (which holds the accumulators and
+    // little else), so that phase L does not wait for a round trip to HBM with nothing else in flight; the last tile requests nothing
+    f32x4 xv[3], gv[3];
+    float sm;
+    if ((int)blockIdx.x < ntiles) request_rows(x, gy, rs_mlp, M, blockIdx.x, tid, xv, gv, sm);
+
     for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
         const long row0 = (long)tile * DW_T;
         // (opaque per tile: hoisted out of the loop, the LayerNorm parameters would hold 36 registers across it)
@@ -117,17 +174,6 @@ __global__ __launch_bounds__(DW_NW * 64, 1) void mlp_dw_kernel(const float* __re
         // ---- L: inputs -> LDS (8 lanes per token, 12 channels each)
         {
             const int tok = tid_t >> 3, sub = tid_t & 7;
-            const long row = row0 + tok;
-            const bool ok = row < M;
-            const long rrow = ok ? row : (M - 1);
-            const float* xr = x + rrow * DW_C + 12 * sub;
-            const float* gr = gy + rrow * DW_C + 12 * sub;
-            f32x4 xv[3], gv[3];
-#pragma unroll
-            for (int q = 0; q < 3; ++q) {
-                xv[q] = *reinterpret_cast<const f32x4*>(xr + 4 * q);
-                gv[q] = *reinterpret_cast<const f32x4*>(gr + 4 * q);
-            }
             float s1 = 0.f;
 #pragma unroll
             for (int q = 0; q < 3; ++q) s1 += (xv[q][0] + xv[q][1]) + (xv[q][2] + xv[q][3]);
@@ -147,7 +193,6 @@ __global__ __launch_bounds__(DW_NW * 64, 1) void mlp_dw_kernel(const float* __re
             s2 += __shfl_xor(s2, 2, 64);
             s2 += __shfl_xor(s2, 4, 64);
             const float rstd = rsqrtf(s2 * (1.f / DW_C) + eps);
-            const float sm = ok ? (rs_mlp ? rs_mlp[rrow] : 1.f) : 0.f;  // (rows past M contribute nothing: dy = 0 gives dA = 0)
 #pragma unroll
             for (int q = 0; q < 3; ++q) {
                 const int ch = 12 * sub + 4 * q;
@@ -179,6 +224,13 @@ __global__ __launch_bounds__(DW_NW * 64, 1) void mlp_dw_kernel(const float* __re
         }
 
         // ---- C: hidden tiles of this wave's slice; the token-contracting products
+        // lane bases of the tile (from the opaque tid_t: kept across the tile loop they would be spilled)
+        const int c_t = tid_t & 15, g_t = (tid_t >> 4) & 3;
+        const int frag_b = img_off(c_t, 8 * g_t);                             // row c, channels 8g: A fragments of P / Q, W1's B fragments
+        const int tr_b = img_off(4 * g_t + (c_t >> 2), 4 * (c_t & 3));        // transpose reads, even channel tiles (odd: ^ 32)
+        const int da_b = L_DA + 4 * g_t * DA_ROW + (hid0 + c_t) * 2;          // dA column of this lane's hidden unit, token 4g
+        const char* w1_frag = smem + L_W1 + hid0 * 192 + frag_b;
+        const bf16* w2row = W2Tp + (hid0 + c_t) * DW_C + (g_t < 2 ? 16 * g_t : 16 * (g_t - 2) + 4);  // (see above; per tile like the bases)
 #pragma unroll
         for (int t = 0; t < 3; ++t) {
             bf16x8 w2f[3];
@@ -191,19 +243,21 @@ __global__ __launch_bounds__(DW_NW * 64, 1) void mlp_dw_kernel(const float* __re
 #pragma unroll 1
             for (int p = 0; p < 2; ++p) {
                 bf16x8 hfA, dfA;  // hidden unit hid0 + 16 t + c, tokens 32 p + {4g + r, 16 + 4g + r}: A fragments over the pair's tokens
+                const char* xw_frag = smem + L_XW + 2 * IMG_ROWS16 * p + frag_b;   // the pair's first row of LN(x); dy lies L_DY - L_XW on
+                const char* xh_tr = smem + L_XH + 2 * IMG_ROWS16 * p + tr_b;       // likewise xhat for the transpose reads
+                char* da_pair = smem + 32 * DA_ROW * p + da_b;
 #pragma unroll
                 for (int jj = 0; jj < 2; ++jj) {
-                    const int arow = 32 * p + 16 * jj + c;
                     f32x4 P = f32x4{0.f, 0.f, 0.f, 0.f}, Q = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
                     for (int ks = 0; ks < 3; ++ks) {
-                        const bf16x8 a = *reinterpret_cast<const bf16x8*>(smem + L_XW + img_off(arow, 32 * ks + 8 * g));
-                        const bf16x8 d = *reinterpret_cast<const bf16x8*>(smem + L_DY + img_off(arow, 32 * ks + 8 * g));
-                        const bf16x8 b = *reinterpret_cast<const bf16x8*>(smem + L_W1 + img_off(hid0 + 16 * t + c, 32 * ks + 8 * g));
+                        const bf16x8 a = *reinterpret_cast<const bf16x8*>(xw_frag + IMG_ROWS16 * jj + IMG_CH32 * ks);
+                        const bf16x8 d = *reinterpret_cast<const bf16x8*>(xw_frag + (L_DY - L_XW) + IMG_ROWS16 * jj + IMG_CH32 * ks);
+                        const bf16x8 b = *reinterpret_cast<const bf16x8*>(w1_frag + IMG_ROWS16 * t + IMG_CH32 * ks);
                         P = mfma(a, b, P);
                         Q = mfma(d, w2f[ks], Q);
                     }
-                    char* da_col = smem + L_DA + (32 * p + 16 * jj + 4 * g) * DA_ROW + (hid0 + 16 * t + c) * 2;
+                    char* da_col = da_pair + 16 * DA_ROW * jj + 32 * t;
 #pragma unroll
                     for (int r = 0; r < 4; ++r) {
                         float gl, dg;
@@ -216,16 +270,19 @@ __global__ __launch_bounds__(DW_NW * 64, 1) void mlp_dw_kernel(const float* __re
                     }
                 }
                 // (the B fragments are re-read for every hidden tile: keeping the pair's six of each live costs 48 registers the loop does not have)
+                const char* xh_tr_odd = smem + L_XH + 2 * IMG_ROWS16 * p + (tr_b ^ 32);
 #pragma unroll
                 for (int n = 0; n < 6; ++n) {
-                    const bf16x8 bd = tr_pair(smem + L_DY, 32 * p + 4 * g + (c >> 2), 16 * n + 4 * (c & 3), 16);
-                    const bf16x8 bx = tr_pair(smem + L_XH, 32 * p + 4 * g + (c >> 2), 16 * n + 4 * (c & 3), 16);
+                    const char* tr = ((n & 1) ? xh_tr_odd : xh_tr) + IMG_CH32 * (n >> 1);
+                    const bf16x8 bd = tr_pair(tr + (L_DY - L_XH), tr + (L_DY - L_XH) + IMG_ROWS16);
+                    const bf16x8 bx = tr_pair(tr, tr + IMG_ROWS16);
                     mfma_acc(hfA, bd, accW[t][n]);
                     mfma_acc(dfA, bx, accG[t][n]);
                 }
             }
         }
         __syncthreads();
+        if (tile + (int)gridDim.x < ntiles) request_rows(x, gy, rs_mlp, M, tile + gridDim.x, tid_t, xv, gv, sm);
 
         // ---- D: dxhat^T [channels][tokens] for 16 tokens x 48 channels per wave, LayerNorm backward, residual add
         {
@@ -234,13 +291,31 @@ __global__ __launch_bounds__(DW_NW * 64, 1) void mlp_dw_kernel(const float* __re
             f32x4 acc3[3];
 #pragma unroll
             for (int i = 0; i < 3; ++i) acc3[i] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll 2
-            for (int ks = 0; ks < DW_H / 32; ++ks) {
-                const bf16x8 b = *reinterpret_cast<const bf16x8*>(smem + L_DA + (16 * j + c) * DA_ROW + (32 * ks + 8 * g) * 2);
+            // bases of the dA row and of W1's transpose reads (both rows of a pair, three channel tiles); 32 hidden units further is
+            // +64 / +6144 bytes, which leaves the offset field after ten steps: the bases advance once, half way
+            const char* da_row = smem + L_DA + (16 * j + c) * DA_ROW + 16 * g;
+            const char* w1_tr[3][2];
+#pragma unroll
+            for (int i = 0; i < 3; ++i)
+#pragma unroll
+                for (int rw = 0; rw < 2; ++rw) w1_tr[i][rw] = smem + L_W1 + img_off(8 * g + (c >> 2) + 4 * rw, 16 * (n0 + i) + 4 * (c & 3));
+            constexpr int KH = DW_H / 64;
+#pragma unroll 1
+            for (int kh = 0; kh < 2; ++kh) {
+#pragma unroll
+                for (int ks = 0; ks < KH; ++ks) {
+                    const bf16x8 b = *reinterpret_cast<const bf16x8*>(da_row + IMG_CH32 * ks);
+#pragma unroll
+                    for (int i = 0; i < 3; ++i) {
+                        const bf16x8 a = tr_pair(w1_tr[i][0] + 2 * IMG_ROWS16 * ks, w1_tr[i][1] + 2 * IMG_ROWS16 * ks);
+                        acc3[i] = mfma(a, b, acc3[i]);
+                    }
+                }
+                da_row += IMG_CH32 * KH;
 #pragma unroll
                 for (int i = 0; i < 3; ++i) {
-                    const bf16x8 a = tr_pair(smem + L_W1, 32 * ks + 8 * g + (c >> 2), 16 * (n0 + i) + 4 * (c & 3), 4);
-                    acc3[i] = mfma(a, b, acc3[i]);
+                    w1_tr[i][0] += 2 * IMG_ROWS16 * KH;
+                    w1_tr[i][1] += 2 * IMG_ROWS16 * KH;
                 }
             }
             const int tok = 16 * j + c;

@@ -1,7 +1,8 @@
 #!/bin/bash
 # VGPR / scratch / spill table of one translation unit's gfx950 kernels: bash tools/kernel_regs.sh gemm [name filter]
-# (any file of esvit_amd/csrc by its stem: gemm, window_attn_big, chunk_attn, flash_attn, ...; build the library first)
-o=esvit_amd/csrc/build/$1.o; t=$(mktemp -d)
+# (any file of esvit_amd/csrc by its stem: gemm, window_attn_big, chunk_attn, flash_attn, ...; build the library first;
+#  OBJDIR=<dir> reads the objects of a variant build, python -m esvit_amd.build --variant: <variant>/obj)
+o=${OBJDIR:-esvit_amd/csrc/build}/$1.o; t=$(mktemp -d)
 /opt/rocm/lib/llvm/bin/llvm-objcopy -O binary --only-section=.hip_fatbin $o $t/fat.bin
 /opt/rocm/lib/llvm/bin/clang-offload-bundler --unbundle --type=o --targets=hipv4-amdgcn-amd-amdhsa--gfx950 --input=$t/fat.bin --output=$t/k.co
 /opt/rocm/lib/llvm/bin/llvm-readelf --notes $t/k.co | python3 -c "
