@@ -74,6 +74,28 @@ class GridGroup(C.Structure):
 MAX_GRID_GROUPS = 4
 
 
+class PatchCrop(C.Structure):
+    """esvit_patch_crop: one crop tensor of the fused patch embedding"""
+    _fields_ = [("img", vp), ("nB", i32), ("H", i32), ("W", i32), ("reserved", i32), ("row0", i64)]
+
+
+PATCH_EMBED_MAX_CROPS = 16
+PATCH_EMBED_FWD, PATCH_EMBED_BWD, PATCH_EMBED_REDUCE = 0, 1, 2
+
+
+class PatchEmbed(C.Structure):
+    """esvit_patch_embed: the host descriptor the fused mode of esvit_patch_im2col (nB = -crops) takes in place of the image pointer"""
+    _fields_ = [
+        ("mode", i32), ("E", i32),
+        ("W", vp), ("bias", vp), ("gamma", vp), ("beta", vp),
+        ("eps", f32), ("first_partial", i32),
+        ("x", vp), ("mean", vp), ("rstd", vp),
+        ("gx", vp), ("partials", vp),
+        ("dW", vp), ("dbp", vp), ("dgamma", vp), ("dbeta", vp),
+        ("crops", PatchCrop * PATCH_EMBED_MAX_CROPS),
+    ]
+
+
 # name -> (restype, argtypes); every symbol declared in include/esvit_hip.h
 SIGNATURES = {
     "esvit_version": (C.c_int, []),

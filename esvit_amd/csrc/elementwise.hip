@@ -279,8 +279,11 @@ extern "C" int esvit_colsum(int dtype, const void* x, int64_t rows, int N, int64
     return esvit_partial_reduce(ws, nblk, N, N, out, accumulate, stream);
 }
 
+int esvit_i_patch_embed(int dtype, const void* desc, int ncrops, int S, int P, int Kpad, hipStream_t stream);  // patch_embed.hip
+
 extern "C" int esvit_patch_im2col(int dtype, const float* img, void* cols, int nB, int S, int P, int Kpad, esvit_stream_t s_) {
     STREAM(s_);
+    if (nB < 0) return esvit_i_patch_embed(dtype, img, -(long)nB > 0x7fffffff ? 0 : -nB, S, P, Kpad, stream);  // fused mode: img is a host esvit_patch_embed
     // S < 65536: the side of a square image; otherwise the rectangle H = S & 0xffff (rows), W = S >> 16 (columns)
     const int H = S < 65536 ? S : (S & 0xffff), W = S < 65536 ? S : (S >> 16);
     ESVIT_CHECK_ARG(img && cols && nB > 0 && S > 0 && H > 0 && W > 0 && P > 0 && P % 4 == 0 && H % P == 0 && W % P == 0 && Kpad % 8 == 0 &&

@@ -40,6 +40,7 @@ int64_t esvit_i_probe_ce_reg_row();
 int64_t esvit_i_global_attn_ws(int64_t Z, int64_t L, int64_t backward);
 int64_t esvit_i_mlp_dw_ws(int dtype, int C, int64_t M);
 int64_t esvit_i_attn_branch_bwd_grid(int dtype, int C, int64_t windows);
+int64_t esvit_i_patch_embed_ws(int dtype, int E, int64_t M);
 
 extern "C" int64_t esvit_query(int what, int64_t a, int64_t b, int64_t c) {
     switch (what) {
@@ -61,6 +62,7 @@ extern "C" int64_t esvit_query(int what, int64_t a, int64_t b, int64_t c) {
         case ESVIT_Q_GLOBAL_ATTN_WS: return esvit_i_global_attn_ws(a, b, c);
         case ESVIT_Q_MLP_DW_WS: return esvit_i_mlp_dw_ws((int)a, (int)b, c);
         case ESVIT_Q_ATTN_BWD_FUSED_GRID: return esvit_i_attn_branch_bwd_grid((int)a, (int)b, c);
+        case ESVIT_Q_PATCH_EMBED_WS: return esvit_i_patch_embed_ws((int)a, (int)b, c);
     }
     esvit_set_error("esvit_query: unknown question %d", what);
     return ESVIT_ERR_ARG;

@@ -744,6 +744,44 @@ def _patch_cols(o, img, patch, Kc, out=None):
     return cols if out is None else out.copy_(cols)
 
 
+# bf16 mode, 4 x 4 patches of 3 channels with PATCH_NORM: projection + LayerNorm in ONE kernel straight from the images, and a backward
+# that recomputes them per tile and keeps dW, dbp, dgamma, dbeta on the chip (the fused mode of esvit_patch_im2col) -- the column matrix,
+# the projection output and dL/dy are never written, and only the images, mean, rstd are kept for the backward.  "0": A-B runs.
+PATCH_FUSED = os.environ.get("ESVIT_PATCH_FUSED", "1") != "0"
+
+
+def _patch_fused(o, Wp, g, patch, imgs):
+    return (PATCH_FUSED and g is not None and hasattr(o, "patch_embed_fwd") and o.act_dtype() == torch.bfloat16
+            and o.patch_embed_supported(o.act_dtype(), Wp.shape[0], patch, Wp.shape[1])
+            and all(im.dtype == torch.float32 and im.shape[1] == 3 and im.shape[2] % 4 == 0 and im.shape[3] % 4 == 0 for im in imgs))
+
+
+def _patch_fused_fwd(ctx, o, Wp, bp, g, b, imgs):
+    E = Wp.shape[0]
+    imgs = [im.contiguous() for im in imgs]
+    W = _weight(Wp, (E, o.PATCH_EMBED_K))
+    train = any(ctx.needs_input_grad)
+    x, mean, rstd = o.patch_embed_fwd(imgs, W, bp.detach(), g.detach(), b.detach(), LN_EPS, stats=train)
+    ctx.fused, ctx.params = True, (Wp, bp, g, b)
+    if train:
+        ctx.save_for_backward(mean, rstd, g, W, bp, *imgs)
+    return x
+
+
+def _patch_fused_bwd(ctx, o, gx):
+    mean, rstd, g, W, bp = ctx.saved_tensors[:5]
+    imgs = list(ctx.saved_tensors[5:])
+    Wp, bp_p, g_p, b_p = ctx.params
+    E = W.shape[0]
+    sinks = [P.grad_out(Wp, (E, o.PATCH_EMBED_K)), P.grad_out(bp_p), P.grad_out(g_p), P.grad_out(b_p)]
+    part, nparts = o.patch_embed_bwd(imgs, W, bp.detach(), g.detach(), gx.contiguous().view(mean.shape[0], E), mean, rstd)
+    # the fold of the partial records is a leaf like the weight-gradient GEMM it replaces: same side stream, same join
+    outs = _side_run(lambda: o.patch_embed_reduce(part, nparts, E, out=sinks), part)
+    _side_join()
+    dW, dbp, dg, db = [_alias(t, sk) for t, sk in zip(outs, sinks)]
+    return dW.view(ctx.wshape), dbp, dg, db
+
+
 class PatchEmbedFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, img, Wp, bp, g, b, patch):
@@ -751,6 +789,10 @@ class PatchEmbedFn(torch.autograd.Function):
         E = Wp.shape[0]
         Kc = Wp.shape[1] * patch * patch
         nB, _, S, Sw = img.shape
+        ctx.fused = False
+        if _patch_fused(o, Wp, g, patch, [img]):
+            ctx.wshape = tuple(Wp.shape)
+            return _patch_fused_fwd(ctx, o, Wp, bp, g, b, [img]).view(nB, (S // patch) * (Sw // patch), E)
         cols = _patch_cols(o, img, patch, Kc)
         W = _weight(Wp, (E, Kc))
         y = o.linear_fwd(cols, W, bp, out_f32=True)
@@ -765,6 +807,8 @@ class PatchEmbedFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, gx):
         o = ops_module()
+        if ctx.fused:
+            return (None,) + _patch_fused_bwd(ctx, o, gx) + (None,)
         if len(ctx.saved_tensors) == 1:
             (cols,) = ctx.saved_tensors
             M = cols.shape[0]
@@ -788,6 +832,9 @@ class PatchEmbedMultiFn(torch.autograd.Function):
         o = ops_module()
         E = Wp.shape[0]
         Kc = Wp.shape[1] * patch * patch
+        ctx.wshape, ctx.n_img, ctx.fused = tuple(Wp.shape), len(imgs), False
+        if _patch_fused(o, Wp, g, patch, imgs):
+            return _patch_fused_fwd(ctx, o, Wp, bp, g, b, imgs)
         rows = [im.shape[0] * (im.shape[2] // patch) * (im.shape[3] // patch) for im in imgs]  # one entry per crop tensor, in crop order
         cols = torch.empty((sum(rows), Kc), dtype=o.act_dtype(), device=imgs[0].device)
         r0 = 0
@@ -806,6 +853,8 @@ class PatchEmbedMultiFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, gx):
         o = ops_module()
+        if ctx.fused:
+            return _patch_fused_bwd(ctx, o, gx) + (None,) + (None,) * ctx.n_img
         if len(ctx.saved_tensors) == 1:
             (cols,) = ctx.saved_tensors
             M = cols.shape[0]

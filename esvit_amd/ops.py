@@ -10,7 +10,7 @@ import os
 import numpy as np
 import torch
 
-from ._lib import BF16, EPI_GELU, EPI_GELU_BWD, EPI_NONE, EPI_QGELU, EPI_QGELU_BWD, F32, GEMM_AUTO, GEMM_DMA8, GEMM_P8, GemmDesc, GemmTopk, GridGroup, MAX_GRID_GROUPS, check, lib
+from ._lib import BF16, EPI_GELU, EPI_GELU_BWD, EPI_NONE, EPI_QGELU, EPI_QGELU_BWD, F32, GEMM_AUTO, GEMM_DMA8, GEMM_P8, GemmDesc, GemmTopk, GridGroup, MAX_GRID_GROUPS, PATCH_EMBED_BWD, PATCH_EMBED_FWD, PATCH_EMBED_MAX_CROPS, PATCH_EMBED_REDUCE, PatchEmbed, check, lib
 
 _ACT_DTYPE = torch.bfloat16
 
@@ -84,7 +84,7 @@ def relative_position_index(ws):
 # esvit_query questions (include/esvit_hip.h)
 (Q_ATTN_FRAG_ELEMS, Q_ATTN_LSE_ELEMS, Q_ATTN_BWD_PARTS, Q_ATTN_BWD_PAD_ROWS, Q_LN_BWD_BLOCKS, Q_COLSUM_BLOCKS, Q_COL_REDUCE_BLOCKS,
  Q_UPDATE_CHUNK_ELEMS, Q_MLP_FUSED, Q_AUG_MAX_BOX, Q_JPEG_WORKSPACE, Q_RESIZE_FITS, Q_CHUNK_ATTN_WS, Q_TOPK_WS, Q_PROBE_CE_REG_ROW,
- Q_GLOBAL_ATTN_WS, Q_MLP_DW_WS, Q_ATTN_BWD_FUSED_GRID) = range(1, 19)
+ Q_GLOBAL_ATTN_WS, Q_MLP_DW_WS, Q_ATTN_BWD_FUSED_GRID, Q_PATCH_EMBED_WS) = range(1, 20)
 MLP_DW_PARTIAL_FLOATS = 74208  # ESVIT_MLP_DW_PARTIAL_FLOATS
 ATTN_BWD_PARTIAL_FLOATS = 37440  # ESVIT_ATTN_BWD_PARTIAL_FLOATS
 
@@ -718,6 +718,118 @@ def patch_im2col(img, P, Kpad, dtype=None, out=None):
         cols = torch.empty((rows, Kpad), dtype=dt, device=img.device)
     check(lib.esvit_patch_im2col(_code(dt), _p(img), _p(cols), nB, H if H == W else (H | (W << 16)), P, Kpad, _stream()), "patch_im2col")
     return cols
+
+
+# ---- fused patch embedding (the fused mode of esvit_patch_im2col): image -> LayerNorm(conv 4x4/4) tokens in one kernel each way
+PATCH_EMBED_FWD_TILE, PATCH_EMBED_BWD_TILE = 64, 128  # token rows per workgroup tile of the two kernels
+PATCH_EMBED_K = 48
+
+
+def patch_embed_supported(dt, E, patch=4, in_ch=3):
+    """the fused patch embedding exists at this activation dtype and geometry (bf16, 4 x 4 patches of 3 channels, E in {96, 128, 192})"""
+    return patch == 4 and in_ch == 3 and dt in (torch.bfloat16, torch.float32) and query(Q_PATCH_EMBED_WS, _code(dt), int(E), 1) > 0
+
+
+def patch_embed_rows(imgs):
+    return [im.shape[0] * (im.shape[2] // 4) * (im.shape[3] // 4) for im in imgs]
+
+
+def _patch_embed_call(d, ncrops, what):
+    check(lib.esvit_patch_im2col(BF16, C.cast(C.pointer(d), C.c_void_p), None, -ncrops, 0, 4, PATCH_EMBED_K, _stream()), what)
+
+
+def _patch_embed_chunks(imgs, row0=0):
+    """(first crop, crops, first row, rows) of every launch: at most PATCH_EMBED_MAX_CROPS crop tensors each"""
+    rows = patch_embed_rows(imgs)
+    out, r = [], row0
+    for i in range(0, len(imgs), PATCH_EMBED_MAX_CROPS):
+        n = sum(rows[i:i + PATCH_EMBED_MAX_CROPS])
+        out.append((i, imgs[i:i + PATCH_EMBED_MAX_CROPS], r, n))
+        r += n
+    return out
+
+
+def _patch_embed_desc(mode, W, bias, gamma, crops, row0):
+    d = PatchEmbed()
+    d.mode, d.E = mode, W.shape[0]
+    d.W, d.bias, d.gamma = _p(_actc(W)), _p(_f32c(bias)), _p(_f32c(gamma))
+    r = row0
+    for i, im in enumerate(crops):
+        im = _f32c(im)
+        if im.dim() != 4 or im.shape[1] != 3:
+            raise ValueError("patch embedding: images are [nB, 3, H, W], not %s" % (tuple(im.shape),))
+        cr = d.crops[i]
+        cr.img, cr.nB, cr.H, cr.W, cr.row0 = _p(im), im.shape[0], im.shape[2], im.shape[3], r
+        r += im.shape[0] * (im.shape[2] // 4) * (im.shape[3] // 4)
+    return d
+
+
+def patch_embed_fwd(imgs, W, bias, gamma, beta, eps, *, stats=True, out=None):
+    """imgs: fp32 [nB_i, 3, H_i, W_i] (sides multiples of 4), W act [E, 48] -> (x fp32 [sum rows, E], mean, rstd fp32 [rows] or None, None
+    without stats): LayerNorm(patch projection), crops in order, rows (image, patch row, patch column).  out: preallocated (x, mean, rstd)"""
+    E = W.shape[0]
+    assert W.shape == (E, PATCH_EMBED_K) and len(imgs) > 0
+    M = sum(patch_embed_rows(imgs))
+    dev = imgs[0].device
+    if out is not None:
+        x, mean, rstd = out
+        assert x.shape == (M, E) and (mean is None) == (rstd is None) and (mean is None or (mean.shape == (M,) and rstd.shape == (M,)))
+    else:
+        x = torch.empty((M, E), dtype=torch.float32, device=dev)
+        mean = torch.empty((M,), dtype=torch.float32, device=dev) if stats else None
+        rstd = torch.empty((M,), dtype=torch.float32, device=dev) if stats else None
+    for _, crops, r0, _ in _patch_embed_chunks(imgs):
+        d = _patch_embed_desc(PATCH_EMBED_FWD, W, bias, gamma, crops, r0)
+        d.beta, d.eps = _p(_f32c(beta)), eps
+        d.x, d.mean, d.rstd = _p(_f32c(x)), _p(None if mean is None else _f32c(mean)), _p(None if rstd is None else _f32c(rstd))
+        _patch_embed_call(d, len(crops), "patch_embed_fwd")
+    return x, mean, rstd
+
+
+def patch_embed_parts(E, imgs):
+    """partial records the backward over these crop tensors writes (one launch per PATCH_EMBED_MAX_CROPS of them) on the current device"""
+    return sum(query(Q_PATCH_EMBED_WS, BF16, E, n) // (4 * E * (PATCH_EMBED_K + 3)) for _, _, _, n in _patch_embed_chunks(imgs))
+
+
+def patch_embed_bwd(imgs, W, bias, gamma, gx, mean, rstd, *, partials=None):
+    """the backward of patch_embed_fwd up to its partial sums: gx fp32 [rows, E] -> (partials fp32 [records, 51 E], records); every record is
+    [dW E x 48 | dbias | dgamma | dbeta] of one workgroup.  patch_embed_reduce finishes.  partials: a preallocated buffer"""
+    E = W.shape[0]
+    gx, mean, rstd = _f32c(gx), _f32c(mean), _f32c(rstd)
+    M = sum(patch_embed_rows(imgs))
+    assert gx.shape == (M, E) and mean.shape == (M,) and rstd.shape == (M,)
+    nparts = patch_embed_parts(E, imgs)
+    if nparts <= 0:
+        raise RuntimeError("patch_embed_bwd: no fused patch embedding at E = %d" % E)
+    rec = E * (PATCH_EMBED_K + 3)
+    if partials is None:
+        partials = torch.empty((nparts, rec), dtype=torch.float32, device=gx.device)
+    assert partials.numel() >= nparts * rec and partials.dtype == torch.float32 and partials.is_contiguous()
+    first = 0
+    for _, crops, r0, n in _patch_embed_chunks(imgs):
+        d = _patch_embed_desc(PATCH_EMBED_BWD, W, bias, gamma, crops, r0)
+        d.gx, d.mean, d.rstd, d.partials, d.first_partial = _p(gx), _p(mean), _p(rstd), _p(partials), first
+        _patch_embed_call(d, len(crops), "patch_embed_bwd")
+        first += query(Q_PATCH_EMBED_WS, BF16, E, n) // (4 * rec)
+    return partials, nparts
+
+
+def patch_embed_reduce(partials, nparts, E, *, out=None):
+    """-> (dW fp32 [E, 48], dbias, dgamma, dbeta fp32 [E]) = the first nparts records of `partials` summed in a fixed order.
+    out: the four fp32 tensors to write (gradient-bucket slots), each or any None"""
+    dev = partials.device
+    outs = list(out) if out is not None else [None] * 4
+    shapes = [(E, PATCH_EMBED_K), (E,), (E,), (E,)]
+    for i, shp in enumerate(shapes):
+        if outs[i] is None:
+            outs[i] = torch.empty(shp, dtype=torch.float32, device=dev)
+        assert outs[i].numel() == E * (PATCH_EMBED_K if i == 0 else 1)
+        _f32c(outs[i])
+    d = PatchEmbed()
+    d.mode, d.E, d.first_partial, d.partials = PATCH_EMBED_REDUCE, E, int(nparts), _p(_f32c(partials))
+    d.dW, d.dbp, d.dgamma, d.dbeta = [_p(t) for t in outs]
+    _patch_embed_call(d, 1, "patch_embed_reduce")
+    return tuple(outs)
 
 
 def token_mean_fwd(x, dtype=None):

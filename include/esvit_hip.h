@@ -85,6 +85,11 @@ const char* esvit_last_error(void);
  *                                              the mode does not exist (anything but bf16, C = 96).  Needs no device (then: the size of an MI355X) */
 #define ESVIT_Q_ATTN_BWD_FUSED_GRID 18
 #define ESVIT_ATTN_BWD_PARTIAL_FLOATS 37440 /* dWqkv 288 x 96 + dWproj 96 x 96 + dbqkv 288 + dbproj 96 + dgamma 96 + dbeta 96 */
+/*   ESVIT_Q_PATCH_EMBED_WS (dtype, E, rows)    BYTES of partial records one backward launch of the fused patch embedding (the fused mode of
+ *                                              esvit_patch_im2col) writes for `rows` token rows: 51 E floats per workgroup (one per CU, at most
+ *                                              one per 128 rows); 0 where the mode does not exist (anything but bf16, E in {96, 128, 192}).
+ *                                              Needs no device (then: the size of an MI355X) */
+#define ESVIT_Q_PATCH_EMBED_WS 19
 int64_t esvit_query(int what, int64_t a, int64_t b, int64_t c);
 
 /* ---- host-side integer index maps (bit-exact vs reference) -------------
@@ -299,7 +304,54 @@ int esvit_colsum(int dtype, const void* x, int64_t rows, int N, int64_t ld, floa
  * S < 65536: a square image, H = W = S.  Otherwise S carries a rectangle: H = S & 0xffff (rows),
  * W = S >> 16 (columns); a square image in this form gives the same bits as the plain call.
  * ESVIT_ERR_ARG before any launch unless P % 4 == 0, H % P == 0, W % P == 0, H > 0, W > 0,
- * Kpad % 8 == 0 and Kpad >= 3*P*P. */
+ * Kpad % 8 == 0 and Kpad >= 3*P*P.
+ *
+ * FUSED MODE (nB = -G, G = 1 .. ESVIT_PATCH_EMBED_MAX_CROPS; dtype ESVIT_BF16, S = 0, P = 4, Kpad = 48; cols unused): `img` is a HOST
+ * esvit_patch_embed whose first G crop records are read -- the Swin patch embedding with PATCH_NORM (swin_transformer.py:531-547),
+ * Conv2d(3, E, 4, 4) + LayerNorm(E), E in {96, 128, 192}, straight from the images: no column matrix, projection output or dL/dy is
+ * ever written.  The crops of a call own consecutive token rows (crop i + 1 starts where crop i ends; rows are (image, patch row,
+ * patch column)), H and W any multiples of 4, at most ESVIT_PATCH_EMBED_MAX_ROWS rows.  Columns keep the (c, ph, pw) order and the
+ * bf16 rounding of the plain mode; W is the bf16 [E, 48] weight, everything else fp32.
+ *   ESVIT_PATCH_EMBED_FWD     x[row, E] = LayerNorm(cols W^T + bias) * gamma + beta; mean / rstd [row] written unless both are NULL
+ *   ESVIT_PATCH_EMBED_BWD     from gx = dL/dx [row, E] and the forward's mean / rstd: one partial record
+ *                             [dW E x 48 | dbias E | dgamma E | dbeta E] per workgroup of the launch, written from record first_partial
+ *                             of `partials` on; esvit_query(ESVIT_Q_PATCH_EMBED_WS, dtype, E, rows of the call) BYTES per call.  dL/dy
+ *                             is rounded to bf16 before it meets the columns, as esvit_layernorm_bwd's activation-dtype output is.
+ *                             The images get no gradient.
+ *   ESVIT_PATCH_EMBED_REDUCE  (G ignored) the first `first_partial` records of `partials` summed in a fixed order into dW, dbias,
+ *                             dgamma, dbeta.  No atomics in either launch: the bits depend on the call's shapes only.
+ * ESVIT_ERR_ARG before any device call for anything else (another dtype, E, P; a null or misaligned pointer -- images, W and x 16
+ * bytes --; a crop that does not start where the one before it ends). */
+#define ESVIT_PATCH_EMBED_MAX_CROPS 16
+#define ESVIT_PATCH_EMBED_MAX_ROWS (1 << 30)
+#define ESVIT_PATCH_EMBED_FWD 0
+#define ESVIT_PATCH_EMBED_BWD 1
+#define ESVIT_PATCH_EMBED_REDUCE 2
+typedef struct {
+    const float* img; /* fp32 [nB, 3, H, W] */
+    int32_t nB, H, W;
+    int32_t reserved;
+    int64_t row0; /* first token row of this crop */
+} esvit_patch_crop;
+typedef struct {
+    int32_t mode, E;
+    const void* W;
+    const float* bias;
+    const float* gamma;
+    const float* beta;
+    float eps;
+    int32_t first_partial;
+    float* x;
+    float* mean;
+    float* rstd;
+    const float* gx;
+    float* partials;
+    float* dW;
+    float* dbp;
+    float* dgamma;
+    float* dbeta;
+    esvit_patch_crop crops[ESVIT_PATCH_EMBED_MAX_CROPS];
+} esvit_patch_embed;
 int esvit_patch_im2col(int dtype, const float* img, void* cols, int nB, int S, int P, int Kpad,
                        esvit_stream_t stream);
 /* PatchMerging gather + LayerNorm(4C) (swin_transformer.py:410-417): x fp32 [nB,H,W,C] ->
