@@ -5,16 +5,28 @@ the data path -- torch provides allocation, streams and the autograd graph only.
 Stages (reference lines):
   SwinBlockFn      swin_transformer.py:275-333 (+120-152): LN -> pad/roll/partition -> qkv -> window
                    attention -> proj -> reverse/unroll/crop + residual -> LN -> MLP + residual
-  PatchEmbedFn     swin_transformer.py:537-547
-  PatchMergeFn     swin_transformer.py:393-420
+  SwinBlockMultiFn the same over the token rows of several resolution groups (swin_transformer.py:729-751)
+  PatchEmbedFn, PatchEmbedMultiFn   swin_transformer.py:537-547
+  PatchMergeFn, PatchMergeMultiFn   swin_transformer.py:393-420
   FinalNormFn      swin_transformer.py:687
   TokenMeanFn      swin_transformer.py:688-689
-  DinoHeadFn       vision_transformer.py:414-418
+  DinoHeadFn       vision_transformer.py:384-418 without BatchNorm, any number of Linear layers
+  DinoHeadBnFn     vision_transformer.py:391-402, 414-418 (use_bn), any number of BatchNorm layers
   ConvEmbedFn, CvtAttnFn, CvtFfnFn   cvt_v4_transformer.py:349-382, 108-220 (+75-105), 62-72  (BASELINE config 5)
   ConvEmbedMultiFn, CvtAttnMultiFn, CvtFfnMultiFn   the same over the token rows of several resolution groups (cvt_v4_transformer.py:625-628)
+  VitPatchEmbedFn, VitBlockFn, VitBlockMultiFn   vision_transformer.py:121-139, 96-116, 186-233
+  VilBlockFn       vision_longformer.py:36-118, layers/longformer2d.py
+
+Shared by the block families: the unfused MLP branch (_mlp_fwd / _mlp_bwd: LayerNorm -> fc1 + GELU -> fc2 + residual, called by the Swin,
+ViT and Vision Longformer blocks and CvT's feed-forward), Swin's choice between the fused, the wide and the unfused MLP kernels
+(_swin_mlp_fwd) and the fused backwards (_mlp_branch_bwd, _attn_branch_bwd).  A forward names the route it took (ctx.mlp_route,
+ctx.attn_bwd_fused) and saves its tensors by name (_save_named); a backward reads both back and infers nothing from what was saved.
+The weight gradients of the blocks and of DinoHeadFn are leaves launched through _side_run into their bucket slots (_wgrad, _ln_sinks),
+and such a node joins (_side_join) before it returns.
 """
 import math
 import os
+import types
 
 import torch
 
@@ -326,12 +338,95 @@ def _mlp_branch_bwd(o, x1, gy, dyb, g2, b2, W1, bfc1, params, dp_mlp, dp_out):
     return gx1, dyw, _alias(dg2, ln2), _alias(db2, ln2), _alias(dW1, wsink), _alias(dbfc1, bsink), dW2, dbfc2
 
 
+# ---- the unfused MLP branch: LayerNorm -> fc1 + GELU -> fc2 + residual.  Row-wise, so the Swin, ViT and Vision Longformer blocks and
+# CvT's feed-forward all run these two bodies, per resolution group or over the rows of all groups alike ---------------------------------
+_MLP_SAVED = ("mean2", "rstd2", "h", "a1", "a1g")
+
+
+def _mlp_fwd(o, x1, prm, W1, W2, eps, rowscale, rows_per_sample, save, quick=False):
+    """x1 fp32 [M, C]; prm: (norm.weight, norm.bias, fc1.bias, fc2.bias); W1, W2: activation-dtype weights; quick: CvT's QuickGELU;
+    rowscale: None or the DropPath factors, one per `rows_per_sample` rows -> (x2 fp32, (mean2, rstd2, h, a1, a1g) when saving)"""
+    g2, b2, bfc1, bfc2 = prm
+    h, _, mean2, rstd2 = o.layernorm_fwd(x1, g2, b2, eps)
+    if save:
+        a1g, a1 = o.linear_fwd(h, W1, bfc1, gelu=True, want_preact=True, quick=quick)
+    else:  # (inference keeps nothing: the LayerNorm output goes before fc2 allocates)
+        a1g, a1, h = o.linear_fwd(h, W1, bfc1, gelu=True, quick=quick), None, None
+    x2 = o.linear_fwd(a1g, W2, bfc2, residual=x1, rowscale=rowscale, rows_per_sample=rows_per_sample, out_f32=True)
+    return x2, ((mean2, rstd2, h, a1, a1g) if save else None)
+
+
+def _mlp_bwd(o, dyb, h, a1, a1g, W1, W2, params, quick=False, shapes2d=(None, None)):
+    """dyb: cast(DropPath * dL/dx2) [M, C]; params: (fc1.weight, fc1.bias, fc2.weight, fc2.bias) parameters; shapes2d: the matrix
+    shapes of CvT's 1x1-conv weights -> (dh, dW1, dbfc1, dW2, dbfc2); the caller's LayerNorm backward takes dh.  The two weight-gradient
+    GEMMs are leaves of the chain: side stream, bucket slots, and the CALLER joins (_side_join) before its node returns"""
+    W1_p, bfc1_p, W2_p, bfc2_p = params
+    dW2, dbfc2 = _side_run(lambda: _wgrad(dyb, a1g, W2_p, shapes2d[1], want_bias=True, bias_param=bfc2_p), dyb, a1g)
+    da1 = o.linear_dgrad(dyb, W2, gelu_preact=a1, quick=quick)
+    dW1, dbfc1 = _side_run(lambda: _wgrad(da1, h, W1_p, shapes2d[0], want_bias=True, bias_param=bfc1_p), da1, h)
+    dh = o.linear_dgrad(da1, W1)
+    return dh, dW1, dbfc1, dW2, dbfc2
+
+
+def _per_row(rowscale, rows_per_sample):
+    """(the fused MLP kernels take per-row DropPath factors)"""
+    return rowscale if rowscale is None or rows_per_sample == 1 else rowscale.repeat_interleave(rows_per_sample)
+
+
+def _swin_mlp_fwd(o, x1, prm, W1, W2, w1p, rowscale, rows_per_sample, save, next_norm=None):
+    """the MLP branch of a Swin block on x1 fp32 [M, C] -> (x2, route, what the backward of that route reads or None, the next block's
+    `pre` or None).  Routes:
+      "fused"  narrow stage: LayerNorm -> fc1 + GELU -> fc2 + residual in one kernel, the hidden activation never reaches HBM (the
+               training pass keeps x1 only: the backward recomputes).  Wide stage (C = 384), inference pass: the same, without the next
+               LayerNorm.  next_norm: (weight, bias) of the NEXT block's norm1 -- the kernel then also emits that block's `pre`
+      "wide"   wide stage, training pass: one kernel writes x2 and what the unfused backward reads (LayerNorm output and statistics,
+               pre-activation, GELU) in place of the LayerNorm launch and the two GEMM launches
+      "plain"  the unfused sequence (_mlp_fwd)"""
+    g2, b2, bfc1, bfc2 = prm
+    M, C = x1.shape
+    if (not save and _mlp_fused_infer(W1, C)) or (save and _mlp_fused_train(W1, C)):
+        rs = _per_row(rowscale, rows_per_sample)
+        w1k = W1 if C == 384 else _mlp_w(w1p, "MLP_W1_FWD")
+        if next_norm is not None and C != 384:
+            x2, nxt = o.mlp_fused_fwd(x1, g2, b2, LN_EPS, w1k, bfc1, W2, bfc2, rowscale=rs, next_norm=(next_norm[0].detach(), next_norm[1].detach()))
+            return x2, "fused", None, nxt
+        return o.mlp_fused_fwd(x1, g2, b2, LN_EPS, w1k, bfc1, W2, bfc2, rowscale=rs), "fused", None, None
+    if save and _mlp_wide_train(W1, C, M):
+        x2, a1, a1g, h, mean2, rstd2 = o.mlp_fused_fwd_train(x1, g2, b2, LN_EPS, W1, bfc1, W2, bfc2, rowscale=_per_row(rowscale, rows_per_sample))
+        return x2, "wide", (mean2, rstd2, h, a1, a1g), None
+    x2, saved = _mlp_fwd(o, x1, prm, W1, W2, LN_EPS, rowscale, rows_per_sample, save)
+    return x2, "plain", saved, None
+
+
+# ---- what a forward keeps for its backward goes by name: the routes of a block save different sets, and a backward that counted
+# positions would read another route's tensor the day one of them saves one more ----------------------------------------------------
+def _save_named(ctx, **named):
+    """ctx.save_for_backward of tensors (None allowed) and tuples of tensors under their names"""
+    flat, at = [], {}
+    for name, v in named.items():
+        if isinstance(v, (tuple, list)):
+            at[name] = (len(flat), len(flat) + len(v))
+            flat.extend(v)
+        else:
+            at[name] = len(flat)
+            flat.append(v)
+    ctx.saved_at = at
+    ctx.save_for_backward(*flat)
+
+
+def _load_named(ctx):
+    """-> namespace of what _save_named kept"""
+    t = ctx.saved_tensors
+    return types.SimpleNamespace(**{name: (tuple(t[at[0]:at[1]]) if isinstance(at, tuple) else t[at]) for name, at in ctx.saved_at.items()})
+
+
 # ------------------------------------------------------------------------------------------------
 # Swin block
 # ------------------------------------------------------------------------------------------------
 def _block_forward(x, geom, nH, index, dp, prm, wts, save, w1p=None, wattn=None):
     """x fp32 [nB, L, C].  prm: fp32 parameters; wts: activation-dtype weight copies.
-    dp: None or (scale_attn [nB], scale_mlp [nB]) DropPath factors."""
+    dp: None or (scale_attn [nB], scale_mlp [nB]) DropPath factors.
+    -> (y, None), or when saving (y, (is the attention backward the one-kernel mode, MLP route, tensors for the backward by name))"""
     o = ops_module()
     (g1, b1, table, bqkv, bproj, g2, b2, bfc1, bfc2) = prm
     (Wqkv, Wproj, W1, W2) = wts
@@ -342,10 +437,12 @@ def _block_forward(x, geom, nH, index, dp, prm, wts, save, w1p=None, wattn=None)
     # everything stays in token order: the attention kernel applies pad/roll/partition through geom.win2tok and
     # injects the qkv bias at zero-pad slots, so no GEMM ever runs on pad rows
     frag = o.new_bias_frag(nH, geom.N, x.device) if save else None  # kept for the backward (no second fill)
+    bwd_fused = False
     if wattn is not None and _attn_fused(Wqkv.dtype, C, nH, (geom,), save, [(nB * L, nB * geom.nW)]):
         rs1 = None if dp1 is None else dp1.repeat_interleave(L)
-        # (a training pass whose backward is the one-kernel mode needs no side outputs: the saved tuple keeps its length, with None in their places)
-        side = bool(save) and not _attn_bwd_fused(o, Wqkv.dtype, C, nH, (geom,), [(nB * L, nB * geom.nW)])
+        # (a training pass whose backward is the one-kernel mode needs no side outputs)
+        bwd_fused = bool(save) and _attn_bwd_fused(o, Wqkv.dtype, C, nH, (geom,), [(nB * L, nB * geom.nW)])
+        side = bool(save) and not bwd_fused
         res = o.attn_branch_fwd(x2d, g1, b1, LN_EPS, _perm_w(wattn[0]), bqkv, _perm_w(wattn[1]), bproj, geom.win2tok, L, table, geom.ws, geom.region_ids,
                                 geom.nW, geom.N, nH, scale, rowscale=rs1, bias_frag=frag, save=side)
         lse = None
@@ -361,88 +458,82 @@ def _block_forward(x, geom, nH, index, dp, prm, wts, save, w1p=None, wattn=None)
         x1 = o.linear_fwd(ao, Wproj, bproj, residual=x2d, rowscale=dp1, rows_per_sample=L, out_f32=True)
     if not save:  # inference keeps nothing for a backward: the attention branch's intermediates go before the MLP allocates its own
         xw = qkv = ao = None
-    if (not save and _mlp_fused_infer(W1, C)) or (save and _mlp_fused_train(W1, C)):
-        rs2 = None if dp2 is None else dp2.repeat_interleave(L)  # (the fused kernels take per-row DropPath factors)
-        x2 = o.mlp_fused_fwd(x1, g2, b2, LN_EPS, W1 if C == 384 else _mlp_w(w1p, "MLP_W1_FWD"), bfc1, W2, bfc2, rowscale=rs2)
-        saved = (mean1, rstd1, xw, qkv, ao, x1, lse, frag) if save else None
-        return x2.view(nB, L, C), saved
-    elif save and _mlp_wide_train(W1, C, nB * L):
-        rs2 = None if dp2 is None else dp2.repeat_interleave(L)
-        x2, a1, a1g, h, mean2, rstd2 = o.mlp_fused_fwd_train(x1, g2, b2, LN_EPS, W1, bfc1, W2, bfc2, rowscale=rs2)
-    else:
-        h, _, mean2, rstd2 = o.layernorm_fwd(x1, g2, b2, LN_EPS)
-        if save:
-            a1g, a1 = o.linear_fwd(h, W1, bfc1, gelu=True, want_preact=True)
-        else:
-            a1g, a1 = o.linear_fwd(h, W1, bfc1, gelu=True), None
-            h = None
-        x2 = o.linear_fwd(a1g, W2, bfc2, residual=x1, rowscale=dp2, rows_per_sample=L, out_f32=True)
-    saved = (mean1, rstd1, xw, qkv, ao, x1, mean2, rstd2, h, a1, a1g, lse, frag) if save else None
-    return x2.view(nB, L, C), saved
+    x2, route, mlp_saved, _ = _swin_mlp_fwd(o, x1, (g2, b2, bfc1, bfc2), W1, W2, w1p, dp2, L, save)
+    if not save:
+        return x2.view(nB, L, C), None
+    saved = dict(mean1=mean1, rstd1=rstd1, xw=xw, qkv=qkv, ao=ao, x1=x1, lse=lse, frag=frag, **dict(zip(_MLP_SAVED, mlp_saved or ())))
+    return x2.view(nB, L, C), (bwd_fused, route, saved)
 
 
 class SwinBlockFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, geom, nH, index, dp, g1, b1, table, Wqkv_p, bqkv, Wproj_p, bproj, g2, b2, W1_p, bfc1, W2_p, bfc2):
-        wts = (_weight(Wqkv_p), _weight(Wproj_p), _weight(W1_p), _weight(W2_p))
+        Wqkv, Wproj, W1, W2 = wts = (_weight(Wqkv_p), _weight(Wproj_p), _weight(W1_p), _weight(W2_p))
         x = x.contiguous()
-        y, saved = _block_forward(x, geom, nH, index, dp, (g1, b1, table, bqkv, bproj, g2, b2, bfc1, bfc2), wts, True, W1_p, (Wqkv_p, Wproj_p))
+        y, (ctx.attn_bwd_fused, ctx.mlp_route, saved) = _block_forward(x, geom, nH, index, dp, (g1, b1, table, bqkv, bproj, g2, b2, bfc1, bfc2), wts, True, W1_p,
+                                                                       (Wqkv_p, Wproj_p))
         ctx.geom, ctx.nH, ctx.dp = geom, nH, dp
         ctx.wparams = (Wqkv_p, Wproj_p, W1_p, W2_p)
         ctx.mlp_params = (g2, b2, W1_p, bfc1, W2_p, bfc2)
-        ctx.fused_mlp = len(saved) == 8
-        ctx.attn_bwd_fused = saved[3] is None  # (no qkv was saved: _block_forward chose the one-kernel backward)
         ctx.attn_params = (g1, b1, table, Wqkv_p, bqkv, Wproj_p, bproj)
-        ctx.save_for_backward(x, index, g1, table, g2, bqkv, b2, bfc1, *wts, *saved)
+        _save_named(ctx, x=x, index=index, g1=g1, table=table, g2=g2, bqkv=bqkv, b2=b2, bfc1=bfc1, Wqkv=Wqkv, Wproj=Wproj, W1=W1, W2=W2, **saved)
         return y
 
     @staticmethod
     def backward(ctx, gy):
         o = ops_module()
         geom, nH, dp = ctx.geom, ctx.nH, ctx.dp
-        if ctx.fused_mlp:
-            (x, index, g1, table, g2, bqkv, b2, bfc1, Wqkv, Wproj, W1, W2, mean1, rstd1, xw, qkv, ao, x1, lse, frag) = ctx.saved_tensors
-        else:
-            (x, index, g1, table, g2, bqkv, b2, bfc1, Wqkv, Wproj, W1, W2, mean1, rstd1, xw, qkv, ao, x1, mean2, rstd2, h, a1,
-             a1g, lse, frag) = ctx.saved_tensors
+        s = _load_named(ctx)
+        x, x1, g1, g2, bqkv = s.x, s.x1, s.g1, s.g2, s.bqkv
         nB, L, C = x.shape
         M = nB * L
         scale = (C // nH) ** -0.5
         dp1, dp2 = (None, None) if dp is None else dp
         gy = gy.contiguous().view(M, C)
         Wqkv_p, Wproj_p, W1_p, W2_p = ctx.wparams
+        g1_p, b1_p, table_p, _, bqkv_p, _, bproj_p = ctx.attn_params
+        g2_p, b2_p, _, bfc1_p, _, bfc2_p = ctx.mlp_params
         # ---- MLP branch ----
-        onchip = ctx.fused_mlp and _mlp_dw_onchip(o, W1, C)  # (the kernel scales and casts gy itself: no activation-dtype copy is read)
+        fused_mlp = ctx.mlp_route == "fused"
+        onchip = fused_mlp and _mlp_dw_onchip(o, s.W1, C)  # (the kernel scales and casts gy itself: no activation-dtype copy is read)
         dyb = None if onchip else o.gather_cast(gy, M, rowscale=dp2, rows_per_sample=L)
-        if ctx.fused_mlp:
-            rs2 = None if dp2 is None else dp2.repeat_interleave(L)
-            rs1 = None if dp1 is None else dp1.repeat_interleave(L)
-            gx1, dyw, dg2, db2, dW1, dbfc1, dW2, dbfc2 = _mlp_branch_bwd(o, x1, gy, dyb, g2, b2, W1, bfc1, ctx.mlp_params, rs2, rs1)
+        if fused_mlp:
+            gx1, dyw, dg2, db2, dW1, dbfc1, dW2, dbfc2 = _mlp_branch_bwd(o, x1, gy, dyb, g2, s.b2, s.W1, s.bfc1, ctx.mlp_params, _per_row(dp2, L), _per_row(dp1, L))
         else:
-            dW2, dbfc2 = _wgrad(dyb, a1g, W2_p, want_bias=True)
-            da1 = o.linear_dgrad(dyb, W2, gelu_preact=a1)
-            dW1, dbfc1 = _wgrad(da1, h, W1_p, want_bias=True)
-            dh = o.linear_dgrad(da1, W1)
-            # ---- attention branch ---- (the LayerNorm backward also emits the DropPath-scaled activation-dtype copy of gx1)
-            gx1, dyw, dg2, db2 = o.layernorm_bwd_cast(dh, x1, mean2, rstd2, g2, g_in=gy, rowscale=dp1, rows_per_sample=L)
+            dh, dW1, dbfc1, dW2, dbfc2 = _mlp_bwd(o, dyb, s.h, s.a1, s.a1g, s.W1, s.W2, (W1_p, bfc1_p, W2_p, bfc2_p))
+            ln2 = _ln_sinks(g2_p, b2_p)
+            # (the LayerNorm backward also emits the DropPath-scaled activation-dtype copy of gx1, the attention branch's operand)
+            gx1, dyw, dg2, db2 = o.layernorm_bwd_cast(dh, x1, s.mean2, s.rstd2, g2, g_in=gy, rowscale=dp1, rows_per_sample=L, gb_out=ln2)
+            dg2, db2 = _alias(dg2, ln2), _alias(db2, ln2)
+        # ---- attention branch ----
         if ctx.attn_bwd_fused:
             gx, _, dg1, db1, dtable, dWqkv, dbqkv, dWproj, dbproj = _attn_branch_bwd(
-                o, x.view(M, C), gx1, ((0, nB, L, geom),), nH, (frag,), index, table, Wqkv, ctx.attn_params, g1, ctx.attn_params[1].detach(), bqkv,
-                None if dp1 is None else dp1.repeat_interleave(L), None, False)
+                o, x.view(M, C), gx1, ((0, nB, L, geom),), nH, (s.frag,), s.index, s.table, s.Wqkv, ctx.attn_params, g1, b1_p.detach(), bqkv,
+                _per_row(dp1, L), None, False)
             _side_join()
             return (gx.view(nB, L, C), None, None, None, None, dg1, db1, dtable, dWqkv, dbqkv, dWproj, dbproj, dg2, db2, dW1, dbfc1,
                     dW2, dbfc2)
-        dWproj, dbproj = _wgrad(dyw, ao, Wproj_p, want_bias=True)
-        dao = o.linear_dgrad(dyw, Wproj)
-        dqkv, dbias_ws, dpad_ws = o.window_attn_bwd(qkv, bqkv, geom.win2tok, L, dao, ao, lse, None, geom.ws, geom.region_ids,
-                                                    geom.nW, geom.N, nH, scale, bias_frag=frag)
-        dtable = o.relpos_bias_bwd(dbias_ws, index, geom.N, table.shape[0], **_relpos_kw(o))
-        dWqkv, dbqkv = _wgrad(dqkv, xw, Wqkv_p, want_bias=True)
-        o.colsum(dpad_ws, out=dbqkv[C:], accumulate=True)  # k/v bias gradient from the zero-pad slots
-        dxw = o.linear_dgrad(dqkv, Wqkv)
-        gx, dg1, db1 = o.layernorm_bwd(dxw, x.view(M, C), mean1, rstd1, g1, g_in=gx1)
+        dWproj, dbproj = _side_run(lambda: _wgrad(dyw, s.ao, Wproj_p, want_bias=True, bias_param=bproj_p), dyw, s.ao)
+        dao = o.linear_dgrad(dyw, s.Wproj)
+        dqkv, dbias_ws, dpad_ws = o.window_attn_bwd(s.qkv, bqkv, geom.win2tok, L, dao, s.ao, s.lse, None, geom.ws, geom.region_ids,
+                                                    geom.nW, geom.N, nH, scale, bias_frag=s.frag)
+        tsink = P.grad_out(table_p)
+        dtable = _alias(o.relpos_bias_bwd(dbias_ws, s.index, geom.N, s.table.shape[0], out=tsink, accumulate=False if tsink is not None else None,
+                                          **_relpos_kw(o)), tsink)
+        wsink, bsink = P.grad_out(Wqkv_p), P.grad_out(bqkv_p)
+
+        def wqkv():
+            dWqkv, dbqkv = o.linear_wgrad(dqkv, s.xw, out=wsink, want_bias=True, db_out=bsink)
+            o.colsum(dpad_ws, out=dbqkv[C:], accumulate=True)  # k/v bias gradient from the zero-pad slots
+            return dWqkv, dbqkv
+
+        dWqkv, dbqkv = _side_run(wqkv, dqkv, s.xw, dpad_ws)
+        dWqkv, dbqkv = _alias(dWqkv, wsink), _alias(dbqkv, bsink)
+        dxw = o.linear_dgrad(dqkv, s.Wqkv)
+        ln1 = _ln_sinks(g1_p, b1_p)
+        gx, dg1, db1 = o.layernorm_bwd(dxw, x.view(M, C), s.mean1, s.rstd1, g1, g_in=gx1, gb_out=ln1)
         _side_join()
-        return (gx.view(nB, L, C), None, None, None, None, dg1, db1, dtable, dWqkv, dbqkv, dWproj, dbproj, dg2, db2, dW1, dbfc1,
+        return (gx.view(nB, L, C), None, None, None, None, _alias(dg1, ln1), _alias(db1, ln1), dtable, dWqkv, dbqkv, dWproj, dbproj, dg2, db2, dW1, dbfc1,
                 dW2, dbfc2)
 
 
@@ -456,7 +547,7 @@ def _block_forward_multi(X, segs, nH, dp_rows, prm, wts, save, pre=None, next_no
     """X fp32 [M, C]; segs: tuple of (row0, nB, L, geom); dp_rows: None or (per-row DropPath scale attn [M], mlp [M]).
     pre: (norm1(X) in the activation dtype, mean, rstd) when the previous block's fused MLP kernel already produced them;
     next_norm: (weight, bias) of the NEXT block's norm1 -- the fused MLP kernel then also emits that block's `pre`.
-    -> (y, saved, lses, next block's pre or None)"""
+    -> (y, None or (is the attention backward the one-kernel mode, MLP route, tensors for the backward by name), lses, next block's pre or None)"""
     o = ops_module()
     (g1, b1, table, bqkv, bproj, g2, b2, bfc1, bfc2) = prm
     (Wqkv, Wproj, W1, W2) = wts
@@ -465,13 +556,15 @@ def _block_forward_multi(X, segs, nH, dp_rows, prm, wts, save, pre=None, next_no
     dp1, dp2 = (None, None) if dp_rows is None else dp_rows
     fused_attn = wattn is not None and _attn_fused(Wqkv.dtype, C, nH, [sg[3] for sg in segs], save, [(sg[1] * sg[2], sg[1] * sg[3].nW) for sg in segs])
     lses, frags = [], {}
+    bwd_fused = False
     if fused_attn:
         # the whole branch in one kernel per resolution group; `pre` (the LayerNorm output the previous block's fused MLP kernel may
         # have produced) is not needed: the kernel normalises the rows it loads for the residual anyway
         Wq_p, Wp_p = _perm_w(wattn[0]), _perm_w(wattn[1])
         x1 = torch.empty_like(X)
         # (a training pass whose backward is the one-kernel mode needs no side outputs)
-        side = bool(save) and not _attn_bwd_fused(o, Wqkv.dtype, C, nH, [sg[3] for sg in segs], [(sg[1] * sg[2], sg[1] * sg[3].nW) for sg in segs])
+        bwd_fused = bool(save) and _attn_bwd_fused(o, Wqkv.dtype, C, nH, [sg[3] for sg in segs], [(sg[1] * sg[2], sg[1] * sg[3].nW) for sg in segs])
+        side = bool(save) and not bwd_fused
         if side:
             xw = torch.empty((M, C), dtype=Wqkv.dtype, device=X.device)
             qkv = torch.empty((M, 3 * C), dtype=Wqkv.dtype, device=X.device)
@@ -509,29 +602,11 @@ def _block_forward_multi(X, segs, nH, dp_rows, prm, wts, save, pre=None, next_no
                                        out=ao[r0:r1], bias_frag=frags[(geom.ws, geom.N)])
             lses.append((lse, frags[(geom.ws, geom.N)]))
         x1 = o.linear_fwd(ao, Wproj, bproj, residual=X, rowscale=dp1, rows_per_sample=1, out_f32=True)
-    if (not save and _mlp_fused_infer(W1, C)) or (save and _mlp_fused_train(W1, C)):
-        # narrow stage: LayerNorm -> fc1 + GELU -> fc2 + residual in one kernel, the hidden activation never reaches HBM (the
-        # training pass keeps x1 only: the backward recomputes).  Wide stage (C = 384), inference pass: the same, without the next LayerNorm
-        nxt = None
-        w1k = W1 if C == 384 else _mlp_w(w1p, "MLP_W1_FWD")
-        if next_norm is not None and C != 384:
-            x2, nxt = o.mlp_fused_fwd(x1, g2, b2, LN_EPS, w1k, bfc1, W2, bfc2, rowscale=dp2, next_norm=(next_norm[0].detach(), next_norm[1].detach()))
-        else:
-            x2 = o.mlp_fused_fwd(x1, g2, b2, LN_EPS, w1k, bfc1, W2, bfc2, rowscale=dp2)
-        return x2, ((mean1, rstd1, xw, qkv, ao, x1) if save else None), lses, nxt
-    elif save and _mlp_wide_train(W1, C, M):
-        # wide stage, training pass: one kernel writes x2 and what the unfused backward below reads (LayerNorm output and statistics,
-        # pre-activation, GELU) in place of the LayerNorm launch and the two GEMM launches
-        x2, a1, a1g, h, mean2, rstd2 = o.mlp_fused_fwd_train(x1, g2, b2, LN_EPS, W1, bfc1, W2, bfc2, rowscale=dp2)
-    else:
-        h, _, mean2, rstd2 = o.layernorm_fwd(x1, g2, b2, LN_EPS)
-        if save:
-            a1g, a1 = o.linear_fwd(h, W1, bfc1, gelu=True, want_preact=True)
-        else:
-            a1g, a1 = o.linear_fwd(h, W1, bfc1, gelu=True), None
-        x2 = o.linear_fwd(a1g, W2, bfc2, residual=x1, rowscale=dp2, rows_per_sample=1, out_f32=True)
-    saved = (mean1, rstd1, xw, qkv, ao, x1, mean2, rstd2, h, a1, a1g) if save else None
-    return x2, saved, lses, None
+    x2, route, mlp_saved, nxt = _swin_mlp_fwd(o, x1, (g2, b2, bfc1, bfc2), W1, W2, w1p, dp2, 1, save, next_norm)
+    if not save:
+        return x2, None, lses, nxt
+    saved = dict(mean1=mean1, rstd1=rstd1, xw=xw, qkv=qkv, ao=ao, x1=x1, **dict(zip(_MLP_SAVED, mlp_saved or ())))
+    return x2, (bwd_fused, route, saved), lses, nxt
 
 
 class SwinBlockMultiFn(torch.autograd.Function):
@@ -549,19 +624,17 @@ class SwinBlockMultiFn(torch.autograd.Function):
                 W2_p, bfc2):
         """pre / next_norm: see _block_forward_multi (plain tuples: no gradient flows through them -- norm1's own backward uses
         the saved statistics).  Third output: the next block's `pre` tuple flattened (xw, mean, rstd), or three None"""
-        wts = (_weight(Wqkv_p), _weight(Wproj_p), _weight(W1_p), _weight(W2_p))
+        Wqkv, Wproj, W1, W2 = wts = (_weight(Wqkv_p), _weight(Wproj_p), _weight(W1_p), _weight(W2_p))
         X = X.contiguous()
-        y, saved, lses, nxt = _block_forward_multi(X, segs, nH, dp_rows, (g1, b1, table, bqkv, bproj, g2, b2, bfc1, bfc2), wts, True, pre, next_norm, W1_p,
-                                                   (Wqkv_p, Wproj_p))
+        y, (ctx.attn_bwd_fused, ctx.mlp_route, saved), lses, nxt = _block_forward_multi(X, segs, nH, dp_rows, (g1, b1, table, bqkv, bproj, g2, b2, bfc1, bfc2), wts,
+                                                                                        True, pre, next_norm, W1_p, (Wqkv_p, Wproj_p))
         ctx.segs, ctx.nH, ctx.dp_rows, ctx.lses = segs, nH, dp_rows, lses
         ctx.wparams = (Wqkv_p, Wproj_p, W1_p, W2_p)
         ctx.sparams = (g1, b1, table, bqkv, bproj, g2, b2, bfc1, bfc2)  # small parameters: their gradients go to bucket slots too
         ctx.emit_shadow, ctx.prev_scale = Xsh is not None, prev_scale
         ctx.set_materialize_grads(False)
-        ctx.fused_mlp = len(saved) == 6
-        ctx.attn_bwd_fused = saved[3] is None  # (no qkv was saved: _block_forward_multi chose the one-kernel backward)
-        ctx.save_for_backward(X, index, g1, table, g2, bqkv, b2, bfc1, *wts, *saved)
-        ysh = torch.empty(X.shape, dtype=wts[0].dtype, device=X.device)
+        _save_named(ctx, X=X, index=index, g1=g1, table=table, g2=g2, bqkv=bqkv, b2=b2, bfc1=bfc1, Wqkv=Wqkv, Wproj=Wproj, W1=W1, W2=W2, **saved)
+        ysh = torch.empty(X.shape, dtype=Wqkv.dtype, device=X.device)
         if nxt is None:
             return y, ysh, None, None, None
         ctx.mark_non_differentiable(*nxt)
@@ -571,10 +644,8 @@ class SwinBlockMultiFn(torch.autograd.Function):
     def backward(ctx, gy, gysh, *_unused):
         o = ops_module()
         segs, nH, dp_rows = ctx.segs, ctx.nH, ctx.dp_rows
-        if ctx.fused_mlp:
-            (X, index, g1, table, g2, bqkv, b2, bfc1, Wqkv, Wproj, W1, W2, mean1, rstd1, xw, qkv, ao, x1) = ctx.saved_tensors
-        else:
-            (X, index, g1, table, g2, bqkv, b2, bfc1, Wqkv, Wproj, W1, W2, mean1, rstd1, xw, qkv, ao, x1, mean2, rstd2, h, a1, a1g) = ctx.saved_tensors
+        s = _load_named(ctx)
+        X, index, g1, table, g2, bqkv, Wqkv, x1, xw, qkv, ao = s.X, s.index, s.g1, s.table, s.g2, s.bqkv, s.Wqkv, s.x1, s.xw, s.qkv, s.ao
         M, C = X.shape
         scale = (C // nH) ** -0.5
         dp1, dp2 = (None, None) if dp_rows is None else dp_rows
@@ -582,20 +653,18 @@ class SwinBlockMultiFn(torch.autograd.Function):
         Wqkv_p, Wproj_p, W1_p, W2_p = ctx.wparams
         g1_p, b1_p, table_p, bqkv_p, bproj_p, g2_p, b2_p, bfc1_p, bfc2_p = ctx.sparams
         # ---- MLP branch ----
+        fused_mlp = ctx.mlp_route == "fused"
         if gysh is not None:
             dyb = gysh.contiguous()
         else:
-            dyb = None if (ctx.fused_mlp and _mlp_dw_onchip(o, W1, C)) else o.gather_cast(gy, M, rowscale=dp2, rows_per_sample=1)
-        if ctx.fused_mlp:
-            gx1, dyw, dg2, db2, dW1, dbfc1, dW2, dbfc2 = _mlp_branch_bwd(o, x1, gy, dyb, g2, b2, W1, bfc1,
+            dyb = None if (fused_mlp and _mlp_dw_onchip(o, s.W1, C)) else o.gather_cast(gy, M, rowscale=dp2, rows_per_sample=1)
+        if fused_mlp:
+            gx1, dyw, dg2, db2, dW1, dbfc1, dW2, dbfc2 = _mlp_branch_bwd(o, x1, gy, dyb, g2, s.b2, s.W1, s.bfc1,
                                                                           (g2_p, b2_p, W1_p, bfc1_p, W2_p, bfc2_p), dp2, dp1)
         else:
-            dW2, dbfc2 = _side_run(lambda: _wgrad(dyb, a1g, W2_p, want_bias=True, bias_param=bfc2_p), dyb, a1g)
-            da1 = o.linear_dgrad(dyb, W2, gelu_preact=a1)
-            dW1, dbfc1 = _side_run(lambda: _wgrad(da1, h, W1_p, want_bias=True, bias_param=bfc1_p), da1, h)
-            dh = o.linear_dgrad(da1, W1)
+            dh, dW1, dbfc1, dW2, dbfc2 = _mlp_bwd(o, dyb, s.h, s.a1, s.a1g, s.W1, s.W2, (W1_p, bfc1_p, W2_p, bfc2_p))
             ln2 = _ln_sinks(g2_p, b2_p)
-            gx1, dyw, dg2, db2 = o.layernorm_bwd_cast(dh, x1, mean2, rstd2, g2, g_in=gy, rowscale=dp1, rows_per_sample=1, gb_out=ln2)
+            gx1, dyw, dg2, db2 = o.layernorm_bwd_cast(dh, x1, s.mean2, s.rstd2, g2, g_in=gy, rowscale=dp1, rows_per_sample=1, gb_out=ln2)
             dg2, db2 = _alias(dg2, ln2), _alias(db2, ln2)
         # ---- attention branch ----
         if ctx.attn_bwd_fused:
@@ -605,7 +674,7 @@ class SwinBlockMultiFn(torch.autograd.Function):
             _side_join()
             return (gx, gxb, None, None, None, None, None, None, None, dg1, db1, dtable, dWqkv, dbqkv, dWproj, dbproj, dg2, db2, dW1, dbfc1, dW2, dbfc2)
         dWproj, dbproj = _side_run(lambda: _wgrad(dyw, ao, Wproj_p, want_bias=True, bias_param=bproj_p), dyw, ao)
-        dao = o.linear_dgrad(dyw, Wproj)
+        dao = o.linear_dgrad(dyw, s.Wproj)
         dqkv = torch.empty_like(qkv)
         tsink = P.grad_out(table_p)
         # the bias-gradient slabs of all groups in one buffer: ONE fold + scatter launch per block (every launch between the large kernels of
@@ -634,9 +703,9 @@ class SwinBlockMultiFn(torch.autograd.Function):
         dxw = o.linear_dgrad(dqkv, Wqkv)
         ln1 = _ln_sinks(g1_p, b1_p)
         if ctx.emit_shadow:  # the previous block's operand rides along with dL/dX
-            gx, gxb, dg1, db1 = o.layernorm_bwd_cast(dxw, X, mean1, rstd1, g1, g_in=gx1, rowscale=ctx.prev_scale, rows_per_sample=1, gb_out=ln1)
+            gx, gxb, dg1, db1 = o.layernorm_bwd_cast(dxw, X, s.mean1, s.rstd1, g1, g_in=gx1, rowscale=ctx.prev_scale, rows_per_sample=1, gb_out=ln1)
         else:
-            gx, dg1, db1 = o.layernorm_bwd(dxw, X, mean1, rstd1, g1, g_in=gx1, gb_out=ln1)
+            gx, dg1, db1 = o.layernorm_bwd(dxw, X, s.mean1, s.rstd1, g1, g_in=gx1, gb_out=ln1)
             gxb = None
         dg1, db1 = _alias(dg1, ln1), _alias(db1, ln1)
         _side_join()
@@ -1038,32 +1107,42 @@ def _last_logits(o, z, w, stats):
     return o.linear_fwd(z, w), None, None
 
 
-def _head_forward(x, prm, save, stats=None):
+def _head_forward(x, params, save, stats=None):
+    """DINOHead without BatchNorm and with any number of Linear layers (vision_transformer.py:388-402, 414-418): nlayers = 1 is one
+    Linear into the bottleneck, otherwise Linear + GELU (nlayers - 1 times) and a last Linear; then l2-normalise and the weight-normed
+    last layer.  params = (W_1, b_1, ..., W_L, b_L, weight_v, weight_g) -> ((logits, row_max | None, row_lse | None), tensors for the
+    backward by name).  save False: an inference pass, which writes no pre-activations"""
     o = ops_module()
-    W1p, b1, W2p, b2, W3p, b3, v, g = prm
-    W1, W2, W3 = _weight(W1p), _weight(W2p), _weight(W3p)
-    xa = o.cast_to_act(x.contiguous())
-    if save:
-        h1g, h1 = o.linear_fwd(xa, W1, b1, gelu=True, want_preact=True)
-        h2g, h2 = o.linear_fwd(h1g, W2, b2, gelu=True, want_preact=True)
-    else:
-        h1g, h1 = o.linear_fwd(xa, W1, b1, gelu=True), None
-        h2g, h2 = o.linear_fwd(h1g, W2, b2, gelu=True), None
-    h3 = o.linear_fwd(h2g, W3, b3)
-    z, inv = o.l2norm_fwd(h3)
+    L = (len(params) - 2) // 2
+    Wp, bp = params[0:2 * L:2], params[1:2 * L:2]
+    v, g = params[2 * L:]
+    Ws = [_weight(w) for w in Wp]
+    acts, pres = [o.cast_to_act(x.contiguous())], []
+    for i in range(L - 1):
+        if save:
+            hg, hpre = o.linear_fwd(acts[-1], Ws[i], bp[i], gelu=True, want_preact=True)
+        else:
+            hg, hpre = o.linear_fwd(acts[-1], Ws[i], bp[i], gelu=True), None
+        acts.append(hg)
+        pres.append(hpre)
+    hL = o.linear_fwd(acts[-1], Ws[L - 1], bp[L - 1])
+    z, inv = o.l2norm_fwd(hL)
     w, winv = _last_layer_weight(v, g)
-    logits = _last_logits(o, z, w, stats)
-    return logits, (W1, W2, W3, xa, h1, h1g, h2, h2g, z, inv, w, winv)
+    return _last_logits(o, z, w, stats), dict(z=z, inv=inv, w=w, winv=winv, Ws=Ws, acts=acts, pres=pres)
 
 
 class DinoHeadFn(torch.autograd.Function):
+    """_head_forward and its backward: every weight gradient is a leaf on the side stream, the last layer's together with the
+    weight-norm backward it feeds"""
+
     @staticmethod
-    def forward(ctx, x, stats, W1p, b1, W2p, b2, W3p, b3, v, g):
-        (logits, mx, lse), saved = _head_forward(x, (W1p, b1, W2p, b2, W3p, b3, v, g), True, stats)
-        ctx.save_for_backward(v, g, *saved)
+    def forward(ctx, x, stats, *params):
+        (logits, mx, lse), kept = _head_forward(x, params, True, stats)
+        L = (len(params) - 2) // 2
+        v, g = params[2 * L:]
         ctx.need_dg = g.requires_grad
-        ctx.wparams = (W1p, W2p, W3p, v)
-        ctx.bparams = (b1, b2, b3)
+        ctx.wparams, ctx.bparams, ctx.vparam = params[0:2 * L:2], params[1:2 * L:2], v
+        _save_named(ctx, v=v, g=g, **kept)
         if mx is not None:
             ctx.mark_non_differentiable(mx, lse)
         return logits, mx, lse
@@ -1071,96 +1150,40 @@ class DinoHeadFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dlogits, _gmx=None, _glse=None):
         o = ops_module()
-        v, g, W1, W2, W3, xa, h1, h1g, h2, h2g, z, inv, w, winv = ctx.saved_tensors
+        s = _load_named(ctx)
+        L = len(s.Ws)
         dlogits = dlogits.contiguous()
-        W1p, W2p, W3p, vp = ctx.wparams
-        b1p, b2p, b3p = ctx.bparams
-        dz = o.linear_dgrad(dlogits, w)
-        sink = P.grad_out(vp)
+        dz = o.linear_dgrad(dlogits, s.w)
+        sink = P.grad_out(ctx.vparam)
 
         def wlast():
-            dw = o.linear_wgrad(dlogits, z)
-            return o.weightnorm_bwd(dw, v, g, winv, ctx.need_dg, dv_out=sink)
+            dw = o.linear_wgrad(dlogits, s.z)
+            return o.weightnorm_bwd(dw, s.v, s.g, s.winv, ctx.need_dg, dv_out=sink)
 
-        dv, dg = _side_run(wlast, dlogits, z)
-        if sink is not None:
-            dv = dv.detach()  # a fresh alias of the bucket slot (see _wgrad)
-        dh3 = o.l2norm_bwd(dz, z, inv)
-        dW3, db3 = _side_run(lambda: _wgrad(dh3, h2g, W3p, want_bias=True, bias_param=b3p), dh3, h2g)
-        dh2 = o.linear_dgrad(dh3, W3, gelu_preact=h2)
-        dW2, db2 = _side_run(lambda: _wgrad(dh2, h1g, W2p, want_bias=True, bias_param=b2p), dh2, h1g)
-        dh1 = o.linear_dgrad(dh2, W2, gelu_preact=h1)
-        dW1, db1 = _side_run(lambda: _wgrad(dh1, xa, W1p, want_bias=True, bias_param=b1p), dh1, xa)
-        dx = o.linear_dgrad(dh1, W1, out_f32=True)
+        dv, dg = _side_run(wlast, dlogits, s.z)
+        dh = o.l2norm_bwd(dz, s.z, s.inv)
+        grads = [None] * (2 * L)
+        for i in range(L - 1, -1, -1):
+            grads[2 * i], grads[2 * i + 1] = _side_run(lambda dh=dh, i=i: _wgrad(dh, s.acts[i], ctx.wparams[i], want_bias=True, bias_param=ctx.bparams[i]),
+                                                       dh, s.acts[i])
+            if i > 0:
+                dh = o.linear_dgrad(dh, s.Ws[i], gelu_preact=s.pres[i - 1])
+        dx = o.linear_dgrad(dh, s.Ws[0], out_f32=True)
         _side_join()
-        return dx, None, dW1, db1, dW2, db2, dW3, db3, dv, dg
+        return (dx, None) + tuple(grads) + (_alias(dv, sink), dg)
 
 
 def dino_head(x, prm, stats=None):
-    """-> (logits, row_max, row_lse): the statistics are None unless stats = (inv_temp, center) was given and the shape allows"""
+    """prm = (W_1, b_1, ..., W_L, b_L, weight_v, weight_g) -> (logits, row_max, row_lse): the statistics are None unless stats =
+    (inv_temp, center) was given and the shape allows"""
     if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in prm)):
         return DinoHeadFn.apply(x, stats, *prm)
     return _head_forward(x, prm, False, stats)[0]
 
 
-class DinoHeadNFn(torch.autograd.Function):
-    """DINOHead with any number of Linear layers (vision_transformer.py:388-402, nlayers != 3, no BatchNorm): nlayers = 1 is one
-    Linear into the bottleneck, otherwise Linear + GELU (nlayers - 1 times) and a last Linear; then l2-normalise and the weight-normed
-    last layer as in DinoHeadFn.  params = (W_1, b_1, ..., W_L, b_L, weight_v, weight_g)."""
-
-    @staticmethod
-    def forward(ctx, x, stats, *params):
-        o = ops_module()
-        L = (len(params) - 2) // 2
-        Wp, bp = params[0:2 * L:2], params[1:2 * L:2]
-        v, g = params[2 * L], params[2 * L + 1]
-        Ws = [_weight(w) for w in Wp]
-        h = o.cast_to_act(x.contiguous())
-        acts, pres = [h], []
-        for i in range(L - 1):
-            hg, hpre = o.linear_fwd(acts[-1], Ws[i], bp[i], gelu=True, want_preact=True)
-            acts.append(hg)
-            pres.append(hpre)
-        hL = o.linear_fwd(acts[-1], Ws[L - 1], bp[L - 1])
-        z, inv = o.l2norm_fwd(hL)
-        w, winv = _last_layer_weight(v, g)
-        logits, mx, lse = _last_logits(o, z, w, stats)
-        ctx.L = L
-        ctx.need_dg = g.requires_grad
-        ctx.wparams, ctx.bparams, ctx.vparam = tuple(Wp), tuple(bp), v
-        ctx.save_for_backward(v, g, z, inv, w, winv, *Ws, *acts, *pres)
-        if mx is not None:
-            ctx.mark_non_differentiable(mx, lse)
-        return logits, mx, lse
-
-    @staticmethod
-    def backward(ctx, dlogits, _gmx=None, _glse=None):
-        o = ops_module()
-        L = ctx.L
-        t = ctx.saved_tensors
-        v, g, z, inv, w, winv = t[:6]
-        Ws, acts, pres = t[6:6 + L], t[6 + L:6 + 2 * L], t[6 + 2 * L:]
-        dlogits = dlogits.contiguous()
-        dz = o.linear_dgrad(dlogits, w)
-        dw = o.linear_wgrad(dlogits, z)
-        sink = P.grad_out(ctx.vparam)
-        dv, dg = o.weightnorm_bwd(dw, v, g, winv, ctx.need_dg, dv_out=sink)
-        if sink is not None:
-            dv = dv.detach()
-        dh = o.l2norm_bwd(dz, z, inv)
-        grads = [None] * (2 * L)
-        for i in range(L - 1, -1, -1):
-            grads[2 * i], grads[2 * i + 1] = _wgrad(dh, acts[i], ctx.wparams[i], want_bias=True, bias_param=ctx.bparams[i])
-            if i > 0:
-                dh = o.linear_dgrad(dh, Ws[i], gelu_preact=pres[i - 1])
-        dx = o.linear_dgrad(dh, Ws[0], out_f32=True)
-        return (dx, None) + tuple(grads) + (dv, dg)
-
-
 def dino_head_n(x, lin_params, v, g, stats=None):
     """lin_params: [(W, b), ...] of the head's Linear layers in order -> (logits, row_max | None, row_lse | None)"""
-    flat = [p for wb in lin_params for p in wb]
-    return DinoHeadNFn.apply(x, stats, *flat, v, g)
+    return dino_head(x, [p for wb in lin_params for p in wb] + [v, g], stats)
 
 
 class ApeAddFn(torch.autograd.Function):
@@ -1208,99 +1231,52 @@ def _head_bn_coef(o, d, st, gam, bet):
     return coef, n
 
 
+def _bn_gelu_bwd(o, dh, d, coef, gam, n, group, eval_bn):
+    """dh = dL/d GELU(BN(d)) -> (dL/dd, dgamma, dbeta)"""
+    du = o.col_affine2(d, coef[0], coef[1], x2=dh, act=2)     # through the GELU, at the rebuilt BN output
+    red = o.bn_bwd_local(o.col_sums2(du, d), coef)            # (sum du, sum du*xhat) of this rank = (d beta, d gamma)
+    dbet, dgam = red[0].clone(), red[1].clone()
+    if eval_bn:
+        abc = o.bn_bwd_coeffs(None, n, gam, coef)
+    else:
+        _allreduce_stats(red, group)
+        abc = o.bn_bwd_coeffs(red, n, gam, coef)
+    return o.col_affine2(du, abc[0], abc[2], d, abc[1]), dgam, dbet
+
+
 class DinoHeadBnFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x, st1, st2, stats, W1p, b1, g1, be1, W2p, b2, g2, be2, W3p, b3, v, g):
-        o = ops_module()
-        W1, W2, W3 = _weight(W1p), _weight(W2p), _weight(W3p)
-        xa = o.cast_to_act(x.contiguous())
-        gam1, bet1, gam2, bet2 = (t.detach().contiguous() for t in (g1, be1, g2, be2))
-        d1 = o.linear_fwd(xa, W1, b1)
-        coef1, n1 = _head_bn_coef(o, d1, st1, gam1, bet1)
-        h1 = o.col_affine2(d1, coef1[0], coef1[1], act=1)
-        d2 = o.linear_fwd(h1, W2, b2)
-        coef2, n2 = _head_bn_coef(o, d2, st2, gam2, bet2)
-        h2 = o.col_affine2(d2, coef2[0], coef2[1], act=1)
-        h3 = o.linear_fwd(h2, W3, b3)
-        z, inv = o.l2norm_fwd(h3)
-        w, winv = _last_layer_weight(v, g)
-        logits, mx, lse = _last_logits(o, z, w, stats)
-        ctx.save_for_backward(v, g, W1, W2, W3, xa, d1, coef1, gam1, h1, d2, coef2, gam2, h2, z, inv, w, winv)
-        ctx.meta = (n1, n2, st1.get("group"), bool(st1.get("eval")), g.requires_grad)
-        ctx.wparams = (W1p, W2p, W3p, v)
-        if mx is not None:
-            ctx.mark_non_differentiable(mx, lse)
-        return logits, mx, lse
-
-    @staticmethod
-    def _bn_gelu_bwd(o, dh, d, coef, gam, n, group, eval_bn):
-        """dh = dL/d GELU(BN(d)) -> (dL/dd, dgamma, dbeta)"""
-        du = o.col_affine2(d, coef[0], coef[1], x2=dh, act=2)     # through the GELU, at the rebuilt BN output
-        red = o.bn_bwd_local(o.col_sums2(du, d), coef)            # (sum du, sum du*xhat) of this rank = (d beta, d gamma)
-        dbet, dgam = red[0].clone(), red[1].clone()
-        if eval_bn:
-            abc = o.bn_bwd_coeffs(None, n, gam, coef)
-        else:
-            _allreduce_stats(red, group)
-            abc = o.bn_bwd_coeffs(red, n, gam, coef)
-        return o.col_affine2(du, abc[0], abc[2], d, abc[1]), dgam, dbet
-
-    @staticmethod
-    def backward(ctx, dlogits, _gmx=None, _glse=None):
-        o = ops_module()
-        v, g, W1, W2, W3, xa, d1, coef1, gam1, h1, d2, coef2, gam2, h2, z, inv, w, winv = ctx.saved_tensors
-        n1, n2, group, eval_bn, need_dg = ctx.meta
-        W1p, W2p, W3p, vp = ctx.wparams
-        dlogits = dlogits.contiguous()
-        dz = o.linear_dgrad(dlogits, w)
-        dw = o.linear_wgrad(dlogits, z)
-        sink = P.grad_out(vp)
-        dv, dg = o.weightnorm_bwd(dw, v, g, winv, need_dg, dv_out=sink)
-        if sink is not None:
-            dv = dv.detach()
-        dh3 = o.l2norm_bwd(dz, z, inv)
-        dW3, db3 = _wgrad(dh3, h2, W3p, want_bias=True)
-        dd2, dg2, dbe2 = DinoHeadBnFn._bn_gelu_bwd(o, o.linear_dgrad(dh3, W3), d2, coef2, gam2, n2, group, eval_bn)
-        dW2, db2 = _wgrad(dd2, h1, W2p, want_bias=True)
-        dd1, dg1, dbe1 = DinoHeadBnFn._bn_gelu_bwd(o, o.linear_dgrad(dd2, W2), d1, coef1, gam1, n1, group, eval_bn)
-        dW1, db1 = _wgrad(dd1, xa, W1p, want_bias=True)
-        dx = o.linear_dgrad(dd1, W1, out_f32=True)
-        return dx, None, None, None, dW1, db1, dg1, dbe1, dW2, db2, dg2, dbe2, dW3, db3, dv, dg
-
-
-class DinoHeadBnNFn(torch.autograd.Function):
-    """DINOHead(use_bn=True) with any number of layers (vision_transformer.py:391-402, nlayers != 3): (Linear -> BatchNorm1d -> GELU)
-    nlayers - 1 times, a Linear into the bottleneck, l2-normalise, the weight-normed last layer -- the passes of DinoHeadBnFn in a
-    loop.  params = (W_1, b_1, bn_1.weight, bn_1.bias, ..., W_L, b_L, weight_v, weight_g); bn_states: one dict per BatchNorm."""
+    """DINOHead(use_bn=True) with any number of layers (vision_transformer.py:391-402): (Linear -> BatchNorm1d -> GELU) nlayers - 1
+    times, a Linear into the bottleneck, l2-normalise, the weight-normed last layer.  params = (W_1, b_1, bn_1.weight, bn_1.bias, ...,
+    W_L, b_L, weight_v, weight_g); bn_states: one dict per BatchNorm.  Applied in every mode: the forward updates the running statistics
+    and num_batches_tracked of a training-mode BatchNorm"""
 
     @staticmethod
     def forward(ctx, x, bn_states, stats, *params):
         o = ops_module()
-        L = (len(params) - 2 + 2) // 4                      # hidden layers carry four tensors, the last Linear two
+        L = len(params) // 4                                # hidden layers carry four tensors, the last Linear and the last layer two each
         hid = [params[4 * i:4 * i + 4] for i in range(L - 1)]
-        Wl, bl = params[4 * (L - 1)], params[4 * (L - 1) + 1]
-        v, g = params[-2], params[-1]
+        Wl, bl, v, g = params[4 * (L - 1):]
         h = o.cast_to_act(x.contiguous())
-        saved, meta = [], []
+        hidden, ns = [], []
         for (Wp, b, gam, bet), st in zip(hid, bn_states):
             W = _weight(Wp)
             gam_, bet_ = gam.detach().contiguous(), bet.detach().contiguous()
             d = o.linear_fwd(h, W, b)
             coef, n = _head_bn_coef(o, d, st, gam_, bet_)
-            saved += [W, h, d, coef, gam_]
-            meta.append(n)
+            hidden += [W, h, d, coef, gam_]
+            ns.append(n)
             h = o.col_affine2(d, coef[0], coef[1], act=1)
         WL = _weight(Wl)
         hL = o.linear_fwd(h, WL, bl)
         z, inv = o.l2norm_fwd(hL)
         w, winv = _last_layer_weight(v, g)
         logits, mx, lse = _last_logits(o, z, w, stats)
-        ctx.L, ctx.ns = L, meta
+        ctx.ns = ns
         ctx.group, ctx.eval_bn = (bn_states[0].get("group"), bool(bn_states[0].get("eval"))) if bn_states else (None, False)
         ctx.need_dg = g.requires_grad
         ctx.wparams = tuple(hp[0] for hp in hid) + (Wl,)
         ctx.vparam = v
-        ctx.save_for_backward(v, g, z, inv, w, winv, WL, h, *saved)
+        _save_named(ctx, v=v, g=g, z=z, inv=inv, w=w, winv=winv, WL=WL, hlast=h, hidden=hidden)
         if mx is not None:
             ctx.mark_non_differentiable(mx, lse)
         return logits, mx, lse
@@ -1308,39 +1284,36 @@ class DinoHeadBnNFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dlogits, _gmx=None, _glse=None):
         o = ops_module()
-        L = ctx.L
-        t = ctx.saved_tensors
-        v, g, z, inv, w, winv, WL, hlast = t[:8]
-        per = [t[8 + 5 * i:8 + 5 * i + 5] for i in range(L - 1)]   # (W, input, pre-norm output, coef, gamma) of hidden layer i
+        s = _load_named(ctx)
+        L = len(ctx.wparams)
+        per = [s.hidden[5 * i:5 * i + 5] for i in range(L - 1)]   # (W, input, pre-norm output, coef, gamma) of hidden layer i
         dlogits = dlogits.contiguous()
-        dz = o.linear_dgrad(dlogits, w)
-        dw = o.linear_wgrad(dlogits, z)
+        dz = o.linear_dgrad(dlogits, s.w)
+        dw = o.linear_wgrad(dlogits, s.z)
         sink = P.grad_out(ctx.vparam)
-        dv, dg = o.weightnorm_bwd(dw, v, g, winv, ctx.need_dg, dv_out=sink)
-        if sink is not None:
-            dv = dv.detach()
-        dh = o.l2norm_bwd(dz, z, inv)
-        dWl, dbl = _wgrad(dh, hlast, ctx.wparams[L - 1], want_bias=True)
-        dh = o.linear_dgrad(dh, WL)
+        dv, dg = o.weightnorm_bwd(dw, s.v, s.g, s.winv, ctx.need_dg, dv_out=sink)
+        dh = o.l2norm_bwd(dz, s.z, s.inv)
+        dWl, dbl = _wgrad(dh, s.hlast, ctx.wparams[L - 1], want_bias=True)
+        dh = o.linear_dgrad(dh, s.WL)
         grads = [None] * (4 * (L - 1))
         for i in range(L - 2, -1, -1):
             W, hin, d, coef, gam = per[i]
-            dd, dgam, dbet = DinoHeadBnFn._bn_gelu_bwd(o, dh, d, coef, gam, ctx.ns[i], ctx.group, ctx.eval_bn)
+            dd, dgam, dbet = _bn_gelu_bwd(o, dh, d, coef, gam, ctx.ns[i], ctx.group, ctx.eval_bn)
             dW, db = _wgrad(dd, hin, ctx.wparams[i], want_bias=True)
             grads[4 * i:4 * i + 4] = [dW, db, dgam, dbet]
             dh = o.linear_dgrad(dd, W, out_f32=(i == 0))
-        return (dh, None, None) + tuple(grads) + (dWl, dbl, dv, dg)
+        return (dh, None, None) + tuple(grads) + (dWl, dbl, _alias(dv, sink), dg)
 
 
 def dino_head_bn_n(x, bn_states, hidden, last, v, g, stats=None):
     """hidden: [(W, b, bn.weight, bn.bias), ...]; last: (W, b) of the Linear into the bottleneck -> (logits, row_max, row_lse)"""
     flat = [p for h in hidden for p in h]
-    return DinoHeadBnNFn.apply(x, list(bn_states), stats, *flat, *last, v, g)
+    return DinoHeadBnFn.apply(x, list(bn_states), stats, *flat, *last, v, g)
 
 
 def dino_head_bn(x, st1, st2, prm, stats=None):
     """prm = (W1, b1, bn1.weight, bn1.bias, W2, b2, bn2.weight, bn2.bias, W3, b3, weight_v, weight_g) -> (logits, row_max, row_lse)"""
-    return DinoHeadBnFn.apply(x, st1, st2, stats, *prm)
+    return DinoHeadBnFn.apply(x, [st1, st2], stats, *prm)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -1589,40 +1562,45 @@ def _zero_table(w, nH, device):
     return t
 
 
+def _cvt_ffn_fwd(ctx, X, rowscale, rows_per_sample, prm):
+    """X fp32 [M, C] -> X + DropPath(FeedForward(LayerNorm(X))); keeps on ctx what _cvt_ffn_bwd reads"""
+    g2, b2, W1p, bf1, W2p, bf2 = prm
+    C, Hd = X.shape[1], W1p.shape[0]
+    W1, W2 = _weight(W1p, (Hd, C)), _weight(W2p, (C, Hd))
+    y, (mean, rstd, h, a1, a1g) = _mlp_fwd(ops_module(), X, (g2, b2, bf1, bf2), W1, W2, CVT_LN_EPS, rowscale, rows_per_sample, True, quick=True)
+    ctx.rowscale, ctx.rows_per_sample, ctx.params = rowscale, rows_per_sample, prm
+    ctx.save_for_backward(X, mean, rstd, g2, h, a1, a1g, W1, W2)
+    return y
+
+
+def _cvt_ffn_bwd(ctx, gy):
+    """gy fp32 [M, C] -> (gx, d norm.weight, d norm.bias, d fc1.weight, d fc1.bias, d fc2.weight, d fc2.bias)"""
+    o = ops_module()
+    X, mean, rstd, g2, h, a1, a1g, W1, W2 = ctx.saved_tensors
+    g2_p, b2_p, W1p, bf1_p, W2p, bf2_p = ctx.params
+    M, C = X.shape
+    Hd = W1.shape[0]
+    dyb = o.gather_cast(gy, M, rowscale=ctx.rowscale, rows_per_sample=ctx.rows_per_sample)
+    dh, dW1, dbf1, dW2, dbf2 = _mlp_bwd(o, dyb, h, a1, a1g, W1, W2, (W1p, bf1_p, W2p, bf2_p), quick=True, shapes2d=((Hd, C), (C, Hd)))
+    ln2 = _ln_sinks(g2_p, b2_p)
+    gx, dg2, db2 = o.layernorm_bwd(dh, X, mean, rstd, g2, g_in=gy, gb_out=ln2)
+    _side_join()
+    return gx, _alias(dg2, ln2), _alias(db2, ln2), dW1.view(Hd, C, 1, 1), dbf1, dW2.view(C, Hd, 1, 1), dbf2
+
+
 class CvtFfnFn(torch.autograd.Function):
-    """x + DropPath(FeedForward(LayerNorm(x)))  (cvt_v4_transformer.py:62-72): 1x1 conv -> QuickGELU -> 1x1 conv"""
+    """x + DropPath(FeedForward(LayerNorm(x)))  (cvt_v4_transformer.py:62-72): 1x1 conv -> QuickGELU -> 1x1 conv.  x fp32 [nB, L, C];
+    dp: None or the DropPath scale per sample [nB]"""
 
     @staticmethod
     def forward(ctx, x, dp, g2, b2, W1p, bf1, W2p, bf2):
-        o = ops_module()
         nB, L, C = x.shape
-        x = x.contiguous()
-        x2d = x.view(nB * L, C)
-        Hd = W1p.shape[0]
-        W1, W2 = _weight(W1p, (Hd, C)), _weight(W2p, (C, Hd))
-        h, _, mean, rstd = o.layernorm_fwd(x2d, g2, b2, CVT_LN_EPS)
-        a1g, a1 = o.linear_fwd(h, W1, bf1, gelu=True, want_preact=True, quick=True)
-        y = o.linear_fwd(a1g, W2, bf2, residual=x2d, rowscale=dp, rows_per_sample=L, out_f32=True)
-        ctx.dp = dp
-        ctx.save_for_backward(x, mean, rstd, g2, h, a1, a1g, W1, W2)
-        return y.view(nB, L, C)
+        return _cvt_ffn_fwd(ctx, x.contiguous().view(nB * L, C), dp, L, (g2, b2, W1p, bf1, W2p, bf2)).view(nB, L, C)
 
     @staticmethod
     def backward(ctx, gy):
-        o = ops_module()
-        x, mean, rstd, g2, h, a1, a1g, W1, W2 = ctx.saved_tensors
-        nB, L, C = x.shape
-        M = nB * L
-        Hd = W1.shape[0]
-        gy = gy.contiguous().view(M, C)
-        dyb = o.gather_cast(gy, M, rowscale=ctx.dp, rows_per_sample=L)
-        dW2, dbf2 = _side_run(lambda: o.linear_wgrad(dyb, a1g, want_bias=True), dyb, a1g)
-        da1 = o.linear_dgrad(dyb, W2, gelu_preact=a1, quick=True)
-        dW1, dbf1 = _side_run(lambda: o.linear_wgrad(da1, h, want_bias=True), da1, h)
-        dh = o.linear_dgrad(da1, W1)
-        gx, dg2, db2 = o.layernorm_bwd(dh, x.view(M, C), mean, rstd, g2, g_in=gy)
-        _side_join()
-        return gx.view(nB, L, C), None, dg2, db2, dW1.view(Hd, C, 1, 1), dbf1, dW2.view(C, Hd, 1, 1), dbf2
+        gx, *grads = _cvt_ffn_bwd(ctx, gy.contiguous().view(-1, gy.shape[-1]))
+        return (gx.view(gy.shape), None) + tuple(grads)
 
 
 # ---- ragged multi-crop CvT: every resolution group of a step through ONE set of LayerNorm / GEMM launches -----------------------------
@@ -1836,36 +1814,12 @@ class CvtFfnMultiFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, X, dp_rows, g2, b2, W1p, bf1, W2p, bf2):
-        o = ops_module()
-        X = X.contiguous()
-        M, C = X.shape
-        Hd = W1p.shape[0]
-        W1, W2 = _weight(W1p, (Hd, C)), _weight(W2p, (C, Hd))
-        h, _, mean, rstd = o.layernorm_fwd(X, g2, b2, CVT_LN_EPS)
-        a1g, a1 = o.linear_fwd(h, W1, bf1, gelu=True, want_preact=True, quick=True)
-        y = o.linear_fwd(a1g, W2, bf2, residual=X, rowscale=dp_rows, rows_per_sample=1, out_f32=True)
-        ctx.dp_rows = dp_rows
-        ctx.params = (g2, b2, W1p, bf1, W2p, bf2)
-        ctx.save_for_backward(X, mean, rstd, g2, h, a1, a1g, W1, W2)
-        return y
+        return _cvt_ffn_fwd(ctx, X.contiguous(), dp_rows, 1, (g2, b2, W1p, bf1, W2p, bf2))
 
     @staticmethod
     def backward(ctx, gy):
-        o = ops_module()
-        X, mean, rstd, g2, h, a1, a1g, W1, W2 = ctx.saved_tensors
-        g2_p, b2_p, W1p, bf1_p, W2p, bf2_p = ctx.params
-        M, C = X.shape
-        Hd = W1.shape[0]
-        gy = gy.contiguous()
-        dyb = o.gather_cast(gy, M, rowscale=ctx.dp_rows, rows_per_sample=1)
-        dW2, dbf2 = _side_run(lambda: _wgrad(dyb, a1g, W2p, (C, Hd), want_bias=True, bias_param=bf2_p), dyb, a1g)
-        da1 = o.linear_dgrad(dyb, W2, gelu_preact=a1, quick=True)
-        dW1, dbf1 = _side_run(lambda: _wgrad(da1, h, W1p, (Hd, C), want_bias=True, bias_param=bf1_p), da1, h)
-        dh = o.linear_dgrad(da1, W1)
-        ln2 = _ln_sinks(g2_p, b2_p)
-        gx, dg2, db2 = o.layernorm_bwd(dh, X, mean, rstd, g2, g_in=gy, gb_out=ln2)
-        _side_join()
-        return gx, None, _alias(dg2, ln2), _alias(db2, ln2), dW1.view(Hd, C, 1, 1), dbf1, dW2.view(C, Hd, 1, 1), dbf2
+        gx, *grads = _cvt_ffn_bwd(ctx, gy.contiguous())
+        return (gx, None) + tuple(grads)
 
 
 def cvt_block_multi(X, segs, nH, window, dp_rows, bn_state, attn_prm, ffn_prm, table_p=None, index=None, shift=False):
@@ -2137,8 +2091,19 @@ def vit_attention_bwd(o, dao, att, bqkv, nB, N, nH, scale, dqkv_out=None):
     return dqkv
 
 
+def _vit_mlp_fwd(o, x1, prm, W1, W2, rowscale, rows_per_sample, save):
+    """the MLP branch of a ViT block -> (x2, what the backward reads or None).  Inference pass (the EMA teacher, the eval consumers): the
+    branch in one kernel (deit_tiny / deit_small widths, whose fused kernels take the plain weight cast)"""
+    C = x1.shape[1]
+    if not save and C in (192, 384) and _mlp_fused_infer(W1, C):
+        g2, b2, bfc1, bfc2 = prm
+        return o.mlp_fused_fwd(x1, g2, b2, LN_EPS, W1, bfc1, W2, bfc2, rowscale=_per_row(rowscale, rows_per_sample)), None
+    return _mlp_fwd(o, x1, prm, W1, W2, LN_EPS, rowscale, rows_per_sample, save)
+
+
 def _vit_block_forward(x, nH, dp, prm, wts, save):
-    """Block.forward (vision_transformer.py:110-116) on x fp32 [nB, N, C]"""
+    """Block.forward (vision_transformer.py:110-116) on x fp32 [nB, N, C] -> (y, tensors for the backward by name or None, those of the
+    attention)"""
     o = ops_module()
     (g1, b1, bqkv, bproj, g2, b2, bfc1, bfc2) = prm
     (Wqkv, Wproj, W1, W2) = wts
@@ -2150,42 +2115,30 @@ def _vit_block_forward(x, nH, dp, prm, wts, save):
     qkv = o.linear_fwd(xw, Wqkv, bqkv)
     ao, att = vit_attention(o, qkv, bqkv, nB, N, nH, scale, save)
     x1 = o.linear_fwd(ao, Wproj, bproj, residual=x2d, rowscale=dp1, rows_per_sample=N, out_f32=True)
-    if not save and C in (192, 384) and _mlp_fused_infer(W1, C):
-        # inference pass (the EMA teacher, the eval consumers): the branch in one kernel (deit_tiny / deit_small widths, whose fused kernels
-        # take the plain weight cast)
-        x2 = o.mlp_fused_fwd(x1, g2, b2, LN_EPS, W1, bfc1, W2, bfc2, rowscale=None if dp2 is None else dp2.repeat_interleave(N))
-        return x2.view(nB, N, C), None, att
-    h, _, mean2, rstd2 = o.layernorm_fwd(x1, g2, b2, LN_EPS)
-    if save:
-        a1g, a1 = o.linear_fwd(h, W1, bfc1, gelu=True, want_preact=True)
-    else:
-        a1g, a1 = o.linear_fwd(h, W1, bfc1, gelu=True), None
-    x2 = o.linear_fwd(a1g, W2, bfc2, residual=x1, rowscale=dp2, rows_per_sample=N, out_f32=True)
-    saved = (mean1, rstd1, xw, ao, x1, mean2, rstd2, h, a1, a1g) if save else None
+    x2, mlp_saved = _vit_mlp_fwd(o, x1, (g2, b2, bfc1, bfc2), W1, W2, dp2, N, save)
+    saved = dict(mean1=mean1, rstd1=rstd1, xw=xw, ao=ao, x1=x1, **dict(zip(_MLP_SAVED, mlp_saved))) if save else None
     return x2.view(nB, N, C), saved, att
 
 
 class VitBlockFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, nH, dp, g1, b1, Wqkv_p, bqkv, Wproj_p, bproj, g2, b2, W1_p, bfc1, W2_p, bfc2):
-        wts = (_weight(Wqkv_p), _weight(Wproj_p), _weight(W1_p), _weight(W2_p))
+        Wqkv, Wproj, W1, W2 = wts = (_weight(Wqkv_p), _weight(Wproj_p), _weight(W1_p), _weight(W2_p))
         x = x.contiguous()
         y, saved, att = _vit_block_forward(x, nH, dp, (g1, b1, bqkv, bproj, g2, b2, bfc1, bfc2), wts, True)
         ctx.nH, ctx.dp = nH, dp
         ctx.wparams = (Wqkv_p, Wproj_p, W1_p, W2_p)
         ctx.bparams = (bqkv, bproj, bfc1, bfc2)
         ctx.nparams = (g1, b1, g2, b2)
-        ctx.natt = len(att)
-        ctx.save_for_backward(x, g1, g2, bqkv, *wts, *saved, *att)
+        _save_named(ctx, x=x, g1=g1, g2=g2, bqkv=bqkv, Wqkv=Wqkv, Wproj=Wproj, W1=W1, W2=W2, att=att, **saved)
         return y
 
     @staticmethod
     def backward(ctx, gy):
         o = ops_module()
         nH, dp = ctx.nH, ctx.dp
-        t = ctx.saved_tensors
-        x, g1, g2, bqkv, Wqkv, Wproj, W1, W2, mean1, rstd1, xw, ao, x1, mean2, rstd2, h, a1, a1g = t[:18]
-        att = tuple(t[18:18 + ctx.natt])
+        s = _load_named(ctx)
+        x, xw, ao = s.x, s.xw, s.ao
         nB, N, C = x.shape
         M = nB * N
         scale = (C // nH) ** -0.5
@@ -2195,18 +2148,16 @@ class VitBlockFn(torch.autograd.Function):
         bqkv_p, bproj_p, bfc1_p, bfc2_p = ctx.bparams
         g1_p, b1_p, g2_p, b2_p = ctx.nparams
         dyb = o.gather_cast(gy, M, rowscale=dp2, rows_per_sample=N)
-        dW2, dbfc2 = _wgrad(dyb, a1g, W2_p, want_bias=True, bias_param=bfc2_p)
-        da1 = o.linear_dgrad(dyb, W2, gelu_preact=a1)
-        dW1, dbfc1 = _wgrad(da1, h, W1_p, want_bias=True, bias_param=bfc1_p)
-        dh = o.linear_dgrad(da1, W1)
+        dh, dW1, dbfc1, dW2, dbfc2 = _mlp_bwd(o, dyb, s.h, s.a1, s.a1g, s.W1, s.W2, (W1_p, bfc1_p, W2_p, bfc2_p))
         sink1, sink2 = _ln_sinks(g1_p, b1_p), _ln_sinks(g2_p, b2_p)
-        gx1, dyw, dg2, db2 = o.layernorm_bwd_cast(dh, x1, mean2, rstd2, g2, g_in=gy, rowscale=dp1, rows_per_sample=N, gb_out=sink2)
-        dWproj, dbproj = _wgrad(dyw, ao, Wproj_p, want_bias=True, bias_param=bproj_p)
-        dao = o.linear_dgrad(dyw, Wproj)
-        dqkv = vit_attention_bwd(o, dao, att, bqkv, nB, N, nH, scale)
-        dWqkv, dbqkv = _wgrad(dqkv, xw, Wqkv_p, want_bias=True, bias_param=bqkv_p)
-        dxw = o.linear_dgrad(dqkv, Wqkv)
-        gx, dg1, db1 = o.layernorm_bwd(dxw, x.view(M, C), mean1, rstd1, g1, g_in=gx1, gb_out=sink1)
+        gx1, dyw, dg2, db2 = o.layernorm_bwd_cast(dh, s.x1, s.mean2, s.rstd2, s.g2, g_in=gy, rowscale=dp1, rows_per_sample=N, gb_out=sink2)
+        dWproj, dbproj = _side_run(lambda: _wgrad(dyw, ao, Wproj_p, want_bias=True, bias_param=bproj_p), dyw, ao)
+        dao = o.linear_dgrad(dyw, s.Wproj)
+        dqkv = vit_attention_bwd(o, dao, s.att, s.bqkv, nB, N, nH, scale)
+        dWqkv, dbqkv = _side_run(lambda: _wgrad(dqkv, xw, Wqkv_p, want_bias=True, bias_param=bqkv_p), dqkv, xw)
+        dxw = o.linear_dgrad(dqkv, s.Wqkv)
+        gx, dg1, db1 = o.layernorm_bwd(dxw, x.view(M, C), s.mean1, s.rstd1, s.g1, g_in=gx1, gb_out=sink1)
+        _side_join()
         return (gx.view(nB, N, C), None, None, _alias(dg1, sink1), _alias(db1, sink1), dWqkv, dbqkv, dWproj, dbproj,
                 _alias(dg2, sink2), _alias(db2, sink2), dW1, dbfc1, dW2, dbfc2)
 
@@ -2343,13 +2294,8 @@ def _vil_block_forward(x, nH, dp, chunk, prm, wts, save):
         ao, att = o.vit_attn_fwd(qkv, nB, N, nH, scale, chunk=_chunk3(chunk))
         att = att if save else ()
     x1 = o.linear_fwd(ao, Wproj, bproj, residual=x2d, rowscale=dp1, rows_per_sample=N, out_f32=True)
-    h, _, mean2, rstd2 = o.layernorm_fwd(x1, g2, b2, LN_EPS)
-    if save:
-        a1g, a1 = o.linear_fwd(h, W1, bfc1, gelu=True, want_preact=True)
-    else:
-        a1g, a1 = o.linear_fwd(h, W1, bfc1, gelu=True), None
-    x2 = o.linear_fwd(a1g, W2, bfc2, residual=x1, rowscale=dp2, rows_per_sample=N, out_f32=True)
-    saved = (mean1, rstd1, xw, ao, x1, mean2, rstd2, h, a1, a1g, bqkv) if save else None
+    x2, mlp_saved = _mlp_fwd(o, x1, (g2, b2, bfc1, bfc2), W1, W2, LN_EPS, dp2, N, save)
+    saved = dict(mean1=mean1, rstd1=rstd1, xw=xw, ao=ao, x1=x1, bqkv=bqkv, **dict(zip(_MLP_SAVED, mlp_saved))) if save else None
     return x2.view(nB, N, C), saved, att
 
 
@@ -2357,32 +2303,22 @@ class VilBlockFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, nH, dp, chunk, g1, b1, Wq_p, bq, Wkv_p, bkv, Wproj_p, bproj, g2, b2, W1_p, bfc1, W2_p, bfc2):
         split = Wkv_p is not None
-        wts = (_weight(Wq_p), _weight(Wkv_p) if split else None, _weight(Wproj_p), _weight(W1_p), _weight(W2_p))
+        Wq, Wkv, Wproj, W1, W2 = wts = (_weight(Wq_p), _weight(Wkv_p) if split else None, _weight(Wproj_p), _weight(W1_p), _weight(W2_p))
         x = x.contiguous()
         y, saved, att = _vil_block_forward(x, nH, dp, chunk, (g1, b1, bq, bkv, bproj, g2, b2, bfc1, bfc2), wts, True)
         ctx.nH, ctx.dp, ctx.split, ctx.chunk = nH, dp, split, chunk
         ctx.wparams = (Wq_p, Wkv_p, Wproj_p, W1_p, W2_p)
         ctx.bparams = (bq, bkv, bproj, bfc1, bfc2)
         ctx.nparams = (g1, b1, g2, b2)
-        ctx.natt = len(att)
-        wsave = [w for w in wts if w is not None]
-        ctx.save_for_backward(x, g1, g2, *wsave, *saved, *att)
+        _save_named(ctx, x=x, g1=g1, g2=g2, Wq=Wq, Wkv=Wkv, Wproj=Wproj, W1=W1, W2=W2, att=att, **saved)
         return y
 
     @staticmethod
     def backward(ctx, gy):
         o = ops_module()
         nH, dp, split = ctx.nH, ctx.dp, ctx.split
-        t = list(ctx.saved_tensors)
-        x, g1, g2 = t[:3]
-        nw = 5 if split else 4
-        ws = t[3:3 + nw]
-        if split:
-            Wq, Wkv, Wproj, W1, W2 = ws
-        else:
-            (Wq, Wproj, W1, W2), Wkv = ws, None
-        mean1, rstd1, xw, ao, x1, mean2, rstd2, h, a1, a1g, bqkv = t[3 + nw:14 + nw]
-        att = tuple(t[14 + nw:14 + nw + ctx.natt])
+        s = _load_named(ctx)
+        x, xw, ao, att = s.x, s.xw, s.ao, s.att
         nB, N, C = x.shape
         M = nB * N
         scale = (C // nH) ** -0.5
@@ -2392,30 +2328,27 @@ class VilBlockFn(torch.autograd.Function):
         bq_p, bkv_p, bproj_p, bfc1_p, bfc2_p = ctx.bparams
         g1_p, b1_p, g2_p, b2_p = ctx.nparams
         dyb = o.gather_cast(gy, M, rowscale=dp2, rows_per_sample=N)
-        dW2, dbfc2 = _side_run(lambda: _wgrad(dyb, a1g, W2_p, want_bias=True, bias_param=bfc2_p), dyb, a1g)
-        da1 = o.linear_dgrad(dyb, W2, gelu_preact=a1)
-        dW1, dbfc1 = _side_run(lambda: _wgrad(da1, h, W1_p, want_bias=True, bias_param=bfc1_p), da1, h)
-        dh = o.linear_dgrad(da1, W1)
+        dh, dW1, dbfc1, dW2, dbfc2 = _mlp_bwd(o, dyb, s.h, s.a1, s.a1g, s.W1, s.W2, (W1_p, bfc1_p, W2_p, bfc2_p))
         sink1, sink2 = _ln_sinks(g1_p, b1_p), _ln_sinks(g2_p, b2_p)
-        gx1, dyw, dg2, db2 = o.layernorm_bwd_cast(dh, x1, mean2, rstd2, g2, g_in=gy, rowscale=dp1, rows_per_sample=N, gb_out=sink2)
+        gx1, dyw, dg2, db2 = o.layernorm_bwd_cast(dh, s.x1, s.mean2, s.rstd2, s.g2, g_in=gy, rowscale=dp1, rows_per_sample=N, gb_out=sink2)
         dWproj, dbproj = _side_run(lambda: _wgrad(dyw, ao, Wproj_p, want_bias=True, bias_param=bproj_p), dyw, ao)
-        dao = o.linear_dgrad(dyw, Wproj)
+        dao = o.linear_dgrad(dyw, s.Wproj)
         if ctx.chunk is not None and _chunk_fused(o, ctx.chunk, ao.dtype, C // nH):
             dqkv = o.sliding_chunk_attn_bwd(dao, (att[0], ao, att[1]), nB, N, nH, scale, ctx.chunk[:3])
         elif ctx.chunk is not None:
             dqkv = o.vit_attn_bwd(dao, att, nB, N, nH, scale, chunk=_chunk3(ctx.chunk))
         else:
-            dqkv = vit_attention_bwd(o, dao, att, bqkv, nB, N, nH, scale)
+            dqkv = vit_attention_bwd(o, dao, att, s.bqkv, nB, N, nH, scale)
         if split:
             dq, dkv = dqkv[:, :C].contiguous(), dqkv[:, C:].contiguous()
             dWq, dbq = _side_run(lambda: _wgrad(dq, xw, Wq_p, want_bias=True, bias_param=bq_p), dq, xw)
             dWkv, dbkv = _side_run(lambda: _wgrad(dkv, xw, Wkv_p, want_bias=True, bias_param=bkv_p), dkv, xw)
-            dxw = o.linear_dgrad(dqkv, torch.cat((Wq, Wkv), 0))  # dq Wq + dkv Wkv as one product over the stacked (tiny) weights
+            dxw = o.linear_dgrad(dqkv, torch.cat((s.Wq, s.Wkv), 0))  # dq Wq + dkv Wkv as one product over the stacked (tiny) weights
         else:
             dWq, dbq = _side_run(lambda: _wgrad(dqkv, xw, Wq_p, want_bias=True, bias_param=bq_p), dqkv, xw)
             dWkv, dbkv = None, None
-            dxw = o.linear_dgrad(dqkv, Wq)
-        gx, dg1, db1 = o.layernorm_bwd(dxw, x.view(M, C), mean1, rstd1, g1, g_in=gx1, gb_out=sink1)
+            dxw = o.linear_dgrad(dqkv, s.Wq)
+        gx, dg1, db1 = o.layernorm_bwd(dxw, x.view(M, C), s.mean1, s.rstd1, s.g1, g_in=gx1, gb_out=sink1)
         _side_join()
         return (gx.view(nB, N, C), None, None, None, _alias(dg1, sink1), _alias(db1, sink1), dWq, dbq, dWkv, dbkv, dWproj, dbproj,
                 _alias(dg2, sink2), _alias(db2, sink2), dW1, dbfc1, dW2, dbfc2)
@@ -2436,7 +2369,8 @@ def vil_block(x, nH, dp, chunk, prm_list):
 # row range.  Compared with one pass per group (vision_transformer.py:186-233): half the launches, ONE gradient contribution per
 # parameter (no accumulation adds; the data-parallel reducer can overlap), half the split-K partial traffic of the weight gradients.
 def _vit_block_forward_multi(X, segs, nH, dp_rows, prm, wts, save):
-    """X fp32 [M, C]; segs: tuple of (row0, nB, N); dp_rows: None or (per-row DropPath scale of the attention branch [M], MLP branch [M])"""
+    """X fp32 [M, C]; segs: tuple of (row0, nB, N); dp_rows: None or (per-row DropPath scale of the attention branch [M], MLP branch [M])
+    -> (y, tensors for the backward by name or None, those of every group's attention)"""
     o = ops_module()
     (g1, b1, bqkv, bproj, g2, b2, bfc1, bfc2) = prm
     (Wqkv, Wproj, W1, W2) = wts
@@ -2452,42 +2386,31 @@ def _vit_block_forward_multi(X, segs, nH, dp_rows, prm, wts, save):
         _, att = vit_attention(o, qkv[r0:r1], bqkv, nB, N, nH, scale, save, out=ao[r0:r1])
         atts.append(att)
     x1 = o.linear_fwd(ao, Wproj, bproj, residual=X, rowscale=dp1, rows_per_sample=1, out_f32=True)
-    if not save and C in (192, 384) and _mlp_fused_infer(W1, C):
-        return o.mlp_fused_fwd(x1, g2, b2, LN_EPS, W1, bfc1, W2, bfc2, rowscale=dp2), None, atts  # (inference pass: see _vit_block_forward)
-    h, _, mean2, rstd2 = o.layernorm_fwd(x1, g2, b2, LN_EPS)
-    if save:
-        a1g, a1 = o.linear_fwd(h, W1, bfc1, gelu=True, want_preact=True)
-    else:
-        a1g, a1 = o.linear_fwd(h, W1, bfc1, gelu=True), None
-    x2 = o.linear_fwd(a1g, W2, bfc2, residual=x1, rowscale=dp2, rows_per_sample=1, out_f32=True)
-    saved = (mean1, rstd1, xw, ao, x1, mean2, rstd2, h, a1, a1g) if save else None
+    x2, mlp_saved = _vit_mlp_fwd(o, x1, (g2, b2, bfc1, bfc2), W1, W2, dp2, 1, save)
+    saved = dict(mean1=mean1, rstd1=rstd1, xw=xw, ao=ao, x1=x1, **dict(zip(_MLP_SAVED, mlp_saved))) if save else None
     return x2, saved, atts
 
 
 class VitBlockMultiFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, X, segs, nH, dp_rows, g1, b1, Wqkv_p, bqkv, Wproj_p, bproj, g2, b2, W1_p, bfc1, W2_p, bfc2):
-        wts = (_weight(Wqkv_p), _weight(Wproj_p), _weight(W1_p), _weight(W2_p))
+        Wqkv, Wproj, W1, W2 = wts = (_weight(Wqkv_p), _weight(Wproj_p), _weight(W1_p), _weight(W2_p))
         X = X.contiguous()
         y, saved, atts = _vit_block_forward_multi(X, segs, nH, dp_rows, (g1, b1, bqkv, bproj, g2, b2, bfc1, bfc2), wts, True)
         ctx.segs, ctx.nH, ctx.dp_rows = segs, nH, dp_rows
         ctx.wparams = (Wqkv_p, Wproj_p, W1_p, W2_p)
         ctx.bparams = (bqkv, bproj, bfc1, bfc2)
         ctx.nparams = (g1, b1, g2, b2)
-        ctx.natt = [len(a) for a in atts]
-        ctx.save_for_backward(X, g1, g2, bqkv, *wts, *saved, *[t for a in atts for t in a])
+        _save_named(ctx, X=X, g1=g1, g2=g2, bqkv=bqkv, Wqkv=Wqkv, Wproj=Wproj, W1=W1, W2=W2, **saved, **{"att%d" % i: a for i, a in enumerate(atts)})
         return y
 
     @staticmethod
     def backward(ctx, gy):
         o = ops_module()
         segs, nH, dp_rows = ctx.segs, ctx.nH, ctx.dp_rows
-        t = ctx.saved_tensors
-        X, g1, g2, bqkv, Wqkv, Wproj, W1, W2, mean1, rstd1, xw, ao, x1, mean2, rstd2, h, a1, a1g = t[:18]
-        flat, atts, at = t[18:], [], 0
-        for n in ctx.natt:
-            atts.append(tuple(flat[at:at + n]))
-            at += n
+        s = _load_named(ctx)
+        X, xw, ao = s.X, s.xw, s.ao
+        atts = [getattr(s, "att%d" % i) for i in range(len(segs))]
         M, C = X.shape
         scale = (C // nH) ** -0.5
         dp1, dp2 = (None, None) if dp_rows is None else dp_rows
@@ -2496,21 +2419,18 @@ class VitBlockMultiFn(torch.autograd.Function):
         bqkv_p, bproj_p, bfc1_p, bfc2_p = ctx.bparams
         g1_p, b1_p, g2_p, b2_p = ctx.nparams
         dyb = o.gather_cast(gy, M, rowscale=dp2, rows_per_sample=1)
-        dW2, dbfc2 = _side_run(lambda: _wgrad(dyb, a1g, W2_p, want_bias=True, bias_param=bfc2_p), dyb, a1g)
-        da1 = o.linear_dgrad(dyb, W2, gelu_preact=a1)
-        dW1, dbfc1 = _side_run(lambda: _wgrad(da1, h, W1_p, want_bias=True, bias_param=bfc1_p), da1, h)
-        dh = o.linear_dgrad(da1, W1)
+        dh, dW1, dbfc1, dW2, dbfc2 = _mlp_bwd(o, dyb, s.h, s.a1, s.a1g, s.W1, s.W2, (W1_p, bfc1_p, W2_p, bfc2_p))
         sink1, sink2 = _ln_sinks(g1_p, b1_p), _ln_sinks(g2_p, b2_p)
-        gx1, dyw, dg2, db2 = o.layernorm_bwd_cast(dh, x1, mean2, rstd2, g2, g_in=gy, rowscale=dp1, rows_per_sample=1, gb_out=sink2)
+        gx1, dyw, dg2, db2 = o.layernorm_bwd_cast(dh, s.x1, s.mean2, s.rstd2, s.g2, g_in=gy, rowscale=dp1, rows_per_sample=1, gb_out=sink2)
         dWproj, dbproj = _side_run(lambda: _wgrad(dyw, ao, Wproj_p, want_bias=True, bias_param=bproj_p), dyw, ao)
-        dao = o.linear_dgrad(dyw, Wproj)
+        dao = o.linear_dgrad(dyw, s.Wproj)
         dqkv = torch.empty((M, 3 * C), dtype=dao.dtype, device=dao.device)
         for (r0, nB, N), att in zip(segs, atts):
             r1 = r0 + nB * N
-            vit_attention_bwd(o, dao[r0:r1], att, bqkv, nB, N, nH, scale, dqkv_out=dqkv[r0:r1])
+            vit_attention_bwd(o, dao[r0:r1], att, s.bqkv, nB, N, nH, scale, dqkv_out=dqkv[r0:r1])
         dWqkv, dbqkv = _side_run(lambda: _wgrad(dqkv, xw, Wqkv_p, want_bias=True, bias_param=bqkv_p), dqkv, xw)
-        dxw = o.linear_dgrad(dqkv, Wqkv)
-        gx, dg1, db1 = o.layernorm_bwd(dxw, X, mean1, rstd1, g1, g_in=gx1, gb_out=sink1)
+        dxw = o.linear_dgrad(dqkv, s.Wqkv)
+        gx, dg1, db1 = o.layernorm_bwd(dxw, X, s.mean1, s.rstd1, s.g1, g_in=gx1, gb_out=sink1)
         _side_join()
         return (gx, None, None, None, _alias(dg1, sink1), _alias(db1, sink1), dWqkv, dbqkv, dWproj, dbproj,
                 _alias(dg2, sink2), _alias(db2, sink2), dW1, dbfc1, dW2, dbfc2)

@@ -64,24 +64,15 @@ class DINOHead(nn.Module):
     def forward(self, x):
         lead = x.shape[:-1]
         x2 = x.reshape(-1, x.shape[-1])
-        if self.use_bn and self.nlayers not in (1, 3):
+        if self.use_bn and self.nlayers > 1:
             mods = list(self.mlp)
             hidden = [(mods[i].weight, mods[i].bias, mods[i + 1].weight, mods[i + 1].bias) for i in range(0, len(mods) - 1, 3)]
             return self._finish(Fn.dino_head_bn_n(x2, [self._bn_state(mods[i + 1]) for i in range(0, len(mods) - 1, 3)], hidden,
                                                   (mods[-1].weight, mods[-1].bias), self.last_layer.weight_v, self.last_layer.weight_g,
                                                   self._stats_request()), lead)
-        if self.use_bn and self.nlayers == 3:
-            m = self.mlp
-            prm = [m[0].weight, m[0].bias, m[1].weight, m[1].bias, m[3].weight, m[3].bias, m[4].weight, m[4].bias, m[6].weight, m[6].bias,
-                   self.last_layer.weight_v, self.last_layer.weight_g]
-            return self._finish(Fn.dino_head_bn(x2, self._bn_state(m[1]), self._bn_state(m[4]), prm, self._stats_request()), lead)
-        if self.nlayers != 3:
-            lins = [self.mlp] if isinstance(self.mlp, nn.Linear) else [m for m in self.mlp if isinstance(m, nn.Linear)]
-            return self._finish(Fn.dino_head_n(x2, [(m.weight, m.bias) for m in lins], self.last_layer.weight_v, self.last_layer.weight_g,
-                                               self._stats_request()), lead)
-        prm = [self.mlp[0].weight, self.mlp[0].bias, self.mlp[2].weight, self.mlp[2].bias, self.mlp[4].weight, self.mlp[4].bias,
-               self.last_layer.weight_v, self.last_layer.weight_g]
-        return self._finish(Fn.dino_head(x2, prm, self._stats_request()), lead)
+        lins = [self.mlp] if isinstance(self.mlp, nn.Linear) else [m for m in self.mlp if isinstance(m, nn.Linear)]
+        return self._finish(Fn.dino_head_n(x2, [(m.weight, m.bias) for m in lins], self.last_layer.weight_v, self.last_layer.weight_g,
+                                           self._stats_request()), lead)
 
     def _stats_request(self):
         if self.logit_stats is None:

@@ -320,7 +320,7 @@ def _syncbn_worker(rank, world, port, out):
 
 def _syncbn_stem_worker(rank, world, port, out):
     """the residual stem's Conv 3x3 -> BatchNorm -> ReLU unit (functional.ConvBnReluFn, RES_STEM) and the N-layer BatchNorm head
-    (functional.DinoHeadBnNFn): statistics and backward reductions synchronised over two ranks == one process on the whole batch"""
+    (functional.DinoHeadBnFn): statistics and backward reductions synchronised over two ranks == one process on the whole batch"""
     _init(rank, world, port)
     import esvit_amd.functional as Fn
     import esvit_amd.params as P

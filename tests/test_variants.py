@@ -570,7 +570,7 @@ def _check_head_nlayers(dev, tol):
 
 
 def _check_head_bn_nlayers(dev, tol, zero_floor=1e-2):
-    """DINOHead(use_bn=True) with 1, 2 and 4 layers (functional.DinoHeadBnNFn) vs the reference's own module in train mode"""
+    """DINOHead(use_bn=True) with 1, 2 and 4 layers (functional.DinoHeadBnFn) vs the reference's own module in train mode"""
     import esvit_amd
     g = torch.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "head_bn_nlayers.pt"), weights_only=False)
     c = GU.HEAD_NLAYERS
@@ -624,7 +624,7 @@ def test_head_bn_nlayers_gpu(prec, lib_built):
 
 
 def test_head_nlayers_host_logic_cpu(monkeypatch, lib_built):
-    """DINOHead with 1, 2 and 4 Linear layers (functional.DinoHeadNFn) vs the reference's own module (tests/golden/head_nlayers.pt)"""
+    """DINOHead with 1, 2 and 4 Linear layers (functional.DinoHeadFn) vs the reference's own module (tests/golden/head_nlayers.pt)"""
     import esvit_amd
     import esvit_amd.functional as Fn
     import esvit_amd.params as P
