@@ -678,7 +678,22 @@ int esvit_center_ema(float* center, const float* colsum, float momentum, float d
  * partials j, j + 256, ... in chunk order, then the same butterfly and wave sum.  A chain of at most 16 + 6 + 4 additions in
  * the chunk and min(chunks - 1, ceil(chunks / 256) + 9) in the fold (absent partials enter as exact zeros), whatever the grid's
  * schedule: within the sequential bound (32 + chunks) * 2^-24 relative to the sum of the absolute terms.  A tensor without the
- * has-gradient bit gets 0.
+ * has-gradient bit gets 0.  The atomic form adds the same chunk partials in whatever order they arrive and meets the same bound.
+ * Element contract (u = 2^-24; tests/update_ref.py counts the roundings behind every K, tests/test_update_gpu.py holds the kernels
+ * to it): every output is within K u (sum of the absolute values of the relation's terms) of the relation evaluated exactly from the
+ * launch's fp32 inputs, its fp32 scalars and the statistics the launch read, the later relations from the earlier outputs as stored:
+ *   AdamW  m' = m + (1 - b1)(c g - m)  K = 7;   v' = b2 v + (1 - b2)(c g)^2  K = 12;
+ *          p' = (1 - lr wd) p - (lr / bc1) m' / (sqrt(v') / sqrt(bc2) + eps)  K = 8
+ *   SGD    mu' = momentum mu + (c g + wd p)  K = 6;    LARS  mu' = momentum mu + q (c g + wd p)  K = 16;    both  p' = p - lr mu'  K = 2
+ *   EMA    t' = ema_m t + (1 - ema_m) p'  K = 2;    bf16 copies: round-to-nearest-even of the stored p' and t', exactly
+ * with c = min(1, clip / (sqrt(sum g^2) + 1e-6)) (1 when clip == 0) and q = eta sqrt(sum p^2) / sqrt(c^2 sum g^2 + 2 c wd sum g p +
+ * wd^2 sum p^2), 1 for group 1 and where either root is 0, both evaluated exactly from the statistics.  Against the exact sums the
+ * statistics' bound B = (32 + chunks) u carries over: c within about B / 2 relative, q within (B (1 + cond) / 2 + 8 u) relative where
+ * cond = (c^2 sum g^2 + 2 c wd sum|g p| + wd^2 sum p^2) / |c g + wd p|^2 >= 1.  That is the limit of taking |c g + wd p| from three
+ * statistics instead of from the tensor, as the reference does: it cancels when c g ~ -wd p (cond large), and K = 16 of the LARS buffer
+ * is counted for a radicand that does not (cond near 1, which is what gradients uncorrelated with their weights give).
+ * A tensor without the has-gradient bit keeps p; its teacher and copies are still refreshed.  lr == 0 keeps p bit for bit while the
+ * moments move, ema_m == 1 keeps the teacher, ema_m == 0 makes it p'.  g is never written, and nothing is written through a zero slot.
  * Non-finite guard: if ANY statistic is NaN / inf (a non-finite loss poisons every gradient) the update launch is a no-op --
  * student, moments, teacher and weight copies keep their values (the reference exits before its update, main_esvit.py:546-551);
  * `skipped` (device int32, may be NULL) is then incremented by one, so that a host that looks at the loss only now and then can still
