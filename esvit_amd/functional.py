@@ -14,13 +14,15 @@ Stages (reference lines):
   DinoHeadBnFn     vision_transformer.py:391-402, 414-418 (use_bn), any number of BatchNorm layers
   ConvEmbedFn, CvtAttnFn, CvtFfnFn   cvt_v4_transformer.py:349-382, 108-220 (+75-105), 62-72  (BASELINE config 5)
   ConvEmbedMultiFn, CvtAttnMultiFn, CvtFfnMultiFn   the same over the token rows of several resolution groups (cvt_v4_transformer.py:625-628)
-  VitPatchEmbedFn, VitBlockFn, VitBlockMultiFn   vision_transformer.py:121-139, 96-116, 186-233
-  VilBlockFn       vision_longformer.py:36-118, layers/longformer2d.py
+  VitPatchEmbedFn  vision_transformer.py:121-139
+  VitBodyFn        one block body on token rows behind vit_block (vision_transformer.py:96-116), vit_block_multi (186-233: the rows of
+                   several resolution groups) and vil_block (vision_longformer.py:36-118, layers/longformer2d.py)
 
 Shared by the block families: the unfused MLP branch (_mlp_fwd / _mlp_bwd: LayerNorm -> fc1 + GELU -> fc2 + residual, called by the Swin,
 ViT and Vision Longformer blocks and CvT's feed-forward), Swin's choice between the fused, the wide and the unfused MLP kernels
 (_swin_mlp_fwd) and the fused backwards (_mlp_branch_bwd, _attn_branch_bwd).  A forward names the route it took (ctx.mlp_route,
-ctx.attn_bwd_fused) and saves its tensors by name (_save_named); a backward reads both back and infers nothing from what was saved.
+ctx.attn_bwd_fused, the attention route of every segment of a ViT-family block: vit_attention's _att_saved) and saves its tensors by
+name (_save_named); a backward reads both back and infers nothing from what was saved.
 The weight gradients of the blocks and of DinoHeadFn are leaves launched through _side_run into their bucket slots (_wgrad, _ln_sinks),
 and such a node joins (_side_join) before it returns.
 """
@@ -2007,7 +2009,6 @@ _VIT_WIN = {}
 VIT_LONG_ATTENTION = os.environ.get("ESVIT_VIT_LONG_ATTN", "gemm")
 if VIT_LONG_ATTENTION not in ("gemm", "flash"):
     raise ValueError("ESVIT_VIT_LONG_ATTN: gemm or flash, not %r" % VIT_LONG_ATTENTION)
-_FLASH_TAGS = {}
 
 
 def _vit_window(N, nH, device):
@@ -2040,145 +2041,238 @@ def _vit_flash_route(o, N, hd, dtype):
     return sup is not None and bool(sup(dtype, hd))
 
 
-def _flash_tag(device):
-    """an empty tensor that pads the flash route's saved tuple to five entries: (q | k | v, P) has two, the windowed routes three or four"""
-    t = _FLASH_TAGS.get(str(device))
-    if t is None:
-        t = _FLASH_TAGS[str(device)] = torch.empty(0, dtype=torch.float32, device=device)
-    return t
+def _chunk_fused(o, chunk, dtype, hd):
+    """does this sliding-chunk stage take the fused kernels (ops.sliding_chunk_attn_fwd)?  The model asks for them with a fourth tuple
+    entry, the chunk side (MsViT._stage under CHUNK_ATTENTION = "fused"); an ops module without the entry (the CPU restatement,
+    oracle/ops_ref.py) or an unsupported shape (fp32 parity mode, other head dims) keeps the dense route."""
+    if not isinstance(chunk, tuple) or len(chunk) < 4:
+        return False
+    sup = getattr(o, "sliding_chunk_attn_supported", None)
+    return sup is not None and bool(sup(dtype, hd, chunk[3], chunk[1]))
 
 
-def vit_attention(o, qkv, bqkv, nB, N, nH, scale, save, out=None):
-    """Attention.forward between the projections (vision_transformer.py:76-83) -> (out, tensors for vit_attention_bwd).  A crop is ONE
-    window of the fused MFMA kernels: the 37 tokens of a 96^2 crop in the 64-slot kernels of window_attn.hip, the 197 tokens of a
-    224^2 crop in the 224-slot flash-style kernels of window_attn_big.hip (head_dim 64 in bf16) -- no score matrix in HBM.  What
-    does not fit (fp32 parity mode at head_dim 64, longer sequences) takes the batched-GEMM route of ops.vit_attn_fwd, or, for longer
-    sequences under VIT_LONG_ATTENTION = "flash", the any-length kernels of flash_attn.hip."""
+def _chunk3(chunk):
+    return chunk[:3] if isinstance(chunk, tuple) else chunk
+
+
+# the routes of the attention between the projections and the tensors each keeps for its backward, by name.  "gemm" and "chunk_gemm"
+# keep what ops.vit_attn_fwd returned (`att`) and hand it back whole
+_ATT_KEPT = {"window": ("qkv", "ao", "frag", "lse"), "flash": ("qkv", "ao", "lse"), "gemm": ("att",),
+             "chunk_fused": ("qkv", "ao", "lse"), "chunk_gemm": ("att",)}
+
+
+def _att_saved(route, chunk, **tensors):
+    """what vit_attention hands to vit_attention_bwd: the route's name, Vision Longformer's chunk layout (host-side both) and the
+    route's tensors as attributes"""
+    assert tuple(tensors) == _ATT_KEPT[route]
+    return types.SimpleNamespace(route=route, chunk=_chunk3(chunk), **tensors)
+
+
+def vit_attention(o, qkv, bqkv, nB, N, nH, scale, save, out=None, chunk=None):
+    """Attention.forward between the projections (vision_transformer.py:76-83) -> (out, _att_saved for vit_attention_bwd or None).  A
+    crop is ONE window of the fused MFMA kernels: the 37 tokens of a 96^2 crop in the 64-slot kernels of window_attn.hip, the 197
+    tokens of a 224^2 crop in the 224-slot flash-style kernels of window_attn_big.hip (head_dim 64 in bf16), which also keep a
+    log-sum-exp -- no score matrix in HBM ("window").  What does not fit (fp32 parity mode at head_dim 64, longer sequences) takes the
+    batched-GEMM route of ops.vit_attn_fwd ("gemm"), or, for longer sequences under VIT_LONG_ATTENTION = "flash", the any-length kernels
+    of flash_attn.hip ("flash").  chunk: the sliding-chunk layout of a Vision Longformer stage -- the fused kernels of chunk_attn.hip
+    ("chunk_fused") or the masked batched GEMMs ("chunk_gemm").  The route is chosen HERE, once: the backward goes by its name."""
     hd = qkv.shape[1] // 3 // nH
-    if _vit_fused_route(N, hd, qkv.dtype):
+    if chunk is None and _vit_fused_route(N, hd, qkv.dtype):
         win2tok, ws, table = _vit_window(N, nH, qkv.device)
         frag = o.new_bias_frag(nH, N, qkv.device) if save else None
         ao, lse = o.window_attn_fwd(qkv, bqkv, win2tok, N, table, ws, None, 1, N, nH, scale, out=out, bias_frag=frag)
-        if not save:
-            return ao, ()
-        return ao, ((qkv, ao, frag) if lse is None else (qkv, ao, frag, lse))
-    if _vit_flash_route(o, N, hd, qkv.dtype):
+        return ao, (_att_saved("window", None, qkv=qkv, ao=ao, frag=frag, lse=lse) if save else None)
+    if chunk is None and _vit_flash_route(o, N, hd, qkv.dtype):
         ao, (_, _, lse) = o.global_attn_fwd(qkv, nB, N, nH, scale, out=out)
-        if not save:
-            return ao, ()
-        tag = _flash_tag(qkv.device)
-        return ao, (qkv, ao, lse, tag, tag)
-    ao, att = o.vit_attn_fwd(qkv, nB, N, nH, scale)
+        return ao, (_att_saved("flash", None, qkv=qkv, ao=ao, lse=lse) if save else None)
+    lse = att = None
+    if chunk is None:
+        route, (ao, att) = "gemm", o.vit_attn_fwd(qkv, nB, N, nH, scale)
+    elif _chunk_fused(o, chunk, qkv.dtype, hd):
+        route, (ao, (_, _, lse)) = "chunk_fused", o.sliding_chunk_attn_fwd(qkv, nB, N, nH, scale, chunk[:3])
+    else:
+        route, (ao, att) = "chunk_gemm", o.vit_attn_fwd(qkv, nB, N, nH, scale, chunk=_chunk3(chunk))
     if out is not None:
         out.copy_(ao)
         ao = out
-    return ao, att
+    if not save:
+        return ao, None
+    return ao, (_att_saved(route, chunk, qkv=qkv, ao=ao, lse=lse) if route == "chunk_fused" else _att_saved(route, chunk, att=att))
 
 
-def vit_attention_bwd(o, dao, att, bqkv, nB, N, nH, scale, dqkv_out=None):
-    if len(att) == 5:  # the flash route: (qkv, out, log-sum-exp, tag, tag)
-        return o.global_attn_bwd(dao, att[:3], nB, N, nH, scale, dqkv=dqkv_out)
-    if len(att) >= 3:  # the windowed routes: (qkv, out, bias fragments[, log-sum-exp of the 224-slot kernels])
-        qkv, ao, frag = att[:3]
-        lse = att[3] if len(att) == 4 else None
-        win2tok, ws, _ = _vit_window(N, nH, qkv.device)
-        return o.window_attn_bwd(qkv, bqkv, win2tok, N, dao, ao, lse, None, ws, None, 1, N, nH, scale, dqkv_out=dqkv_out, bias_frag=frag,
-                                 **_no_dbias(o, N, qkv.shape[1] // 3 // nH))[0]
-    dqkv = o.vit_attn_bwd(dao, att, nB, N, nH, scale)
+def vit_attention_bwd(o, dao, saved, bqkv, nB, N, nH, scale, dqkv_out=None):
+    route = saved.route
+    if route == "window":
+        win2tok, ws, _ = _vit_window(N, nH, saved.qkv.device)
+        return o.window_attn_bwd(saved.qkv, bqkv, win2tok, N, dao, saved.ao, saved.lse, None, ws, None, 1, N, nH, scale, dqkv_out=dqkv_out,
+                                 bias_frag=saved.frag, **_no_dbias(o, N, saved.qkv.shape[1] // 3 // nH))[0]
+    if route == "flash":
+        return o.global_attn_bwd(dao, (saved.qkv, saved.ao, saved.lse), nB, N, nH, scale, dqkv=dqkv_out)
+    if route == "gemm":
+        dqkv = o.vit_attn_bwd(dao, saved.att, nB, N, nH, scale)
+    elif route == "chunk_fused":
+        dqkv = o.sliding_chunk_attn_bwd(dao, (saved.qkv, saved.ao, saved.lse), nB, N, nH, scale, saved.chunk)
+    elif route == "chunk_gemm":
+        dqkv = o.vit_attn_bwd(dao, saved.att, nB, N, nH, scale, chunk=saved.chunk)
+    else:
+        raise ValueError("vit_attention_bwd: no attention route %r" % (route,))
     if dqkv_out is not None:
         dqkv_out.copy_(dqkv)
         dqkv = dqkv_out
     return dqkv
 
 
-def _vit_mlp_fwd(o, x1, prm, W1, W2, rowscale, rows_per_sample, save):
+def _vit_mlp_fwd(o, x1, prm, W1, W2, rowscale, rows_per_sample, save, one_kernel=True):
     """the MLP branch of a ViT block -> (x2, what the backward reads or None).  Inference pass (the EMA teacher, the eval consumers): the
-    branch in one kernel (deit_tiny / deit_small widths, whose fused kernels take the plain weight cast)"""
+    branch in one kernel (deit_tiny / deit_small widths, whose fused kernels take the plain weight cast) -- unless the caller rules
+    it out (one_kernel = False: Vision Longformer, whose inference pass has not been timed on it)"""
     C = x1.shape[1]
-    if not save and C in (192, 384) and _mlp_fused_infer(W1, C):
+    if one_kernel and not save and C in (192, 384) and _mlp_fused_infer(W1, C):
         g2, b2, bfc1, bfc2 = prm
         return o.mlp_fused_fwd(x1, g2, b2, LN_EPS, W1, bfc1, W2, bfc2, rowscale=_per_row(rowscale, rows_per_sample)), None
     return _mlp_fwd(o, x1, prm, W1, W2, LN_EPS, rowscale, rows_per_sample, save)
 
 
-def _vit_block_forward(x, nH, dp, prm, wts, save):
-    """Block.forward (vision_transformer.py:110-116) on x fp32 [nB, N, C] -> (y, tensors for the backward by name or None, those of the
-    attention)"""
+# ---- ONE block body for the monolithic ViT, its ragged multi-crop form and Vision Longformer: Block.forward (vision_transformer.py:
+# 110-116) on token ROWS.  LayerNorm, the four GEMMs and the residual adds are row-wise, so the rows of every resolution group of a step
+# run through them together; only the attention depends on a crop's token count and is launched once per group on its row range
+# (cf. SwinBlockMultiFn).  Compared with one pass per group (vision_transformer.py:186-233): half the launches, ONE gradient
+# contribution per parameter (no accumulation adds; the data-parallel reducer can overlap), half the split-K partial traffic of the
+# weight gradients.  The three entry points below differ in their arguments only:
+#   segs             tuple of (row0, nB, N): one for vit_block / vil_block (the attention then writes its own output: no `out=`,
+#                    no copy on the GEMM routes), one per resolution group for vit_block_multi
+#   rows_per_sample  N with per-sample DropPath factors, 1 with per-row ones (ragged)
+#   chunk            Vision Longformer's sliding-chunk layout, None otherwise
+#   Wkv / bkv        Vision Longformer's `kv` Linear beside `query` (None: one qkv Linear)
+#   mlp_one_kernel   may the inference pass take the one-kernel MLP branch (_vit_mlp_fwd)?
+def _vit_body_params(prm_list):
+    """(norm1.w, norm1.b, Wq | Wqkv, bq | bqkv, Wkv | None, bkv | None, Wproj, bproj, norm2.w, norm2.b, W1, b1, W2, b2) ->
+    (vectors, weight parameters, their activation-dtype copies) as _vit_body_fwd takes them"""
+    g1, b1, Wq_p, bq, Wkv_p, bkv, Wproj_p, bproj, g2, b2, W1_p, bfc1, W2_p, bfc2 = prm_list
+    wts = (_weight(Wq_p), _weight(Wkv_p) if Wkv_p is not None else None, _weight(Wproj_p), _weight(W1_p), _weight(W2_p))
+    return (g1, b1, bq, bkv, bproj, g2, b2, bfc1, bfc2), (Wq_p, Wkv_p, Wproj_p, W1_p, W2_p), wts
+
+
+def _vit_body_fwd(X, segs, rows_per_sample, nH, dp, chunk, mlp_one_kernel, prm, wts, save):
+    """X fp32 [M, C]; dp: None or the DropPath factors of (attention branch, MLP branch), one per `rows_per_sample` rows -> (y,
+    tensors for the backward by name or None, every segment's _att_saved)"""
     o = ops_module()
-    (g1, b1, bqkv, bproj, g2, b2, bfc1, bfc2) = prm
-    (Wqkv, Wproj, W1, W2) = wts
-    nB, N, C = x.shape
-    x2d = x.view(nB * N, C)
+    (g1, b1, bq, bkv, bproj, g2, b2, bfc1, bfc2) = prm
+    (Wq, Wkv, Wproj, W1, W2) = wts
+    M, C = X.shape
     scale = (C // nH) ** -0.5
     dp1, dp2 = (None, None) if dp is None else dp
-    xw, _, mean1, rstd1 = o.layernorm_fwd(x2d, g1, b1, LN_EPS)
-    qkv = o.linear_fwd(xw, Wqkv, bqkv)
-    ao, att = vit_attention(o, qkv, bqkv, nB, N, nH, scale, save)
-    x1 = o.linear_fwd(ao, Wproj, bproj, residual=x2d, rowscale=dp1, rows_per_sample=N, out_f32=True)
-    x2, mlp_saved = _vit_mlp_fwd(o, x1, (g2, b2, bfc1, bfc2), W1, W2, dp2, N, save)
-    saved = dict(mean1=mean1, rstd1=rstd1, xw=xw, ao=ao, x1=x1, **dict(zip(_MLP_SAVED, mlp_saved))) if save else None
-    return x2.view(nB, N, C), saved, att
+    xw, _, mean1, rstd1 = o.layernorm_fwd(X, g1, b1, LN_EPS)
+    if Wkv is None:   # one qkv Linear
+        qkv, bqkv = o.linear_fwd(xw, Wq, bq), bq
+    else:             # query | kv Linears: the same [q | k | v] column layout (longformer2d.py:160-162)
+        qkv = torch.cat((o.linear_fwd(xw, Wq, bq), o.linear_fwd(xw, Wkv, bkv)), dim=1)
+        bqkv = torch.cat((bq.detach(), bkv.detach()))
+    if len(segs) == 1:
+        (_, nB, N), = segs
+        ao, att = vit_attention(o, qkv, bqkv, nB, N, nH, scale, save, chunk=chunk)
+        atts = [att]
+    else:
+        ao = torch.empty((M, C), dtype=qkv.dtype, device=X.device)
+        atts = [vit_attention(o, qkv[r0:r0 + nB * N], bqkv, nB, N, nH, scale, save, out=ao[r0:r0 + nB * N], chunk=chunk)[1] for (r0, nB, N) in segs]
+    x1 = o.linear_fwd(ao, Wproj, bproj, residual=X, rowscale=dp1, rows_per_sample=rows_per_sample, out_f32=True)
+    x2, mlp_saved = _vit_mlp_fwd(o, x1, (g2, b2, bfc1, bfc2), W1, W2, dp2, rows_per_sample, save, one_kernel=mlp_one_kernel)
+    saved = dict(mean1=mean1, rstd1=rstd1, xw=xw, ao=ao, x1=x1, bqkv=bqkv, **dict(zip(_MLP_SAVED, mlp_saved))) if save else None
+    return x2, saved, atts
 
 
-class VitBlockFn(torch.autograd.Function):
+class VitBodyFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, nH, dp, g1, b1, Wqkv_p, bqkv, Wproj_p, bproj, g2, b2, W1_p, bfc1, W2_p, bfc2):
-        Wqkv, Wproj, W1, W2 = wts = (_weight(Wqkv_p), _weight(Wproj_p), _weight(W1_p), _weight(W2_p))
-        x = x.contiguous()
-        y, saved, att = _vit_block_forward(x, nH, dp, (g1, b1, bqkv, bproj, g2, b2, bfc1, bfc2), wts, True)
-        ctx.nH, ctx.dp = nH, dp
-        ctx.wparams = (Wqkv_p, Wproj_p, W1_p, W2_p)
-        ctx.bparams = (bqkv, bproj, bfc1, bfc2)
+    def forward(ctx, X, segs, rows_per_sample, nH, dp, chunk, mlp_one_kernel, *prm_list):
+        prm, ctx.wparams, wts = _vit_body_params(prm_list)
+        Wq, Wkv, Wproj, W1, W2 = wts
+        g1, b1, bq, bkv, bproj, g2, b2, bfc1, bfc2 = prm
+        y, saved, atts = _vit_body_fwd(X, segs, rows_per_sample, nH, dp, chunk, mlp_one_kernel, prm, wts, True)
+        ctx.segs, ctx.rows_per_sample, ctx.nH, ctx.dp = segs, rows_per_sample, nH, dp
+        ctx.bparams = (bq, bkv, bproj, bfc1, bfc2)
         ctx.nparams = (g1, b1, g2, b2)
-        _save_named(ctx, x=x, g1=g1, g2=g2, bqkv=bqkv, Wqkv=Wqkv, Wproj=Wproj, W1=W1, W2=W2, att=att, **saved)
+        ctx.att_host = [(a.route, a.chunk) for a in atts]  # the tensors of segment i go under "att<i>_<name>"
+        _save_named(ctx, X=X, g1=g1, g2=g2, Wq=Wq, Wkv=Wkv, Wproj=Wproj, W1=W1, W2=W2, **saved,
+                    **{"att%d_%s" % (i, k): getattr(a, k) for i, a in enumerate(atts) for k in _ATT_KEPT[a.route]})
         return y
 
     @staticmethod
     def backward(ctx, gy):
         o = ops_module()
-        nH, dp = ctx.nH, ctx.dp
+        segs, rps, nH, dp = ctx.segs, ctx.rows_per_sample, ctx.nH, ctx.dp
         s = _load_named(ctx)
-        x, xw, ao = s.x, s.xw, s.ao
-        nB, N, C = x.shape
-        M = nB * N
+        X, xw, ao = s.X, s.xw, s.ao
+        atts = [_att_saved(route, chunk, **{k: getattr(s, "att%d_%s" % (i, k)) for k in _ATT_KEPT[route]}) for i, (route, chunk) in enumerate(ctx.att_host)]
+        M, C = X.shape
         scale = (C // nH) ** -0.5
         dp1, dp2 = (None, None) if dp is None else dp
-        gy = gy.contiguous().view(M, C)
-        Wqkv_p, Wproj_p, W1_p, W2_p = ctx.wparams
-        bqkv_p, bproj_p, bfc1_p, bfc2_p = ctx.bparams
+        gy = gy.contiguous()
+        Wq_p, Wkv_p, Wproj_p, W1_p, W2_p = ctx.wparams
+        bq_p, bkv_p, bproj_p, bfc1_p, bfc2_p = ctx.bparams
         g1_p, b1_p, g2_p, b2_p = ctx.nparams
-        dyb = o.gather_cast(gy, M, rowscale=dp2, rows_per_sample=N)
+        dyb = o.gather_cast(gy, M, rowscale=dp2, rows_per_sample=rps)
         dh, dW1, dbfc1, dW2, dbfc2 = _mlp_bwd(o, dyb, s.h, s.a1, s.a1g, s.W1, s.W2, (W1_p, bfc1_p, W2_p, bfc2_p))
         sink1, sink2 = _ln_sinks(g1_p, b1_p), _ln_sinks(g2_p, b2_p)
-        gx1, dyw, dg2, db2 = o.layernorm_bwd_cast(dh, s.x1, s.mean2, s.rstd2, s.g2, g_in=gy, rowscale=dp1, rows_per_sample=N, gb_out=sink2)
+        gx1, dyw, dg2, db2 = o.layernorm_bwd_cast(dh, s.x1, s.mean2, s.rstd2, s.g2, g_in=gy, rowscale=dp1, rows_per_sample=rps, gb_out=sink2)
         dWproj, dbproj = _side_run(lambda: _wgrad(dyw, ao, Wproj_p, want_bias=True, bias_param=bproj_p), dyw, ao)
         dao = o.linear_dgrad(dyw, s.Wproj)
-        dqkv = vit_attention_bwd(o, dao, s.att, s.bqkv, nB, N, nH, scale)
-        dWqkv, dbqkv = _side_run(lambda: _wgrad(dqkv, xw, Wqkv_p, want_bias=True, bias_param=bqkv_p), dqkv, xw)
-        dxw = o.linear_dgrad(dqkv, s.Wqkv)
-        gx, dg1, db1 = o.layernorm_bwd(dxw, x.view(M, C), s.mean1, s.rstd1, s.g1, g_in=gx1, gb_out=sink1)
+        if len(segs) == 1:
+            (_, nB, N), = segs
+            dqkv = vit_attention_bwd(o, dao, atts[0], s.bqkv, nB, N, nH, scale)
+        else:
+            dqkv = torch.empty((M, 3 * C), dtype=dao.dtype, device=dao.device)
+            for (r0, nB, N), att in zip(segs, atts):
+                r1 = r0 + nB * N
+                vit_attention_bwd(o, dao[r0:r1], att, s.bqkv, nB, N, nH, scale, dqkv_out=dqkv[r0:r1])
+        if Wkv_p is None:
+            dWq, dbq = _side_run(lambda: _wgrad(dqkv, xw, Wq_p, want_bias=True, bias_param=bq_p), dqkv, xw)
+            dWkv, dbkv = None, None
+            dxw = o.linear_dgrad(dqkv, s.Wq)
+        else:
+            dq, dkv = dqkv[:, :C].contiguous(), dqkv[:, C:].contiguous()
+            dWq, dbq = _side_run(lambda: _wgrad(dq, xw, Wq_p, want_bias=True, bias_param=bq_p), dq, xw)
+            dWkv, dbkv = _side_run(lambda: _wgrad(dkv, xw, Wkv_p, want_bias=True, bias_param=bkv_p), dkv, xw)
+            dxw = o.linear_dgrad(dqkv, torch.cat((s.Wq, s.Wkv), 0))  # dq Wq + dkv Wkv as one product over the stacked (tiny) weights
+        gx, dg1, db1 = o.layernorm_bwd(dxw, X, s.mean1, s.rstd1, s.g1, g_in=gx1, gb_out=sink1)
         _side_join()
-        return (gx.view(nB, N, C), None, None, _alias(dg1, sink1), _alias(db1, sink1), dWqkv, dbqkv, dWproj, dbproj,
+        return (gx, None, None, None, None, None, None, _alias(dg1, sink1), _alias(db1, sink1), dWq, dbq, dWkv, dbkv, dWproj, dbproj,
                 _alias(dg2, sink2), _alias(db2, sink2), dW1, dbfc1, dW2, dbfc2)
 
 
+def _vit_body(X, segs, rows_per_sample, nH, dp, chunk, mlp_one_kernel, prm_list):
+    """X fp32 [M, C] through one block; the inference pass keeps nothing and builds no node"""
+    X = X.contiguous()
+    if torch.is_grad_enabled() and (X.requires_grad or any(p is not None and p.requires_grad for p in prm_list)):
+        return VitBodyFn.apply(X, segs, rows_per_sample, nH, dp, chunk, mlp_one_kernel, *prm_list)
+    prm, _, wts = _vit_body_params(prm_list)
+    return _vit_body_fwd(X, segs, rows_per_sample, nH, dp, chunk, mlp_one_kernel, prm, wts, False)[0]
+
+
 def vit_block(x, nH, dp, prm_list):
-    if not torch.is_grad_enabled() or not (x.requires_grad or any(p.requires_grad for p in prm_list)):
-        g1, b1, Wqkv_p, bqkv, Wproj_p, bproj, g2, b2, W1_p, bfc1, W2_p, bfc2 = prm_list
-        wts = (_weight(Wqkv_p), _weight(Wproj_p), _weight(W1_p), _weight(W2_p))
-        return _vit_block_forward(x.contiguous(), nH, dp, (g1, b1, bqkv, bproj, g2, b2, bfc1, bfc2), wts, False)[0]
-    return VitBlockFn.apply(x, nH, dp, *prm_list)
+    """x fp32 [nB, N, C]; dp: None or the per-sample DropPath factors of the two branches"""
+    nB, N, C = x.shape
+    return _vit_body(x.contiguous().view(nB * N, C), ((0, nB, N),), N, nH, dp, None, True, (*prm_list[:4], None, None, *prm_list[4:])).view(nB, N, C)
+
+
+def vit_block_multi(X, segs, nH, dp_rows, prm_list):
+    """one ViT block over the token rows of several resolution groups; X fp32 [M, C]; segs: tuple of (row0, nB, N); dp_rows: None or
+    (per-row DropPath scale of the attention branch [M], MLP branch [M])"""
+    return _vit_body(X, segs, 1, nH, dp_rows, None, True, (*prm_list[:4], None, None, *prm_list[4:]))
+
+
+def _vit_block_qkv(o, x, nH, prm_list):
+    """LayerNorm and the qkv projection of a block recomputed on its input x fp32 [nB, N, C] -> (qkv, nB, N, scale)"""
+    g1, b1, Wqkv_p, bqkv = prm_list[:4]
+    nB, N, C = x.shape
+    xw = o.layernorm_fwd(x.contiguous().view(nB * N, C), g1, b1, LN_EPS)[0]
+    return o.linear_fwd(xw, _weight(Wqkv_p), bqkv), nB, N, (C // nH) ** -0.5
 
 
 def vit_block_attention(x, nH, prm_list):
     """the attention probabilities [nB, nH, N, N] of a block (Block.forward(return_attention=True), vision_transformer.py:112)"""
     o = ops_module()
-    g1, b1, Wqkv_p, bqkv = prm_list[:4]
-    nB, N, C = x.shape
-    xw = o.layernorm_fwd(x.contiguous().view(nB * N, C), g1, b1, LN_EPS)[0]
-    qkv = o.linear_fwd(xw, _weight(Wqkv_p), bqkv)
-    _, att = o.vit_attn_fwd(qkv, nB, N, nH, (C // nH) ** -0.5)  # (evaluation hook: the batched-GEMM route keeps P in memory)
-    p = att[-1]
+    qkv, nB, N, scale = _vit_block_qkv(o, x, nH, prm_list)
+    p = o.vit_attn_fwd(qkv, nB, N, nH, scale)[1][-1]  # (evaluation hook: the batched-GEMM route keeps P in memory)
     return p.reshape(nB, nH, p.shape[-2], p.shape[-1])[:, :, :N, :N].float()
 
 
@@ -2229,8 +2323,7 @@ def vit_attention_stats(o, qkv, nB, N, nH, scale, queries=None):
     ents, rows = [], []
     for b0 in range(0, nB, step):
         nb = min(step, nB - b0)
-        _, att = o.vit_attn_fwd(qkv[b0 * N:(b0 + nb) * N], nb, N, nH, scale)
-        p = att[-1]
+        p = o.vit_attn_fwd(qkv[b0 * N:(b0 + nb) * N], nb, N, nH, scale)[1][-1]
         p = p.reshape(nb, nH, p.shape[-2], p.shape[-1])[:, :, :N, :N].float()
         ents.append(torch.special.entr(p).sum(-1))
         if idx is not None:
@@ -2242,204 +2335,19 @@ def vit_block_attention_stats(x, nH, prm_list, queries=None):
     """vit_attention_stats of a block's attention on its input x fp32 [nB, N, C] (LayerNorm and the qkv projection are recomputed, as
     vit_block_attention does)"""
     o = ops_module()
-    g1, b1, Wqkv_p, bqkv = prm_list[:4]
-    nB, N, C = x.shape
-    xw = o.layernorm_fwd(x.contiguous().view(nB * N, C), g1, b1, LN_EPS)[0]
-    qkv = o.linear_fwd(xw, _weight(Wqkv_p), bqkv)
-    return vit_attention_stats(o, qkv, nB, N, nH, (C // nH) ** -0.5, queries)
+    qkv, nB, N, scale = _vit_block_qkv(o, x, nH, prm_list)
+    return vit_attention_stats(o, qkv, nB, N, nH, scale, queries)
 
 
 # ------------------------------------------------------------------------------------------------
-# Vision Longformer (models/vision_longformer.py:406-770): an AttnBlock followed by its MlpBlock is one autograd node, like a ViT
-# block.  'full' stages project with one qkv Linear (vision_longformer.py:36-118); 'longformerhand' stages (layers/longformer2d.py)
+# Vision Longformer (models/vision_longformer.py:406-770): an AttnBlock followed by its MlpBlock is one autograd node: the body of a ViT
+# block (_vit_body).  'full' stages project with one qkv Linear (vision_longformer.py:36-118); 'longformerhand' stages (layers/longformer2d.py)
 # with `query` and `kv` Linears -- shared by local and global tokens (sharew) -- and restrict every local query to the global tokens
 # plus its own and the eight adjacent w x w chunks (`chunk`, esvit_softmax_rows_chunked_fwd).  rpe off (the ape = 1 default of
 # the reference's yaml files): no bias tables.
 # ------------------------------------------------------------------------------------------------
-def _chunk_fused(o, chunk, dtype, hd):
-    """does this sliding-chunk stage take the fused kernels (ops.sliding_chunk_attn_fwd)?  The model asks for them with a fourth tuple
-    entry, the chunk side (MsViT._stage under CHUNK_ATTENTION = "fused"); an ops module without the entry (the CPU restatement,
-    oracle/ops_ref.py) or an unsupported shape (fp32 parity mode, other head dims) keeps the dense route."""
-    if not isinstance(chunk, tuple) or len(chunk) < 4:
-        return False
-    sup = getattr(o, "sliding_chunk_attn_supported", None)
-    return sup is not None and bool(sup(dtype, hd, chunk[3], chunk[1]))
-
-
-def _chunk3(chunk):
-    return chunk[:3] if isinstance(chunk, tuple) else chunk
-
-
-def _vil_block_forward(x, nH, dp, chunk, prm, wts, save):
-    o = ops_module()
-    (g1, b1, bq, bkv, bproj, g2, b2, bfc1, bfc2) = prm
-    (Wq, Wkv, Wproj, W1, W2) = wts
-    nB, N, C = x.shape
-    x2d = x.view(nB * N, C)
-    scale = (C // nH) ** -0.5
-    dp1, dp2 = (None, None) if dp is None else dp
-    xw, _, mean1, rstd1 = o.layernorm_fwd(x2d, g1, b1, LN_EPS)
-    if Wkv is None:   # one qkv Linear
-        qkv, bqkv = o.linear_fwd(xw, Wq, bq), bq
-    else:             # query | kv Linears: the same [q | k | v] column layout (longformer2d.py:160-162)
-        qkv = torch.cat((o.linear_fwd(xw, Wq, bq), o.linear_fwd(xw, Wkv, bkv)), dim=1)
-        bqkv = torch.cat((bq.detach(), bkv.detach()))
-    if chunk is None:
-        ao, att = vit_attention(o, qkv, bqkv, nB, N, nH, scale, save)
-    elif _chunk_fused(o, chunk, qkv.dtype, C // nH):
-        # fused sliding-chunk kernels: saved = (qkv, out, lse); `ao` rides in `saved` below, so only (qkv, lse) are extra
-        ao, (_, _, lse) = o.sliding_chunk_attn_fwd(qkv, nB, N, nH, scale, chunk[:3])
-        att = (qkv, lse) if save else ()
-    else:
-        ao, att = o.vit_attn_fwd(qkv, nB, N, nH, scale, chunk=_chunk3(chunk))
-        att = att if save else ()
-    x1 = o.linear_fwd(ao, Wproj, bproj, residual=x2d, rowscale=dp1, rows_per_sample=N, out_f32=True)
-    x2, mlp_saved = _mlp_fwd(o, x1, (g2, b2, bfc1, bfc2), W1, W2, LN_EPS, dp2, N, save)
-    saved = dict(mean1=mean1, rstd1=rstd1, xw=xw, ao=ao, x1=x1, bqkv=bqkv, **dict(zip(_MLP_SAVED, mlp_saved))) if save else None
-    return x2.view(nB, N, C), saved, att
-
-
-class VilBlockFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x, nH, dp, chunk, g1, b1, Wq_p, bq, Wkv_p, bkv, Wproj_p, bproj, g2, b2, W1_p, bfc1, W2_p, bfc2):
-        split = Wkv_p is not None
-        Wq, Wkv, Wproj, W1, W2 = wts = (_weight(Wq_p), _weight(Wkv_p) if split else None, _weight(Wproj_p), _weight(W1_p), _weight(W2_p))
-        x = x.contiguous()
-        y, saved, att = _vil_block_forward(x, nH, dp, chunk, (g1, b1, bq, bkv, bproj, g2, b2, bfc1, bfc2), wts, True)
-        ctx.nH, ctx.dp, ctx.split, ctx.chunk = nH, dp, split, chunk
-        ctx.wparams = (Wq_p, Wkv_p, Wproj_p, W1_p, W2_p)
-        ctx.bparams = (bq, bkv, bproj, bfc1, bfc2)
-        ctx.nparams = (g1, b1, g2, b2)
-        _save_named(ctx, x=x, g1=g1, g2=g2, Wq=Wq, Wkv=Wkv, Wproj=Wproj, W1=W1, W2=W2, att=att, **saved)
-        return y
-
-    @staticmethod
-    def backward(ctx, gy):
-        o = ops_module()
-        nH, dp, split = ctx.nH, ctx.dp, ctx.split
-        s = _load_named(ctx)
-        x, xw, ao, att = s.x, s.xw, s.ao, s.att
-        nB, N, C = x.shape
-        M = nB * N
-        scale = (C // nH) ** -0.5
-        dp1, dp2 = (None, None) if dp is None else dp
-        gy = gy.contiguous().view(M, C)
-        Wq_p, Wkv_p, Wproj_p, W1_p, W2_p = ctx.wparams
-        bq_p, bkv_p, bproj_p, bfc1_p, bfc2_p = ctx.bparams
-        g1_p, b1_p, g2_p, b2_p = ctx.nparams
-        dyb = o.gather_cast(gy, M, rowscale=dp2, rows_per_sample=N)
-        dh, dW1, dbfc1, dW2, dbfc2 = _mlp_bwd(o, dyb, s.h, s.a1, s.a1g, s.W1, s.W2, (W1_p, bfc1_p, W2_p, bfc2_p))
-        sink1, sink2 = _ln_sinks(g1_p, b1_p), _ln_sinks(g2_p, b2_p)
-        gx1, dyw, dg2, db2 = o.layernorm_bwd_cast(dh, s.x1, s.mean2, s.rstd2, s.g2, g_in=gy, rowscale=dp1, rows_per_sample=N, gb_out=sink2)
-        dWproj, dbproj = _side_run(lambda: _wgrad(dyw, ao, Wproj_p, want_bias=True, bias_param=bproj_p), dyw, ao)
-        dao = o.linear_dgrad(dyw, s.Wproj)
-        if ctx.chunk is not None and _chunk_fused(o, ctx.chunk, ao.dtype, C // nH):
-            dqkv = o.sliding_chunk_attn_bwd(dao, (att[0], ao, att[1]), nB, N, nH, scale, ctx.chunk[:3])
-        elif ctx.chunk is not None:
-            dqkv = o.vit_attn_bwd(dao, att, nB, N, nH, scale, chunk=_chunk3(ctx.chunk))
-        else:
-            dqkv = vit_attention_bwd(o, dao, att, s.bqkv, nB, N, nH, scale)
-        if split:
-            dq, dkv = dqkv[:, :C].contiguous(), dqkv[:, C:].contiguous()
-            dWq, dbq = _side_run(lambda: _wgrad(dq, xw, Wq_p, want_bias=True, bias_param=bq_p), dq, xw)
-            dWkv, dbkv = _side_run(lambda: _wgrad(dkv, xw, Wkv_p, want_bias=True, bias_param=bkv_p), dkv, xw)
-            dxw = o.linear_dgrad(dqkv, torch.cat((s.Wq, s.Wkv), 0))  # dq Wq + dkv Wkv as one product over the stacked (tiny) weights
-        else:
-            dWq, dbq = _side_run(lambda: _wgrad(dqkv, xw, Wq_p, want_bias=True, bias_param=bq_p), dqkv, xw)
-            dWkv, dbkv = None, None
-            dxw = o.linear_dgrad(dqkv, s.Wq)
-        gx, dg1, db1 = o.layernorm_bwd(dxw, x.view(M, C), s.mean1, s.rstd1, s.g1, g_in=gx1, gb_out=sink1)
-        _side_join()
-        return (gx.view(nB, N, C), None, None, None, _alias(dg1, sink1), _alias(db1, sink1), dWq, dbq, dWkv, dbkv, dWproj, dbproj,
-                _alias(dg2, sink2), _alias(db2, sink2), dW1, dbfc1, dW2, dbfc2)
-
-
 def vil_block(x, nH, dp, chunk, prm_list):
-    """prm_list = (norm.w, norm.b, Wq | Wqkv, bq | bqkv, Wkv | None, bkv | None, Wproj, bproj, norm2.w, norm2.b, W1, b1, W2, b2)"""
-    if not torch.is_grad_enabled() or not (x.requires_grad or any(p is not None and p.requires_grad for p in prm_list)):
-        g1, b1, Wq_p, bq, Wkv_p, bkv, Wproj_p, bproj, g2, b2, W1_p, bfc1, W2_p, bfc2 = prm_list
-        wts = (_weight(Wq_p), _weight(Wkv_p) if Wkv_p is not None else None, _weight(Wproj_p), _weight(W1_p), _weight(W2_p))
-        return _vil_block_forward(x.contiguous(), nH, dp, chunk, (g1, b1, bq, bkv, bproj, g2, b2, bfc1, bfc2), wts, False)[0]
-    return VilBlockFn.apply(x, nH, dp, chunk, *prm_list)
-
-
-# ---- ragged multi-crop ViT block: all crops of a step in ONE set of LayerNorm / GEMM launches (cf. SwinBlockMultiFn) ------------
-# LayerNorm, the four GEMMs and the residual adds are row-wise, so the token rows of the 224^2 crops and of the 96^2 crops run
-# through them together; only the attention depends on the crop's token count and is launched once per resolution group on its
-# row range.  Compared with one pass per group (vision_transformer.py:186-233): half the launches, ONE gradient contribution per
-# parameter (no accumulation adds; the data-parallel reducer can overlap), half the split-K partial traffic of the weight gradients.
-def _vit_block_forward_multi(X, segs, nH, dp_rows, prm, wts, save):
-    """X fp32 [M, C]; segs: tuple of (row0, nB, N); dp_rows: None or (per-row DropPath scale of the attention branch [M], MLP branch [M])
-    -> (y, tensors for the backward by name or None, those of every group's attention)"""
-    o = ops_module()
-    (g1, b1, bqkv, bproj, g2, b2, bfc1, bfc2) = prm
-    (Wqkv, Wproj, W1, W2) = wts
-    M, C = X.shape
-    scale = (C // nH) ** -0.5
-    dp1, dp2 = (None, None) if dp_rows is None else dp_rows
-    xw, _, mean1, rstd1 = o.layernorm_fwd(X, g1, b1, LN_EPS)
-    qkv = o.linear_fwd(xw, Wqkv, bqkv)
-    ao = torch.empty((M, C), dtype=qkv.dtype, device=X.device)
-    atts = []
-    for (r0, nB, N) in segs:
-        r1 = r0 + nB * N
-        _, att = vit_attention(o, qkv[r0:r1], bqkv, nB, N, nH, scale, save, out=ao[r0:r1])
-        atts.append(att)
-    x1 = o.linear_fwd(ao, Wproj, bproj, residual=X, rowscale=dp1, rows_per_sample=1, out_f32=True)
-    x2, mlp_saved = _vit_mlp_fwd(o, x1, (g2, b2, bfc1, bfc2), W1, W2, dp2, 1, save)
-    saved = dict(mean1=mean1, rstd1=rstd1, xw=xw, ao=ao, x1=x1, **dict(zip(_MLP_SAVED, mlp_saved))) if save else None
-    return x2, saved, atts
-
-
-class VitBlockMultiFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, X, segs, nH, dp_rows, g1, b1, Wqkv_p, bqkv, Wproj_p, bproj, g2, b2, W1_p, bfc1, W2_p, bfc2):
-        Wqkv, Wproj, W1, W2 = wts = (_weight(Wqkv_p), _weight(Wproj_p), _weight(W1_p), _weight(W2_p))
-        X = X.contiguous()
-        y, saved, atts = _vit_block_forward_multi(X, segs, nH, dp_rows, (g1, b1, bqkv, bproj, g2, b2, bfc1, bfc2), wts, True)
-        ctx.segs, ctx.nH, ctx.dp_rows = segs, nH, dp_rows
-        ctx.wparams = (Wqkv_p, Wproj_p, W1_p, W2_p)
-        ctx.bparams = (bqkv, bproj, bfc1, bfc2)
-        ctx.nparams = (g1, b1, g2, b2)
-        _save_named(ctx, X=X, g1=g1, g2=g2, bqkv=bqkv, Wqkv=Wqkv, Wproj=Wproj, W1=W1, W2=W2, **saved, **{"att%d" % i: a for i, a in enumerate(atts)})
-        return y
-
-    @staticmethod
-    def backward(ctx, gy):
-        o = ops_module()
-        segs, nH, dp_rows = ctx.segs, ctx.nH, ctx.dp_rows
-        s = _load_named(ctx)
-        X, xw, ao = s.X, s.xw, s.ao
-        atts = [getattr(s, "att%d" % i) for i in range(len(segs))]
-        M, C = X.shape
-        scale = (C // nH) ** -0.5
-        dp1, dp2 = (None, None) if dp_rows is None else dp_rows
-        gy = gy.contiguous()
-        Wqkv_p, Wproj_p, W1_p, W2_p = ctx.wparams
-        bqkv_p, bproj_p, bfc1_p, bfc2_p = ctx.bparams
-        g1_p, b1_p, g2_p, b2_p = ctx.nparams
-        dyb = o.gather_cast(gy, M, rowscale=dp2, rows_per_sample=1)
-        dh, dW1, dbfc1, dW2, dbfc2 = _mlp_bwd(o, dyb, s.h, s.a1, s.a1g, s.W1, s.W2, (W1_p, bfc1_p, W2_p, bfc2_p))
-        sink1, sink2 = _ln_sinks(g1_p, b1_p), _ln_sinks(g2_p, b2_p)
-        gx1, dyw, dg2, db2 = o.layernorm_bwd_cast(dh, s.x1, s.mean2, s.rstd2, s.g2, g_in=gy, rowscale=dp1, rows_per_sample=1, gb_out=sink2)
-        dWproj, dbproj = _side_run(lambda: _wgrad(dyw, ao, Wproj_p, want_bias=True, bias_param=bproj_p), dyw, ao)
-        dao = o.linear_dgrad(dyw, s.Wproj)
-        dqkv = torch.empty((M, 3 * C), dtype=dao.dtype, device=dao.device)
-        for (r0, nB, N), att in zip(segs, atts):
-            r1 = r0 + nB * N
-            vit_attention_bwd(o, dao[r0:r1], att, s.bqkv, nB, N, nH, scale, dqkv_out=dqkv[r0:r1])
-        dWqkv, dbqkv = _side_run(lambda: _wgrad(dqkv, xw, Wqkv_p, want_bias=True, bias_param=bqkv_p), dqkv, xw)
-        dxw = o.linear_dgrad(dqkv, s.Wqkv)
-        gx, dg1, db1 = o.layernorm_bwd(dxw, X, s.mean1, s.rstd1, s.g1, g_in=gx1, gb_out=sink1)
-        _side_join()
-        return (gx, None, None, None, _alias(dg1, sink1), _alias(db1, sink1), dWqkv, dbqkv, dWproj, dbproj,
-                _alias(dg2, sink2), _alias(db2, sink2), dW1, dbfc1, dW2, dbfc2)
-
-
-def vit_block_multi(X, segs, nH, dp_rows, prm_list):
-    """one ViT block over the token rows of several resolution groups; X fp32 [M, C]"""
-    if torch.is_grad_enabled() and (X.requires_grad or any(p.requires_grad for p in prm_list)):
-        return VitBlockMultiFn.apply(X, segs, nH, dp_rows, *prm_list)
-    g1, b1, Wqkv_p, bqkv, Wproj_p, bproj, g2, b2, W1_p, bfc1, W2_p, bfc2 = prm_list
-    wts = (_weight(Wqkv_p), _weight(Wproj_p), _weight(W1_p), _weight(W2_p))
-    return _vit_block_forward_multi(X.contiguous(), segs, nH, dp_rows, (g1, b1, bqkv, bproj, g2, b2, bfc1, bfc2), wts, False)[0]
+    """prm_list = (norm.w, norm.b, Wq | Wqkv, bq | bqkv, Wkv | None, bkv | None, Wproj, bproj, norm2.w, norm2.b, W1, b1, W2, b2).  The
+    inference pass keeps the unfused MLP branch at every width"""
+    nB, N, C = x.shape
+    return _vit_body(x.contiguous().view(nB * N, C), ((0, nB, N),), N, nH, dp, chunk, False, prm_list).view(nB, N, C)

@@ -9,7 +9,7 @@ zero-padded and out-of-range positions that implementation masks are exactly the
 everything, and with SHARE_W the global tokens use the same `query` / `kv` / `proj` Linears; s = 0 stages use plain multi-head
 attention (vision_longformer.py:36-118).
 
-MI355X formulation: an (AttnBlock, MlpBlock) pair is ONE autograd node on the kernels of the monolithic ViT (functional.VilBlockFn):
+MI355X formulation: an (AttnBlock, MlpBlock) pair is ONE autograd node, the block body of the monolithic ViT (functional.vil_block):
 LayerNorm, MFMA GEMMs with fused bias / GELU / residual / DropPath epilogues, and for the attention either the fused windowed
 kernels (full stages: 197 / 50 / 37 / 9 tokens are one window) or, for the sliding-chunk stages, batched MFMA score GEMMs with a
 row softmax restricted to the chunk neighbourhood (esvit_softmax_rows_chunked_fwd).  The patch embeddings are the im2col + GEMM +

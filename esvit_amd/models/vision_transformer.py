@@ -192,7 +192,7 @@ class VisionTransformer(nn.Module):
 
     def _forward_ragged(self, runs):
         """every run of equal-resolution crops as token ROWS of one matrix: the row-wise kernels of a block see all crops at once,
-        the attention is launched per run on its row range (functional.VitBlockMultiFn) -> list of normed [B_g, N_g, C]"""
+        the attention is launched per run on its row range (functional.vit_block_multi) -> list of normed [B_g, N_g, C]"""
         toks = [self._tokens(r) for r in runs]
         C = toks[0].shape[-1]
         segs, row0 = [], 0

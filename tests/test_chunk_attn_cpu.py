@@ -1,6 +1,6 @@
 """-m "not gpu": the fused sliding-chunk attention without a GPU -- the slot -> token arithmetic of the kernels (csrc/chunk_geom.h compiled
 for the host) against the mask of the dense route, a per-chunk torch restatement of the algorithm the kernels implement (forward with
-the log-sum-exp, backward with delta) against oracle/ops_ref.vit_attn_fwd / _bwd, the save / restore plumbing of VilBlockFn on that
+the log-sum-exp, backward with delta) against oracle/ops_ref.vit_attn_fwd / _bwd, the save / restore plumbing of vil_block on that
 restatement against the reference's fixture, and the argument checks of the C entry."""
 import ctypes as C
 import os
@@ -177,7 +177,7 @@ def test_per_chunk_restatement_equals_dense_route(geom, grid, nglo, hd):
 
 def test_vil_block_plumbing_on_the_restatement(cpu_ops, geom, monkeypatch):  # noqa: F811
     """CHUNK_ATTENTION = "fused" with the per-chunk restatement in the place of the kernels: the save / restore of (qkv, lse) in
-    VilBlockFn reproduces the reference's fixture within the bounds of test_vil_full_width_composition_matches_reference_golden"""
+    the block body (functional.VitBodyFn) reproduces the reference's fixture within the bounds of test_vil_full_width_composition_matches_reference_golden"""
     from esvit_amd.models import vision_longformer as vil
     from tests.test_step_gpu import check_full_vil_case
     calls = {"fwd": 0, "bwd": 0, "sup": 0}

@@ -59,16 +59,17 @@ class Session:
     """functional (and head, params, loss) on a Recorder, the route switches pinned to their defaults, _side_run / _side_join and
     every Function's backward wrapped: `unjoined` lists the nodes that returned with side-stream work nobody had joined"""
 
-    def __init__(self, mp, Fn, wide=False):
+    def __init__(self, mp, Fn, wide=False, route=None):
         import esvit_amd.loss as L
         import esvit_amd.params as P
         self.Fn, self.P = Fn, P
-        over = {"mlp_fused_train_supported": lambda dt, Cc, rows=0: dt == torch.bfloat16 and Cc == WIDE_C} if wide else None
+        over = {"mlp_fused_train_supported": lambda dt, Cc, rows=0: dt == torch.bfloat16 and Cc == WIDE_C} if wide else {}
+        over.update(STUBS[route]() if route else {})
         self.rec = rec = Recorder(ops_ref, over)
         for mod in (Fn, L, P):
             mp.setattr(mod, "ops", rec)
         for name, val in (("ATTN_FUSED", True), ("ATTN_BWD_FUSED", False), ("MLP_FUSED_TRAIN", True), ("MLP_WIDE_FUSED", True),
-                          ("MLP_WIDE_TRAIN", wide), ("MLP_DW_ONCHIP", True)):
+                          ("MLP_WIDE_TRAIN", wide), ("MLP_DW_ONCHIP", True), ("VIT_LONG_ATTENTION", "flash" if route == "flash" else "gemm")):
             mp.setattr(Fn, name, val)
         for name in ("cached_cast", "cached"):
             mp.setattr(P, name, self._muted(getattr(P, name)))
@@ -115,6 +116,66 @@ class Session:
         self.Fn._GEOM.clear()
         del self.rec.trace[:]
         del self.unjoined[:]
+
+
+# ---- attention routes the restatement does not have: stand-ins over its dense route, handed to the Recorder as `over`.  What such a
+# route's forward returns for the backward is a contract of its own: every stand-in's backward insists on the very tensors its forward
+# returned ------------------------------------------------------------------------------------------------------------------------------
+def _returned(kept, saved):
+    assert any(len(k) == len(saved) and all(a is b for a, b in zip(k, saved)) for k in kept), [_sig(t) for t in saved]
+
+
+def _dense_stubs(fwd_name, bwd_name, sup_name, with_chunk):
+    """`fwd_name` -> (ao, (qkv, ao, lse [nB, nH, N])) and `bwd_name` of it, computed by ops_ref.vit_attn_fwd / _bwd"""
+    kept, dense = [], {}
+
+    def fwd(qkv, nB, N, nH, scale, *chunk, out=None):
+        assert len(chunk) == with_chunk
+        ao, att = ops_ref.vit_attn_fwd(qkv, nB, N, nH, scale, *chunk)
+        if out is not None:
+            out.copy_(ao)
+            ao = out
+        lse = torch.zeros(nB, nH, N)
+        kept.append((qkv, ao, lse))
+        dense[id(lse)] = att
+        return ao, kept[-1]
+
+    def bwd(dao, saved, nB, N, nH, scale, *chunk, dqkv=None):
+        assert len(chunk) == with_chunk
+        _returned(kept, saved)
+        dq = ops_ref.vit_attn_bwd(dao, dense[id(saved[2])], nB, N, nH, scale, *chunk)
+        if dqkv is not None:
+            dqkv.copy_(dq)
+            dq = dqkv
+        return dq
+    return {fwd_name: fwd, bwd_name: bwd, sup_name: lambda *a: True}
+
+
+def _window_lse_stubs():
+    """the 224-slot kernels' log-sum-exp: windows of more than 64 tokens return one, and the backward is handed that tensor"""
+    kept = []
+
+    def fwd(qkv, qkv_bias, win2tok, L, table, ws, region_ids, nW, N, nH, scale, **k):
+        ao = ops_ref.window_attn_fwd(qkv, qkv_bias, win2tok, L, table, ws, region_ids, nW, N, nH, scale, **k)[0]
+        lse = torch.zeros(qkv.shape[0] // L * nW, nH, N) if N > 64 else None
+        kept.append((qkv, ao, lse, k.get("bias_frag")))
+        return ao, lse
+
+    def bwd(qkv, qkv_bias, win2tok, L, dout, fwd_out, lse, *a, **k):
+        assert (lse is not None) == (a[4] > 64)
+        _returned(kept, (qkv, fwd_out, lse, k.get("bias_frag")))
+        return ops_ref.window_attn_bwd(qkv, qkv_bias, win2tok, L, dout, fwd_out, lse, *a, **k)
+    return {"window_attn_fwd": fwd, "window_attn_bwd": bwd}
+
+
+STUBS = {"flash": lambda: _dense_stubs("global_attn_fwd", "global_attn_bwd", "global_attn_supported", 0),
+         "chunk_fused": lambda: _dense_stubs("sliding_chunk_attn_fwd", "sliding_chunk_attn_bwd", "sliding_chunk_attn_supported", 1),
+         "window lse": _window_lse_stubs}
+
+
+def _route(name):
+    """the stand-ins a case asks for by its name"""
+    return next((r for r in STUBS if r in name), None)
 
 
 # ---- the cases: name -> run(Fn) -> (outputs, parameters); every case draws its inputs from its own seeded generator -------------------
@@ -203,8 +264,9 @@ def vit_case(multi, dt, grad, groups=VIT_GROUPS, C=192, nH=3):
     return run
 
 
-def vil_case(split, dt, grad, C=96, nH=3, nB=2):
-    """one global token and a 4 x 4 grid of local tokens in 2 x 2 chunks; split: query | kv Linears and the dense chunk route"""
+def vil_case(split, dt, grad, C=96, nH=3, nB=2, fused=False):
+    """one global token and a 4 x 4 grid of local tokens in 2 x 2 chunks; split: query | kv Linears and the dense chunk route, or
+    with `fused` the 4-tuple that asks for the fused sliding-chunk kernels"""
     def run(Fn, arm=None):
         ops_ref.set_act_dtype(dt)
         r = _rand(11 + split)
@@ -213,6 +275,7 @@ def vil_case(split, dt, grad, C=96, nH=3, nB=2):
             q, kv = _attn_prm(r, C, 1), _attn_prm(r, C, 2)
             attn = (q[0], q[1], q[2], q[3], kv[2], kv[3])
             chunk = torch.tensor([-1] + [((i // 4 // 2) << 16) | (i % 4 // 2) for i in range(16)], dtype=torch.int32)
+            chunk = (chunk, 1, 2 * 4, 2) if fused else chunk
         else:
             attn, chunk = _attn_prm(r, C) + (None, None), None
         prm = _param(*attn, r(C, C) * C ** -0.5, 0.1 * r(C), *_mlp_prm(r, C, 4 * C))
@@ -270,8 +333,13 @@ def head_case(L, bn, stats, grad=True):
     return run
 
 
+VIT_LONG_GROUPS = ((2, 5), (1, 230))  # 5 tokens: the 64-slot windowed route; 230: beyond the windowed kernels (batched GEMM, or flash)
+VIT_LSE_GROUPS = ((2, 5), (1, 65))     # 65 tokens: the windowed route that carries a log-sum-exp
+
+
 def cases():
-    """name -> (run, wide route forced).  Names: family / shape / dtype / mode"""
+    """name -> (run, wide route forced).  Names: family / shape / dtype / mode; a name that holds a key of STUBS runs on those
+    stand-ins (_route)"""
     out = {}
     for multi in (False, True):
         fam = "swin_block_multi" if multi else "swin_block"
@@ -283,12 +351,24 @@ def cases():
         for dt in (torch.bfloat16, torch.float32):
             for grad in (True, False):
                 mode = "%s %s" % (str(dt)[6:], "grad" if grad else "no_grad")
-                out["%s C=192 %s" % ("vit_block_multi" if multi else "vit_block", mode)] = (vit_case(multi, dt, grad), False)
+                vit = "vit_block_multi" if multi else "vit_block"
+                out["%s C=192 %s" % (vit, mode)] = (vit_case(multi, dt, grad), False)
+                out["%s C=48 gemm %s" % (vit, mode)] = (vit_case(multi, dt, grad, C=48), False)  # head_dim 16: no fused kernel takes it
+                if grad:
+                    out["%s C=96 window+gemm %s" % (vit, mode)] = (vit_case(multi, dt, grad, VIT_LONG_GROUPS, C=96), False)
+                if dt == torch.bfloat16:
+                    out["%s C=96 window+flash %s" % (vit, mode)] = (vit_case(multi, dt, grad, VIT_LONG_GROUPS, C=96), False)
+                    if grad:
+                        out["%s C=96 window lse %s" % (vit, mode)] = (vit_case(multi, dt, grad, VIT_LSE_GROUPS, C=96), False)
                 out["%s %s" % ("CvtFfnMultiFn" if multi else "CvtFfnFn", mode)] = (cvt_ffn_case(multi, dt, grad), False)
                 if multi:
                     continue
                 for split in (False, True):
                     out["vil_block %s %s" % ("query|kv chunked" if split else "qkv", mode)] = (vil_case(split, dt, grad), False)
+                    if grad:  # head_dim 16: "gemm" and "chunk_gemm"
+                        out["vil_block C=48 %s %s" % ("query|kv chunked" if split else "qkv", mode)] = (vil_case(split, dt, grad, C=48), False)
+                if dt == torch.bfloat16:
+                    out["vil_block query|kv chunk_fused %s" % mode] = (vil_case(True, dt, grad, fused=True), False)
     for L in (1, 2, 3, 4):
         for bn in (False, True):
             for stats in (False, True):
@@ -303,7 +383,7 @@ def record(name, mp=None):
     own = mp is None
     mp = pytest.MonkeyPatch() if own else mp
     try:
-        s = Session(mp, Fn, wide)
+        s = Session(mp, Fn, wide, _route(name))
         run(Fn)
         return list(s.rec.trace), s
     finally:
@@ -365,6 +445,16 @@ ONE_CALL = {  # one contribution per parameter: the ragged Functions over two gr
     "vit_block": vit_case(False, torch.bfloat16, True, VIT_GROUPS[:1]),
     "vil_block qkv": vil_case(False, torch.bfloat16, True),
     "vil_block query|kv": vil_case(True, torch.bfloat16, True),
+    "vit_block_multi gemm": vit_case(True, torch.bfloat16, True, C=48),
+    "vit_block gemm": vit_case(False, torch.bfloat16, True, VIT_GROUPS[:1], C=48),
+    "vit_block_multi window+gemm": vit_case(True, torch.bfloat16, True, VIT_LONG_GROUPS, C=96),
+    "vit_block_multi window+flash": vit_case(True, torch.bfloat16, True, VIT_LONG_GROUPS, C=96),
+    "vit_block flash": vit_case(False, torch.bfloat16, True, VIT_LONG_GROUPS[1:], C=96),
+    "vit_block_multi window lse": vit_case(True, torch.bfloat16, True, VIT_LSE_GROUPS, C=96),
+    "vit_block window lse": vit_case(False, torch.bfloat16, True, VIT_LSE_GROUPS[1:], C=96),
+    "vil_block gemm qkv": vil_case(False, torch.bfloat16, True, C=48),
+    "vil_block chunk_gemm query|kv": vil_case(True, torch.bfloat16, True, C=48),
+    "vil_block query|kv chunk_fused": vil_case(True, torch.bfloat16, True, fused=True),
     "CvtFfnMultiFn": cvt_ffn_case(True, torch.bfloat16, True),
     "CvtFfnFn": cvt_ffn_case(False, torch.bfloat16, True, CVT_GROUPS[:1]),
     "dino_head L=1": head_case(1, False, False), "dino_head L=2": head_case(2, False, True), "dino_head L=3": head_case(3, False, False),
@@ -378,7 +468,7 @@ def test_every_gradient_is_written_into_its_bucket_slot(name, cpu_ops, monkeypat
     is handed its slot exactly once per backward, and the gradient autograd stores is a fresh alias of the slot"""
     import esvit_amd.functional as Fn
     import esvit_amd.params as P
-    s = Session(monkeypatch, Fn, "wide" in name)
+    s = Session(monkeypatch, Fn, "wide" in name, _route(name))
     handed, slots, g0 = {}, {}, P.grad_out
 
     def counting(p, shape2d=None):

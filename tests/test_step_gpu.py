@@ -760,7 +760,7 @@ def test_full_width_bf16_tracks_fp32_mode(arch, B):
 @pytest.mark.parametrize("arch,B,ragged", [
     pytest.param("swin_tiny_w7", 32, None, id="swin_tiny_w7-32"), pytest.param("swin_base_w14", 8, None, id="swin_base_w14-8"),
     pytest.param("deit_small", 16, None, id="deit_small-16"), pytest.param("cvt_s1", 16, None, id="cvt_s1-16"), pytest.param("vil_tiny", 16, None, id="vil_tiny-16"),
-    # one backbone pass per resolution group (SwinBlockFn, VitBlockFn) instead of the model's default route
+    # one backbone pass per resolution group (SwinBlockFn, vit_block) instead of the model's default route
     pytest.param("swin_tiny_w7", 32, False, id="swin_tiny_w7-32-per_group"), pytest.param("deit_small", 16, False, id="deit_small-16-per_group")])
 def test_weight_gradient_stream_is_bit_identical_to_inline(arch, B, ragged, lib_built):
     """functional._side_run launches the weight-gradient GEMMs of a backward node on a side stream and joins before the node returns.  The

@@ -1,5 +1,5 @@
 """Monolithic ViT backbones (models/vision_transformer.py, the reference's default --arch), CPU side: module tree,
-state_dict layout and the autograd glue (VitPatchEmbedFn / VitBlockFn / ApeAddFn / FinalNormFn) on the torch restatement of every
+state_dict layout and the autograd glue (VitPatchEmbedFn / VitBodyFn / ApeAddFn / FinalNormFn) on the torch restatement of every
 kernel, against tests/golden/nano_vit_step.pt -- produced by the REFERENCE's own VisionTransformer + DINOHead + DDINOLoss
 (oracle/gen_golden.py vit)."""
 import os

@@ -171,13 +171,13 @@ def test_small_crops_through_the_windowed_kernels(dt, shape, lib_built):
     finally:
         ops_ref.set_act_dtype(torch.float32)
     o, att = Fn.vit_attention(ops, qkv.cuda(), bqkv.cuda(), B, N, nH, hd ** -0.5, True)
-    assert len(att) == 3                                        # the windowed route was taken
+    assert att.route == "window" and att.lse is None            # the windowed route was taken: the 64-slot kernels keep no log-sum-exp
     d = Fn.vit_attention_bwd(ops, dout.cuda(), att, bqkv.cuda(), B, N, nH, hd ** -0.5)
     tol = 2e-5 if dt == torch.float32 else 2e-2
     _close("attention output (windowed route)", o, o_ref, tol)
     _close("d qkv (windowed route)", d, d_ref, tol * 2)
     long_seq = Fn.vit_attention(ops, torch.randn(2 * 230, 3 * C).to(dt).cuda(), bqkv.cuda(), 2, 230, nH, hd ** -0.5, True)[1]
-    assert len(long_seq) == 2                                   # 230 tokens: beyond the windowed kernels, the batched-GEMM route
+    assert long_seq.route == "gemm"                             # 230 tokens: beyond the windowed kernels, the batched-GEMM route
 
 
 @pytest.mark.parametrize("shape", [(3, 197, 6, 64), (2, 197, 3, 64), (5, 197, 12, 64), (2, 145, 2, 64), (2, 224, 1, 64), (2, 100, 4, 32), (3, 65, 6, 64)])
@@ -200,12 +200,12 @@ def test_large_crops_through_the_flash_kernels(shape, lib_built):
     finally:
         ops_ref.set_act_dtype(torch.float32)
     o, att = Fn.vit_attention(ops, qkv.cuda(), bqkv.cuda(), B, N, nH, hd ** -0.5, True)
-    assert len(att) == 4                                        # (qkv, out, bias fragments, log-sum-exp): the 224-slot kernels
+    assert att.route == "window" and isinstance(att.lse, torch.Tensor)  # the 224-slot kernels: the windowed route WITH a log-sum-exp
     d = Fn.vit_attention_bwd(ops, dout.cuda(), att, bqkv.cuda(), B, N, nH, hd ** -0.5)
     _close("attention output (224-slot kernels)", o, o_ref, 2e-2)
     _close("d qkv (224-slot kernels)", d, d_ref, 4e-2)
     if hd == 64:  # fp32 parity mode at head_dim 64 does not fit them: the batched-GEMM route
-        assert len(Fn.vit_attention(ops, qkv.float().cuda(), bqkv.cuda(), B, N, nH, hd ** -0.5, True)[1]) == 2
+        assert Fn.vit_attention(ops, qkv.float().cuda(), bqkv.cuda(), B, N, nH, hd ** -0.5, True)[1].route == "gemm"
 
 
 @pytest.mark.parametrize("prec", ["fp32", "bf16"])
