@@ -314,6 +314,9 @@ __global__ void region_match_kernel(const float* __restrict__ sim, int B, int S,
 
 // probe.hip: the terms = 0 mode of esvit_dino_ce_fwd_bwd
 int esvit_i_probe_ce(const float* s, const int32_t* target, const float* row_w, int64_t Rs, int K, float* row_loss, float* ds, hipStream_t stream);
+// monitor.hip: the terms = -1 mode of esvit_dino_ce_fwd_bwd
+int esvit_i_dist_stats(int dtype, const void* x, const float* center, const float* row_max, const float* row_lse, float inv_temp, int64_t R,
+                       int K, float* out, float* buf, hipStream_t stream);
 
 extern "C" int esvit_teacher_row_stats(int dtype, const void* t, const float* center, float inv_temp, int64_t R, int K,
                                        float* row_max, float* row_lse, esvit_stream_t s_) {
@@ -354,6 +357,18 @@ extern "C" int esvit_dino_ce_fwd_bwd(int dtype, const void* s, const void* t, co
         ESVIT_CHECK_ARG(s && tmatch && row_loss && (row_w || !ds) && Rs > 0 && Rs <= 0x7fffffffL && K >= 4 && K % 4 == 0,
                         "esvit_dino_ce_fwd_bwd(terms = 0): bad args (Rs=%ld, K=%d: a multiple of 4)", (long)Rs, K);
         return esvit_i_probe_ce((const float*)s, tmatch, row_w, Rs, K, row_loss, (float*)ds, stream);
+    }
+    if (terms == -1) {  // distribution statistics of softmax rows (monitor.hip): entropy, argmax, column sums of the probabilities
+        ESVIT_CHECK_ARG(!t && !t_row_max && !t_row_lse && !tmatch && !row_w && !term_w && !row_order,
+                        "esvit_dino_ce_fwd_bwd(terms = -1): row statistics take no teacher rows, teacher statistics, match table, weights or row order");
+        ESVIT_CHECK_ARG(s_row_max && s_row_lse, "esvit_dino_ce_fwd_bwd(terms = -1): the rows' (max, lse) statistics are required");
+        ESVIT_CHECK_ARG(dtype == ESVIT_BF16 || dtype == ESVIT_F32, "esvit_dino_ce_fwd_bwd(terms = -1): bad dtype");
+        ESVIT_CHECK_ARG(s && row_loss && ds && Rs > 0 && Rs <= 0x7fffffffL && K > 0 && K % 8 == 0 && K < (1 << 24) && inv_student_temp > 0.f,
+                        "esvit_dino_ce_fwd_bwd(terms = -1): bad args (Rs=%ld, K=%d: a multiple of 8 below 2^24, a positive inverse temperature)",
+                        (long)Rs, K);
+        ESVIT_CHECK_ARG(((uintptr_t)s % 16) == 0 && ((uintptr_t)ds % 16) == 0 && (!center || ((uintptr_t)center % 16) == 0),
+                        "esvit_dino_ce_fwd_bwd(terms = -1): rows, centre and buffer must be 16-byte aligned");
+        return esvit_i_dist_stats(dtype, s, center, s_row_max, s_row_lse, inv_student_temp, Rs, K, row_loss, (float*)ds, stream);
     }
     ESVIT_CHECK_ARG((s_row_max == nullptr) == (s_row_lse == nullptr) && !(s_row_max && term_w),
                     "esvit_dino_ce_fwd_bwd: student row statistics come as a (max, lse) pair, for the two-term form");

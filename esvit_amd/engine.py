@@ -283,7 +283,9 @@ def train_one_epoch(student, teacher, teacher_without_ddp, dino_loss, data_loade
     update in the optimizer's place (EsvitTrainer._scaled_update); the caller keeps checkpointing ``fp16_scaler.state_dict()``.
     `mixup_fn` (timm's Mixup or any callable (samples, targets) -> (samples, target matrix)): the crops are mixed and the
     target matrices reach the loss exactly as in main_esvit.py:515-544 (DINOLoss uses them, DDINOLoss ignores them).
-    Returns the rank-averaged epoch means the reference logs (main_esvit.py:593-600)."""
+    Returns the rank-averaged epoch means the reference logs (main_esvit.py:593-600).  A loss that carries a
+    ``monitor.TrainingMonitor`` (``dino_loss.monitor``, or ESVIT_MONITOR=<period>) adds its keys to that dict -- the caller writes
+    them to log.txt as train_<key> -- and one line is printed at every look; without one nothing changes."""
     net = student.module if hasattr(student, "module") else student
     if optimizer_rule(optimizer) is None:
         raise TypeError("esvit_amd.engine.train_one_epoch drives the optimizers of main_esvit.py:408-415 -- torch.optim.AdamW, "
@@ -305,6 +307,10 @@ def train_one_epoch(student, teacher, teacher_without_ddp, dino_loss, data_loade
     last = None
     last_look = -1  # iteration of the previous look at the loss / the refused-update counter
     win_refused = win_seen = 0  # consecutive looks in which every update was refused: refusals / updates in them
+    mon = getattr(dino_loss, "monitor", None)  # monitor.TrainingMonitor or None: health statistics beside the loss
+    mon_sums, mon_seen = {}, 0  # sums over the epoch's observed steps (host floats, filled at the looks)
+    if mon is not None:
+        mon.reset()
     for it, (images, _) in enumerate(data_loader):
         git = n_it * epoch + it
         images = [im.cuda(non_blocking=True) for im in images]
@@ -332,6 +338,13 @@ def train_one_epoch(student, teacher, teacher_without_ddp, dino_loss, data_loade
             if not math.isfinite(v):
                 print("Loss is {}, stopping training".format(v))
                 sys.exit(1)
+            if mon is not None and mon.observed:  # the means over the steps observed since the previous look (same synchronisation point)
+                n_obs, seen = mon.observed, mon.compute()
+                mon.reset()
+                for k, x in seen.items():
+                    mon_sums[k] = mon_sums.get(k, 0.0) + x * n_obs
+                mon_seen += n_obs
+                print("monitor [it %d] " % it + "  ".join("%s %.4f" % kv for kv in seen.items()))
             # a gradient overflow with a FINITE loss (bf16 backward) is refused by the update kernel too: say so, take the refused
             # updates back out of the step counts, and stop when nothing but refusals happened since the last look
             refused = tr.updater.take_skipped()
@@ -357,4 +370,15 @@ def train_one_epoch(student, teacher, teacher_without_ddp, dino_loss, data_loade
     its = range(n_it * epoch, n_it * epoch + n_it)
     lr_avg = sum(float(lr_schedule[i]) for i in its) / max(n_it, 1)
     wd_avg = sum(float(wd_schedule[i]) for i in its) / max(n_it, 1)
-    return {"loss": mean.item(), "lr": lr_avg, "wd": wd_avg}
+    stats = {"loss": mean.item(), "lr": lr_avg, "wd": wd_avg}
+    if mon is not None and mon_seen:
+        # the epoch means of the monitor's keys; over the ranks: the mean of the per-rank values (entropies of per-rank marginals, not
+        # the entropy of the global marginal) in one all-reduce
+        keys = list(mon_sums)
+        vals = [mon_sums[k] / mon_seen for k in keys]
+        if _world() > 1:
+            buf = torch.tensor(vals, dtype=torch.float64, device=dev)
+            dist.all_reduce(buf)
+            vals = (buf / _world()).tolist()
+        stats.update(zip(keys, vals))
+    return stats

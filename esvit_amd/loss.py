@@ -15,6 +15,7 @@ import torch
 import torch.distributed as dist
 import torch.nn as nn
 
+from . import monitor as _monitor
 from . import ops
 
 
@@ -148,6 +149,7 @@ class DINOLoss(_DeferredCenter, nn.Module):
         self.teacher_temp_schedule = _teacher_temp_schedule(warmup_teacher_temp, teacher_temp, warmup_teacher_temp_epochs, nepochs)
         self.assume_unit_grad = False  # set by the fused train step: loss.backward() with grad 1 needs no rescale pass
         self._tables = {}
+        self.monitor = _monitor.from_env()  # a monitor.TrainingMonitor, or None (ESVIT_MONITOR=<period>, or assign one)
 
     def _static(self, B, device):
         key = (B, str(device))
@@ -230,6 +232,7 @@ class DINOLoss(_DeferredCenter, nn.Module):
         if targets_mixup:
             tmatch, tw, off = self._mixup_terms(targets_mixup, B, s.device)
             row_loss, ds = o.dino_ce(s.detach(), t, self.center, mx, lse, tmatch, None, inv_st, inv_tt, term_w=tw)
+            w, rl_terms = tw, row_loss  # (what the monitor sees: the sparse terms, without the constant part below)
             # The constant part of the targets (label smoothing) is scored on EVERY call unless the caller declared it absent
             # (mixup_smoothing = 0.0): whether a batch carries it is not latched from the first batch -- with off = 0 the
             # term is an exact no-op that costs a handful of small launches on the mixup path only.
@@ -239,7 +242,11 @@ class DINOLoss(_DeferredCenter, nn.Module):
         else:
             tmatch, w = self._static(B, s.device)
             row_loss, ds = o.dino_ce(s.detach(), t, self.center, mx, lse, tmatch, w, inv_st, inv_tt, s_stats=s_st)
+            rl_terms = row_loss
         loss = o.sum_f32(row_loss)
+        if self.monitor is not None and self.monitor.due():  # (before update_center: the centre the statistics were taken with)
+            self.monitor.observe(o, dict(t=t, center=self.center, inv_tt=inv_tt, t_stats=(mx, lse), s=s.detach(), inv_st=inv_st, s_stats=s_st,
+                                         tmatch=tmatch, weights=w, row_loss=rl_terms, B=B))
         self.update_center(t)
         return _LossFn.apply(loss, self.assume_unit_grad, student_output, ds)
 
@@ -266,6 +273,7 @@ class DDINOLoss(_DeferredCenter, nn.Module):
         self.teacher_temp_schedule = _teacher_temp_schedule(warmup_teacher_temp, teacher_temp, warmup_teacher_temp_epochs, nepochs)
         self.assume_unit_grad = False
         self._tables = {}
+        self.monitor = _monitor.from_env()  # a monitor.TrainingMonitor, or None (ESVIT_MONITOR=<period>, or assign one)
 
     def _static(self, B, s_npatch, Tt, device):
         """index tables that depend only on (B, crop layout): crop-major <-> image-major permutations, the cls
@@ -335,6 +343,14 @@ class DDINOLoss(_DeferredCenter, nn.Module):
         _, ds_reg = o.dino_ce(s_reg_c.detach(), t_reg, self.center_grid, mx_g, lse_g, tm_reg, tb["w_reg"], inv_st, inv_tt,
                               row_loss=row_loss[n_cls:], row_order=tb["cm_row"], s_stats=st_sg)  # image-major work order: teacher rows stay cached
         loss = o.sum_f32(row_loss)
+        if self.monitor is not None and self.monitor.due():  # (before update_center: the centres the statistics were taken with)
+            self.monitor.observe(
+                o,
+                dict(t=t_cls, center=self.center, inv_tt=inv_tt, t_stats=(mx_c, lse_c), s=s_cls_c.detach(), inv_st=inv_st, s_stats=st_sc,
+                     tmatch=tb["tm_cls"], weights=tb["w_cls"], row_loss=row_loss[:n_cls], B=B),
+                dict(t=t_reg, center=self.center_grid, inv_tt=inv_tt, t_stats=(mx_g, lse_g), s=s_reg_c.detach(), inv_st=inv_st, s_stats=st_sg,
+                     tmatch=tm_reg, weights=tb["w_reg"], row_loss=row_loss[n_cls:], sim=sim, Tt=Tt, crop_id=tb["crop_id"],
+                     cm_row=tb["cm_row"], ncrops=self.ncrops))
         self.update_center(t_cls, t_reg, col_sums=(cs_tc, cs_tg))
         return _LossFn.apply(loss, self.assume_unit_grad, s_cls, s_reg, ds_cls, ds_reg)
 

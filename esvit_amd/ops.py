@@ -84,7 +84,7 @@ def relative_position_index(ws):
 # esvit_query questions (include/esvit_hip.h)
 (Q_ATTN_FRAG_ELEMS, Q_ATTN_LSE_ELEMS, Q_ATTN_BWD_PARTS, Q_ATTN_BWD_PAD_ROWS, Q_LN_BWD_BLOCKS, Q_COLSUM_BLOCKS, Q_COL_REDUCE_BLOCKS,
  Q_UPDATE_CHUNK_ELEMS, Q_MLP_FUSED, Q_AUG_MAX_BOX, Q_JPEG_WORKSPACE, Q_RESIZE_FITS, Q_CHUNK_ATTN_WS, Q_TOPK_WS, Q_PROBE_CE_REG_ROW,
- Q_GLOBAL_ATTN_WS, Q_MLP_DW_WS, Q_ATTN_BWD_FUSED_GRID, Q_PATCH_EMBED_WS) = range(1, 20)
+ Q_GLOBAL_ATTN_WS, Q_MLP_DW_WS, Q_ATTN_BWD_FUSED_GRID, Q_PATCH_EMBED_WS, Q_DIST_STATS) = range(1, 21)
 MLP_DW_PARTIAL_FLOATS = 74208  # ESVIT_MLP_DW_PARTIAL_FLOATS
 ATTN_BWD_PARTIAL_FLOATS = 37440  # ESVIT_ATTN_BWD_PARTIAL_FLOATS
 
@@ -1273,6 +1273,36 @@ def probe_ce(logits, targets, row_w, row_loss=None, want_grad=True, inplace=True
                                     _p(row_loss), _p(ds), None, None, None, _stream()),
           "dino_ce_fwd_bwd(class index)")
     return row_loss, ds
+
+
+def dist_stats_slab():
+    """rows one workgroup of dist_stats owns (its column-sum partials: one per slab)"""
+    return query(Q_DIST_STATS, 0)
+
+
+def dist_stats(x, center, inv_temp, stats, buf=None):
+    """distribution statistics of the softmax rows p = softmax((x - center) * inv_temp) (esvit_dino_ce_fwd_bwd, terms = -1): x act
+    [R, K] read once, center fp32 [K] or None, stats = (row_max, row_lse) of the rows (teacher_row_stats / rowstat_combine)
+    -> (ent fp32 [R] in nats, amax int32 [R]: lowest index of the maximum, -1 for a row with NaN / inf in it, psum fp32 [K] = sum_r p_rk).
+    buf: an fp32 tensor of query(Q_DIST_STATS, R, K) floats to work in (psum is its head), else one is allocated."""
+    x = _actc(x)
+    R, K = x.shape
+    mx, lse = stats
+    assert mx.numel() == R and lse.numel() == R and mx.dtype == lse.dtype == torch.float32 and mx.is_contiguous() and lse.is_contiguous()
+    if center is not None:
+        center = _f32c(center)
+        assert center.numel() == K
+    n = query(Q_DIST_STATS, R, K)
+    if n <= 0:
+        raise RuntimeError("esvit_query(Q_DIST_STATS) failed (%d): %s" % (n, lib.esvit_last_error().decode()))
+    if buf is None:
+        buf = torch.empty((n,), dtype=torch.float32, device=x.device)
+    assert buf.dtype == torch.float32 and buf.numel() >= n and buf.is_contiguous()
+    out = torch.empty((R, 2), dtype=torch.float32, device=x.device)
+    check(lib.esvit_dino_ce_fwd_bwd(_code(x.dtype), _p(x), None, _p(center), None, None, None, None, -1, None, float(inv_temp), 1.0, R, K,
+                                    _p(out), _p(buf), None, _p(mx), _p(lse), _stream()),
+          "dino_ce_fwd_bwd(row statistics)")
+    return out[:, 0], out[:, 1].to(torch.int32), buf[:K]
 
 
 def probe_ce_reg_row():

@@ -90,6 +90,11 @@ const char* esvit_last_error(void);
  *                                              one per 128 rows); 0 where the mode does not exist (anything but bf16, E in {96, 128, 192}).
  *                                              Needs no device (then: the size of an MI355X) */
 #define ESVIT_Q_PATCH_EMBED_WS 19
+/*   ESVIT_Q_DIST_STATS (R, K)                  the row-statistics mode of esvit_dino_ce_fwd_bwd (terms = -1).  R = 0: the slab height, the rows one
+ *                                              workgroup owns (32).  R > 0: FLOATS of the buffer the mode takes through `ds` for R rows of K
+ *                                              columns: K column sums, one partial of K floats per slab, one record of 4 floats per row and
+ *                                              block of 65536 columns: (1 + ceil(R / slab)) K + 4 R ceil(K / 65536) */
+#define ESVIT_Q_DIST_STATS 20
 int64_t esvit_query(int what, int64_t a, int64_t b, int64_t c);
 
 /* ---- host-side integer index maps (bit-exact vs reference) -------------
@@ -631,7 +636,19 @@ int esvit_region_match(const float* sim, int B, int S, int Tt, int ld, const int
  * and "among the top k" is rank < k;  ds fp32 [Rs, K] = row_w[r] (softmax(z)_j - [j == t]).  ds may be s (in place) or NULL (no
  * gradient, s untouched).  A row with a NaN / inf logit or a class outside [0, K) gives loss NaN, rank K and a NaN gradient row, and
  * leaves every other row as it would have been.  No atomics: identical launches give identical bits.  Rows of up to
- * esvit_query(ESVIT_Q_PROBE_CE_REG_ROW) floats are held in registers by one wave; longer rows take a workgroup and three sweeps. */
+ * esvit_query(ESVIT_Q_PROBE_CE_REG_ROW) floats are held in registers by one wave; longer rows take a workgroup and three sweeps.
+ *
+ * terms = -1: DISTRIBUTION STATISTICS of softmax rows (the training-health monitor, esvit_amd/monitor.py; no loss, no gradient).
+ * s dtype [Rs, K] (bf16 or fp32, K % 8 == 0, K < 2^24, 16-byte aligned): the rows; center fp32 [K] or NULL (student rows);
+ * inv_student_temp > 0: the inverse temperature; s_row_max / s_row_lse fp32 [Rs] (REQUIRED): the rows' statistics
+ * row_max = max_k z, row_lse = ln sum_k exp(z - row_max) of z = (s - center) * inv_student_temp, as esvit_teacher_row_stats /
+ * esvit_rowstat_combine give them.  t, t_row_max, t_row_lse, tmatch, row_w, term_w and row_order must be NULL; inv_teacher_temp is
+ * ignored.  With p = softmax(z):
+ *   row_loss fp32 [Rs, 2] = (H(p_r) = row_lse - sum_k p_k (z_k - row_max) in nats, the lowest index of the maximal z as a float);
+ *   ds: an fp32 buffer of esvit_query(ESVIT_Q_DIST_STATS, Rs, K) floats, 16-byte aligned, contents need not be initialised: its first K
+ *       floats receive psum[k] = sum_r p_rk, the rest is scratch (partials per slab of rows and per block of columns, folded in a fixed order).
+ * The rows are read once.  A row whose statistics or logits are NaN / inf gives H = NaN and index -1, and all K column sums are NaN;
+ * the row outputs of every other row are what they would have been.  No atomics: identical launches give identical bits. */
 int esvit_dino_ce_fwd_bwd(int dtype, const void* s, const void* t, const float* center,
                           const float* t_row_max, const float* t_row_lse, const int32_t* tmatch,
                           const float* row_w, int terms, const float* term_w, float inv_student_temp,
