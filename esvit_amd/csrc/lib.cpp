@@ -42,6 +42,7 @@ int64_t esvit_i_mlp_dw_ws(int dtype, int C, int64_t M);
 int64_t esvit_i_attn_branch_bwd_grid(int dtype, int C, int64_t windows);
 int64_t esvit_i_patch_embed_ws(int dtype, int E, int64_t M);
 int64_t esvit_i_dist_stats_ws(int64_t R, int64_t K);
+int64_t esvit_i_attn_tail_ws(int dtype, int C, int64_t M);
 
 extern "C" int64_t esvit_query(int what, int64_t a, int64_t b, int64_t c) {
     switch (what) {
@@ -65,6 +66,7 @@ extern "C" int64_t esvit_query(int what, int64_t a, int64_t b, int64_t c) {
         case ESVIT_Q_ATTN_BWD_FUSED_GRID: return esvit_i_attn_branch_bwd_grid((int)a, (int)b, c);
         case ESVIT_Q_PATCH_EMBED_WS: return esvit_i_patch_embed_ws((int)a, (int)b, c);
         case ESVIT_Q_DIST_STATS: return esvit_i_dist_stats_ws(a, b);
+        case ESVIT_Q_ATTN_TAIL_WS: return esvit_i_attn_tail_ws((int)a, (int)b, c);
     }
     esvit_set_error("esvit_query: unknown question %d", what);
     return ESVIT_ERR_ARG;

@@ -30,6 +30,7 @@
 // LDS (160 KiB): W1 72 KiB | LN(x), xhat, dy 3 x 12 KiB | dA 49 KiB (rows padded to 784 B) | row statistics and sums 1.5 KiB.
 // The [*][96] images use the 16-byte-unit XOR of fused16.h's image A (unit ^ (row >> 2) inside aligned groups of four).
 #include "common.h"
+#include "img96.h"
 #include "../../include/esvit_hip.h"
 
 namespace {
@@ -43,21 +44,11 @@ constexpr int L_W1 = 0, L_XW = L_W1 + DW_H * 192, L_XH = L_XW + DW_T * 192, L_DY
               L_ST = L_DA + DW_T * DA_ROW, L_EX = L_ST + 2 * DW_T * 4, L_END = L_EX + DW_NW * 16 * 8;
 static_assert(L_END <= 160 * 1024, "LDS budget");
 
-typedef short s16x8_ __attribute__((ext_vector_type(8)));
-
-// byte offset of channel ch of row `row` in a [rows][96] bf16 image
-__host__ __device__ constexpr int img_off(int row, int ch) {
-    const int u = ch >> 3;
-    return row * 192 + (((u & ~3) | ((u ^ (row >> 2)) & 3)) << 4) + ((ch & 7) << 1);
-}
-
-// Phases C and D address the images as a lane-dependent base plus a compile-time constant that goes into the 16-bit offset field of
-// the LDS instruction: a phase C trip forms its five bases (6 integer instructions, 77 before), phase D advances its seven bases once
-// per six k-steps.  The XOR of img_off sees (row >> 2) & 3 and the low two bits of the
-// 16-byte unit only, hence:  16 rows further is +3072 bytes;  32 channels further is +64 bytes;  of a 16-channel step only its parity
+// Phases C and D address the images (img96.h) as a lane-dependent base plus a compile-time constant that goes into the 16-bit offset
+// field of the LDS instruction: a phase C trip forms its five bases (6 integer instructions, 77 before), phase D advances its seven
+// bases once per six k-steps.  16 rows further is IMG_ROWS16 bytes, 32 channels further IMG_CH32; of a 16-channel step only its parity
 // reaches the XOR (two bases, 32 bytes apart under XOR);  in phase D, where a transpose read's rows step by 4, the second row of a
 // pair has a base of its own and 32 rows further is +6144.  The images lie a constant apart, so one base serves all of them.
-constexpr int IMG_ROWS16 = 16 * 192, IMG_CH32 = 64;
 constexpr bool img_immediates_hold() {
     for (int c = 0; c < 16; ++c)
         for (int g = 0; g < 4; ++g) {
@@ -87,16 +78,6 @@ static_assert(img_immediates_hold(), "base + immediate addressing of the [*][96]
 __device__ __forceinline__ f32x4 mfma(bf16x8 a, bf16x8 b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0); }
 __device__ __forceinline__ void mfma_acc(const bf16x8& a, const bf16x8& b, f32x4& c) {
     c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
-}
-
-// two transpose reads: element j / 4 + j of the result is image[row0 + j][col + (lane & 15)] / image[row1 + j][..] when lo / hi
-// are the addresses of (row0 / row1 + ((lane & 15) >> 2), col + 4 * (lane & 3)) (mfma.h: frag_ks, frag_v_perm)
-__device__ __forceinline__ bf16x8 tr_pair(const char* lo_p, const char* hi_p) {
-    typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
-    const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)lo_p);
-    const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)hi_p);
-    const s16x8_ both = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-    return __builtin_bit_cast(bf16x8, both);
 }
 
 // the L phase's share of one tile: 12 channels of x and gy of token (t >> 3) and the token's DropPath factor; rows past M read row M - 1

@@ -640,6 +640,10 @@ extern "C" int esvit_layernorm_fwd(int dtype, const float* x, const float* gamma
 
 int esvit_i_ln_bwd_blocks(long rows, int C) { return ln_bwd_nblk(rows, C); }  // esvit_query
 
+int esvit_i_attn_tail_bwd(int dtype, const void* dqkv, const float* x, const float* mean, const float* rstd, const float* gamma, const float* g_in,
+                          int64_t rows, int C, float* dx, float* dgamma, float* dbeta, float* ws, const esvit_ln_qkv_tail* tail, int tokens, void* dx_act,
+                          int act_dtype, const float* rowscale, int rows_per_sample, hipStream_t stream);  // attn_tail_bwd.hip
+
 // dx_act (optional) = cast(rowscale[row / rows_per_sample] * dx): the DropPath-scaled, activation-dtype gradient the following
 // dgrad / wgrad GEMMs read (otherwise a separate esvit_gather_cast pass over dx)
 extern "C" int esvit_layernorm_bwd(int dtype, const void* dy, const float* x, const float* mean, const float* rstd,
@@ -648,6 +652,9 @@ extern "C" int esvit_layernorm_bwd(int dtype, const void* dy, const float* x, co
                                    int period_in, void* dx_act, int act_dtype, const float* rowscale, int rows_per_sample,
                                    esvit_stream_t s_) {
     hipStream_t stream = reinterpret_cast<hipStream_t>(s_);
+    if (period_in == ESVIT_LN_BWD_QKV_TAIL)  // (dy is dqkv and `rowmap` the record of the mode's further operands)
+        return esvit_i_attn_tail_bwd(dtype, dy, x, mean, rstd, gamma, g_in, rows, C, dx, dgamma, dbeta, ws, reinterpret_cast<const esvit_ln_qkv_tail*>(rowmap),
+                                     tokens, dx_act, act_dtype, rowscale, rows_per_sample, stream);
     ESVIT_CHECK_ARG(dy && x && mean && rstd && gamma && (dx || dx_act) && dgamma && dbeta && ws && rows > 0,
                     "esvit_layernorm_bwd: bad args");
     if (rowmap) ESVIT_CHECK_ARG(tokens > 0 && period_in > 0, "esvit_layernorm_bwd: bad rowmap geometry");

@@ -240,6 +240,29 @@ def _attn_bwd_fused(o, dt, C, nH, geoms, sizes):
             and all(o.attn_branch_bwd_supported(dt, C, nH, g.N, r, w) for g, (r, w) in zip(geoms, sizes)))
 
 
+# stage 0 (bf16, C = 96): what follows the window-attention backward has no window structure -- qkv data gradient, qkv weight gradient
+# (on the side stream) and norm1's backward, 32 B per token-channel in four launches.  ops.attn_tail_bwd is the three in one pass over
+# the rows (18 - 20 B), with LayerNorm(x) recomputed from the saved statistics.  "0": A-B runs.
+ATTN_TAIL_FUSED = os.environ.get("ESVIT_ATTN_TAIL_FUSED", "1") != "0"
+
+
+def _attn_tail_fused(o, dt, C):
+    return ATTN_TAIL_FUSED and hasattr(o, "attn_tail_bwd") and o.attn_tail_bwd_supported(dt, C)
+
+
+def _attn_tail_bwd(o, dqkv, X, mean1, rstd1, g1, Wqkv, gx1, pads, params, rowscale, rows_per_sample, want_act):
+    """-> (gx, gx act copy or None, dg1, db1, dWqkv, dbqkv), the gradients in their bucket slots; pads: the window-attention backward's
+    zero-pad slabs, whose column sums are the rest of the k / v bias gradient; params: (norm1.weight, norm1.bias, qkv.weight, qkv.bias)"""
+    g1_p, b1_p, Wqkv_p, bqkv_p = params
+    C = X.shape[1]
+    wsink, bsink, ln1 = P.grad_out(Wqkv_p), P.grad_out(bqkv_p), _ln_sinks(g1_p, b1_p)
+    gx, gxb, dWqkv, dbqkv, dg1, db1 = o.attn_tail_bwd(dqkv, X, mean1, rstd1, g1, b1_p.detach(), Wqkv, gx1, rowscale=rowscale if want_act else None,
+                                                      rows_per_sample=rows_per_sample, want_act=want_act, out=wsink, db_out=bsink, gb_out=ln1)
+    for dpad_ws in pads:
+        o.colsum(dpad_ws, out=dbqkv[C:], accumulate=True)  # k/v bias gradient from the zero-pad slots (behind the reduce, same stream)
+    return gx, gxb, _alias(dg1, ln1), _alias(db1, ln1), _alias(dWqkv, wsink), _alias(dbqkv, bsink)
+
+
 def _attn_bwd_w(o, Wqkv_p, Wproj_p, Wqkv):
     """the bf16 copies the backward mode reads: the plain cast of qkv.weight (the copy every GEMM uses), its transpose and the transpose of
     proj.weight (ops.cast_weight), cached per parameter version like _perm_w"""
@@ -522,6 +545,11 @@ class SwinBlockFn(torch.autograd.Function):
         tsink = P.grad_out(table_p)
         dtable = _alias(o.relpos_bias_bwd(dbias_ws, s.index, geom.N, s.table.shape[0], out=tsink, accumulate=False if tsink is not None else None,
                                           **_relpos_kw(o)), tsink)
+        if _attn_tail_fused(o, s.Wqkv.dtype, C):
+            gx, _, dg1, db1, dWqkv, dbqkv = _attn_tail_bwd(o, dqkv, x.view(M, C), s.mean1, s.rstd1, g1, s.Wqkv, gx1, (dpad_ws,),
+                                                           (g1_p, b1_p, Wqkv_p, bqkv_p), None, 1, False)
+            _side_join()
+            return (gx.view(nB, L, C), None, None, None, None, dg1, db1, dtable, dWqkv, dbqkv, dWproj, dbproj, dg2, db2, dW1, dbfc1, dW2, dbfc2)
         wsink, bsink = P.grad_out(Wqkv_p), P.grad_out(bqkv_p)
 
         def wqkv():
@@ -692,6 +720,11 @@ class SwinBlockMultiFn(torch.autograd.Function):
             pads.append(dpad_ws)
         dtable = o.relpos_bias_bwd(dbuf, index, N, table.shape[0], out=tsink, accumulate=False if tsink is not None else None, **_relpos_kw(o))
         dtable = _alias(dtable, tsink)
+        if _attn_tail_fused(o, Wqkv.dtype, C):  # (the previous block's operand rides along with dL/dX when it has a reader)
+            gx, gxb, dg1, db1, dWqkv, dbqkv = _attn_tail_bwd(o, dqkv, X, s.mean1, s.rstd1, g1, Wqkv, gx1, pads, (g1_p, b1_p, Wqkv_p, bqkv_p),
+                                                             ctx.prev_scale, 1, ctx.emit_shadow)
+            _side_join()
+            return (gx, gxb, None, None, None, None, None, None, None, dg1, db1, dtable, dWqkv, dbqkv, dWproj, dbproj, dg2, db2, dW1, dbfc1, dW2, dbfc2)
         wsink, bsink = P.grad_out(Wqkv_p), P.grad_out(bqkv_p)
 
         def wqkv():
@@ -721,6 +754,9 @@ def swin_block_multi(X, segs, nH, index, dp_rows, prm_list, shadow=None, prev_sc
     (_block_forward_multi)"""
     if torch.is_grad_enabled() and (X.requires_grad or any(p.requires_grad for p in prm_list)):
         y, ysh, xw, mean, rstd = SwinBlockMultiFn.apply(X, shadow, segs, nH, index, dp_rows, prev_scale, pre, next_norm, *prm_list)
+        w1 = _weight(prm_list[9])
+        if _mlp_fused_train(w1, X.shape[1]) and _mlp_dw_onchip(ops_module(), w1, X.shape[1]):
+            ysh = None  # (this block's MLP backward scales and casts dL/dy itself: nobody would read the copy its successor wrote)
         return y, ysh, (None if xw is None else (xw, mean, rstd))
     g1, b1, table, Wqkv, bqkv, Wproj, bproj, g2, b2, W1, bfc1, W2, bfc2 = prm_list
     wts = (_weight(Wqkv), _weight(Wproj), _weight(W1), _weight(W2))

@@ -84,9 +84,11 @@ def relative_position_index(ws):
 # esvit_query questions (include/esvit_hip.h)
 (Q_ATTN_FRAG_ELEMS, Q_ATTN_LSE_ELEMS, Q_ATTN_BWD_PARTS, Q_ATTN_BWD_PAD_ROWS, Q_LN_BWD_BLOCKS, Q_COLSUM_BLOCKS, Q_COL_REDUCE_BLOCKS,
  Q_UPDATE_CHUNK_ELEMS, Q_MLP_FUSED, Q_AUG_MAX_BOX, Q_JPEG_WORKSPACE, Q_RESIZE_FITS, Q_CHUNK_ATTN_WS, Q_TOPK_WS, Q_PROBE_CE_REG_ROW,
- Q_GLOBAL_ATTN_WS, Q_MLP_DW_WS, Q_ATTN_BWD_FUSED_GRID, Q_PATCH_EMBED_WS, Q_DIST_STATS) = range(1, 21)
+ Q_GLOBAL_ATTN_WS, Q_MLP_DW_WS, Q_ATTN_BWD_FUSED_GRID, Q_PATCH_EMBED_WS, Q_DIST_STATS, Q_ATTN_TAIL_WS) = range(1, 22)
 MLP_DW_PARTIAL_FLOATS = 74208  # ESVIT_MLP_DW_PARTIAL_FLOATS
 ATTN_BWD_PARTIAL_FLOATS = 37440  # ESVIT_ATTN_BWD_PARTIAL_FLOATS
+ATTN_TAIL_PARTIAL_FLOATS = 28128  # ESVIT_ATTN_TAIL_PARTIAL_FLOATS
+LN_BWD_QKV_TAIL = -1  # ESVIT_LN_BWD_QKV_TAIL
 
 
 def query(what, a=0, b=0, c=0):
@@ -608,6 +610,52 @@ def layernorm_bwd_to_act(dy, x, mean, rstd, gamma, *, gb_out=None):
     check(lib.esvit_layernorm_bwd(_code(dy.dtype), _p(dy), _p(x), _p(mean), _p(rstd), _p(gamma), None, rows, Cc, None, _p(dgamma),
                                   _p(dbeta), _p(ws), None, 0, 0, _p(dxa), _code(dxa.dtype), None, 0, _stream()), "layernorm_bwd(to act)")
     return dxa, dgamma, dbeta
+
+
+class LnQkvTail(C.Structure):
+    """esvit_ln_qkv_tail (include/esvit_hip.h)"""
+    _fields_ = [(n, C.c_void_p) for n in ("Wqkv", "beta", "dWqkv", "dbqkv")]
+
+
+def attn_tail_bwd_supported(dt, Cc):
+    """the qkv-tail mode of esvit_layernorm_bwd exists at this dtype and width (bf16, C = 96)"""
+    return dt in (torch.float32, torch.bfloat16) and query(Q_ATTN_TAIL_WS, _code(dt), int(Cc), 1) > 0
+
+
+def attn_tail_bwd_grid(dt, Cc, M):
+    """workgroups (= partials, = the summation order) of attn_tail_bwd for M rows on the current device"""
+    return query(Q_ATTN_TAIL_WS, _code(dt), int(Cc), int(M)) // (4 * ATTN_TAIL_PARTIAL_FLOATS)
+
+
+def attn_tail_bwd(dqkv, x, mean, rstd, gamma, beta, Wqkv, g_in, *, rowscale=None, rows_per_sample=0, want_act=False, out=None, db_out=None,
+                  gb_out=None):
+    """the tail of a Swin block's attention-branch backward in one pass over the rows: qkv data gradient, qkv weight and bias gradient and
+    norm1's backward.  dqkv act [M, 3C], x fp32 [M, C] (the block input), mean / rstd of norm1, Wqkv act [3C, C] (the plain cast),
+    g_in fp32 [M, C] = dL/dx1 -> (gx fp32 [M, C], gx_act = cast(rowscale * gx) or None, dWqkv fp32 [3C, C], dbqkv fp32 [3C], dgamma,
+    dbeta).  out / db_out / gb_out: the fp32 tensors to write dWqkv / dbqkv / (dgamma, dbeta) to (gradient-bucket slots)"""
+    dqkv, x, g_in, Wqkv = _actc(dqkv), _f32c(x), _f32c(g_in), _actc(Wqkv)
+    M, Cc = x.shape
+    dt, dev = dqkv.dtype, x.device
+    assert dqkv.shape == (M, 3 * Cc) and Wqkv.shape == (3 * Cc, Cc) and Wqkv.dtype == dt and g_in.shape == x.shape
+    assert mean.shape == (M,) and rstd.shape == (M,)
+    nbytes = query(Q_ATTN_TAIL_WS, _code(dt), Cc, M)
+    if nbytes <= 0:
+        raise RuntimeError("attn_tail_bwd: no qkv-tail mode at dtype %s, C = %d" % (dt, Cc))
+    dW = out if out is not None else torch.empty((3 * Cc, Cc), dtype=torch.float32, device=dev)
+    db = db_out if db_out is not None else torch.empty((3 * Cc,), dtype=torch.float32, device=dev)
+    assert dW.shape == (3 * Cc, Cc) and db.shape == (3 * Cc,)
+    dgamma, dbeta = _ln_grad_outs(Cc, dev, gb_out)
+    gx = torch.empty_like(x)
+    gxa = torch.empty((M, Cc), dtype=dt, device=dev) if want_act else None
+    assert rowscale is None or want_act
+    # (a tensor of its own, not the shared scratch: the partials are larger than the scratch's floor, and growing that for good would
+    # change what every later caller of the slot finds)
+    ws = torch.empty((nbytes // 4,), dtype=torch.float32, device=dev)
+    rec = LnQkvTail(_p(Wqkv).value, _p(_f32c(beta)).value, _p(_f32c(dW)).value, _p(_f32c(db)).value)
+    check(lib.esvit_layernorm_bwd(_code(dt), _p(dqkv), _p(x), _p(_f32c(mean)), _p(_f32c(rstd)), _p(_f32c(gamma)), _p(g_in), M, Cc, _p(gx), _p(dgamma),
+                                  _p(dbeta), _p(ws), C.cast(C.pointer(rec), C.c_void_p), 0, LN_BWD_QKV_TAIL, _p(gxa), _code(dt) if want_act else 0,
+                                  _p(rowscale), rows_per_sample, _stream()), "layernorm_bwd(qkv tail)")
+    return gx, gxa, dW, db, dgamma, dbeta
 
 
 MERGE_LN_PAD = True  # merge_ln_fwd / merge_ln_bwd take pad=True: odd grids padded inside the kernel (ESVIT_MERGE_PAD, include/esvit_hip.h)

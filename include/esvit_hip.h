@@ -95,6 +95,12 @@ const char* esvit_last_error(void);
  *                                              columns: K column sums, one partial of K floats per slab, one record of 4 floats per row and
  *                                              block of 65536 columns: (1 + ceil(R / slab)) K + 4 R ceil(K / 65536) */
 #define ESVIT_Q_DIST_STATS 20
+/*   ESVIT_Q_ATTN_TAIL_WS (dtype, C, M)         BYTES of the partial records of esvit_layernorm_bwd's qkv-tail mode for M rows: one partial of
+ *                                              ESVIT_ATTN_TAIL_PARTIAL_FLOATS floats per workgroup of the launch (one per CU, at most one per
+ *                                              64 rows); 0 where the mode does not exist (anything but bf16, C = 96).  Needs no device (then:
+ *                                              the size of an MI355X) */
+#define ESVIT_Q_ATTN_TAIL_WS 21
+#define ESVIT_ATTN_TAIL_PARTIAL_FLOATS 28128 /* dWqkv 288 x 96 + dbqkv 288 + dgamma 96 + dbeta 96 */
 int64_t esvit_query(int what, int64_t a, int64_t b, int64_t c);
 
 /* ---- host-side integer index maps (bit-exact vs reference) -------------
@@ -283,7 +289,24 @@ int esvit_layernorm_fwd(int dtype, const float* x, const float* gamma, const flo
  * dx_act (optional, un-mapped rows only) = rowscale[row / rows_per_sample] * dx: the DropPath-scaled copy the next dgrad / wgrad
  * GEMMs of the backward read (rowscale may be NULL = 1) -- saves one esvit_gather_cast pass.  act_dtype: its dtype -- `dtype`, or
  * ESVIT_BF16 while dy is fp32 (the patch-embedding norm, whose upstream gradient is the fp32 residual-stream gradient).  dx may be NULL
- * when dx_act is given (only the copy is wanted; g_in must then be NULL). */
+ * when dx_act is given (only the copy is wanted; g_in must then be NULL).
+ *
+ * qkv-tail mode (period_in == ESVIT_LN_BWD_QKV_TAIL; bf16, C = 96): the tail of a Swin block's attention-branch backward in one
+ * persistent kernel and an index-ordered reduce.  dy is then dqkv bf16 [rows, 3C], the gradient of qkv = LayerNorm(x) Wqkv^T + bqkv,
+ * and `rowmap` points at an esvit_ln_qkv_tail record instead of a row map (tokens = 0).  The call forms dxw = bf16(dqkv Wqkv) per
+ * 64-row tile on the chip, applies the LayerNorm backward to it (dx = g_in + LN'(dxw), dx_act, dgamma, dbeta as above; dx and g_in
+ * are required) and accumulates dWqkv = dqkv^T LayerNorm(x) [3C, C] and dbqkv = colsum(dqkv) [3C] beside it, LayerNorm(x) recomputed
+ * from x, mean, rstd, gamma and the record's beta with the forward's expression and rounded to bf16 as the forward's output is.  ws:
+ * esvit_query(ESVIT_Q_ATTN_TAIL_WS, dtype, C, rows) bytes, 16-byte aligned; workgroup b walks tiles b, b + grid, ... and writes
+ * partial b, the reduce sums the partials in index order and OVERWRITES dWqkv, dbqkv, dgamma, dbeta (no atomics: identical launches
+ * give identical bits).  Any other dtype or width returns ESVIT_ERR_ARG before any launch. */
+#define ESVIT_LN_BWD_QKV_TAIL (-1)
+typedef struct esvit_ln_qkv_tail {
+    const void* Wqkv;   /* bf16 [3C, C]: the plain cast of qkv.weight, 16-byte aligned */
+    const float* beta;  /* fp32 [C] */
+    float* dWqkv;       /* fp32 [3C, C] out */
+    float* dbqkv;       /* fp32 [3C] out */
+} esvit_ln_qkv_tail;
 int esvit_layernorm_bwd(int dtype, const void* dy, const float* x, const float* mean, const float* rstd,
                         const float* gamma, const float* g_in, int64_t rows, int C, float* dx,
                         float* dgamma, float* dbeta, float* ws, const int32_t* rowmap, int tokens,

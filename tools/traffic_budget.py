@@ -12,7 +12,7 @@ tok_t = [B * 2 * 3136 // 4 ** s for s in range(4)]               # teacher rows 
 # bytes per token-channel, current dataflow (DESIGN.md 12 lists the tensors behind every number)
 attn_fwd_s = [18, 28, 32, 32]     # stage 0: fused kernel with side outputs; stage 1: unfused, LayerNorm output from the previous fused MLP; 2-3: unfused
 attn_fwd_t = [8, 8, 32, 32]       # stages 0-1: fused kernel
-attn_bwd_s = [54, 54, 54, 54]
+attn_bwd_s = [40, 54, 54, 54]     # stage 0: qkv data / weight gradient and norm1's backward in one pass (esvit_layernorm_bwd's qkv-tail mode: 18 in place of 32)
 mlp_fwd_s = [8, 10, 40, 40]       # stages 0-1: fused; 2-3: LayerNorm + fc1 (GELU output and pre-activation) + fc2
 mlp_fwd_t = [8, 8, 32, 32]
 mlp_bwd_s = [52, 52, 64, 64]      # stages 0-1: fused data-gradient kernel + the hidden-sized operands of the two weight-gradient GEMMs
