@@ -1856,14 +1856,17 @@ def _chunk_grid(chunk, N):
     return tab, int(nglo), nx, ny, int(w)
 
 
-def sliding_chunk_attn_fwd(qkv, B, N, nH, scale, chunk):
+def sliding_chunk_attn_fwd(qkv, B, N, nH, scale, chunk, out=None):
     """Vision Longformer's sliding-chunk attention in one set of fused kernels: qkv [B * N, 3C] (tokens [globals | (x, y) row-major])
-    -> (out [B * N, C], saved = (qkv, out, lse fp32 [B, nH, N])).  chunk = (table, nglo, tokens per chunk row) as MsViT._stage builds it."""
+    -> (out [B * N, C], saved = (qkv, out, lse fp32 [B, nH, N])).  chunk = (table, nglo, tokens per chunk row) as MsViT._stage builds it.
+    out: optional destination whose first B * N rows are written."""
     qkv = _actc(qkv)
     tab, nglo, nx, ny, w = _chunk_grid(chunk, N)
     Cc = qkv.shape[1] // 3
     assert qkv.shape[0] == B * N
-    out = torch.empty((B * N, Cc), dtype=qkv.dtype, device=qkv.device)
+    if out is None:
+        out = torch.empty((B * N, Cc), dtype=qkv.dtype, device=qkv.device)
+    assert out.dtype == qkv.dtype and out.is_contiguous() and out.shape[0] >= B * N and out.shape[1] == Cc
     lse = torch.empty((B, nH, N), dtype=torch.float32, device=qkv.device)
     ws = workspace(query(Q_CHUNK_ATTN_WS, B * nH, N, 0), qkv.device, slot=3)
     check(lib.esvit_window_attn_fwd(_code(qkv.dtype), _p(qkv), None, _p(tab), N, None, w | ATTN_SLIDING_CHUNK, _p(ws), None, nx, B, ny, nH, Cc // nH,
@@ -1871,14 +1874,17 @@ def sliding_chunk_attn_fwd(qkv, B, N, nH, scale, chunk):
     return out, (qkv, out, lse)
 
 
-def sliding_chunk_attn_bwd(dout, saved, B, N, nH, scale, chunk):
-    """gradient of sliding_chunk_attn_fwd with respect to qkv: dout [B * N, C] -> dqkv [B * N, 3C]"""
+def sliding_chunk_attn_bwd(dout, saved, B, N, nH, scale, chunk, dqkv=None):
+    """gradient of sliding_chunk_attn_fwd with respect to qkv: dout [B * N, C] -> dqkv [B * N, 3C] (dqkv: optional destination whose
+    first B * N rows are written)"""
     qkv, out, lse = saved
     dout = _actc(dout)
     tab, nglo, nx, ny, w = _chunk_grid(chunk, N)
     Cc = qkv.shape[1] // 3
-    assert dout.shape == out.shape and dout.dtype == qkv.dtype
-    dqkv = torch.empty_like(qkv)
+    assert dout.shape == (B * N, Cc) and out.shape[0] >= B * N and dout.dtype == qkv.dtype
+    if dqkv is None:
+        dqkv = torch.empty_like(qkv)
+    assert dqkv.dtype == qkv.dtype and dqkv.is_contiguous() and dqkv.shape[0] >= B * N and dqkv.shape[1] == 3 * Cc
     ws = workspace(query(Q_CHUNK_ATTN_WS, B * nH, N, 1), qkv.device, slot=3)
     check(lib.esvit_window_attn_bwd(_code(qkv.dtype), _p(qkv), None, _p(tab), N, _p(dout), _p(out), _p(lse), None, w | ATTN_SLIDING_CHUNK, _p(ws), None,
                                     nx, B, ny, nH, Cc // nH, float(scale), _p(dqkv), None, None, _stream()), "window_attn_bwd(sliding chunk)")
