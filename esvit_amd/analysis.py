@@ -7,7 +7,10 @@ block in one backbone pass.  The reference loops over images at batch size 1 bec
 block.  Swin backbones have two routes (SWIN_STATS): "maps", the default, keeps the window maps of `forward_selfattention` and reduces
 them in torch; "fused" takes the statistics mode of the window kernels (csrc/window_attn.hip, window_attn_big.hip,
 ops.window_attn_stats) block by block in one backbone pass and forms no map.  `swin_attention_rows` puts the attention of
-chosen pixel positions back on the token grid of any block.  Plotting, the two augmented views and the per-head ordering of the figures
+chosen pixel positions back on the token grid of any block.  A Vision Longformer (MsViT) goes block pair by block pair in one backbone
+pass: its sliding-chunk stages through the statistics mode of the fused per-chunk kernels (csrc/chunk_attn.hip, ops.chunk_attn_stats;
+DESIGN §11), its full-attention stages through the flash statistics, so no L x L tensor exists where the kernels support the shape;
+`vil_attention_rows` returns the attention of pixel positions or global tokens on each stage's grid.  Plotting, the two augmented views and the per-head ordering of the figures
 stay with the caller."""
 import math
 import os
@@ -16,6 +19,7 @@ import torch
 
 from . import functional as Fn
 from .models.swin_transformer import SwinTransformer, _grid, _hw_of
+from .models.vision_longformer import Long2DSCSelfAttention, MsViT, _pair_params
 from .models.vision_transformer import VisionTransformer
 
 _LOG2E = 1.0 / math.log(2.0)
@@ -90,6 +94,33 @@ def _swin_block_stats(model, images, blocks, slots_of=None):
     return out
 
 
+def _vil_block_stats(model, images, blocks, queries_of=None):
+    """one backbone pass under no_grad that walks the stages as MsViT._stage does and stops after the last chosen block pair: per chosen
+    pair (flat index over all stages) the statistics call on the pair's input, then the pair's ordinary forward -> {pair: (entropy, rows,
+    (nglo, nx, ny))}.  queries_of(pair index, stage, tokens) -> the listed query tokens of that pair, or None.  While it advances the
+    pass asks for the fused chunk route (the fourth `chunk` entry) and the flash forward: no L x L tensor where the kernels exist"""
+    want, out, i = set(blocks), {}, 0
+    with torch.no_grad(), Fn._long_attention("flash"):
+        nB, _, H, W = images.shape
+        src, nchw = images, True
+        for li, (layer, cfg) in enumerate(zip(model._layers(), model.layer_cfgs)):
+            x, nx, ny = layer[0](src, nB, H, W, nchw)
+            sparse = isinstance(layer[1].attn, Long2DSCSelfAttention)
+            chunk = (model._chunk_table(cfg['g'], nx, ny, cfg['f'], x.device), cfg['g'], cfg['f'] * ny, cfg['f']) if sparse else None
+            for b in range(1, len(layer), 2):
+                prm = _pair_params(layer[b], layer[b + 1])
+                if i in want:
+                    q = None if queries_of is None else queries_of(i, li, x.shape[1])
+                    ent, rows = Fn.vil_block_attention_stats(x, cfg['h'], chunk, prm, q)
+                    out[i] = (ent, rows, (cfg['g'], nx, ny))
+                if i == max(want):
+                    return out
+                x = Fn.vil_block(x, cfg['h'], None, chunk, prm)
+                i += 1
+            src, H, W, nchw = x[:, cfg['g']:].contiguous(), nx, ny, False
+    return out
+
+
 def attention_entropy(model, images, queries=None, unit="bits"):
     """Shannon entropy of the attention distribution of every query token, block by block.
 
@@ -97,7 +128,10 @@ def attention_entropy(model, images, queries=None, unit="bits"):
     token).  One backbone pass without gradients; the entropy is accumulated beside the running softmax statistics, no N x N tensor
     exists at any point.  SwinTransformer: -> a list with one tensor [B * nW, nH, ws^2] (or [..., len(queries)]) per block, from the
     window maps of `forward_selfattention(images, n=2)`; `swin_window_to_grid` puts such a tensor back on the token grid of its block
-    (`model.feature_grid(H, W)` lists the grids).  Any other backbone: TypeError.
+    (`model.feature_grid(H, W)` lists the grids).  MsViT (Vision Longformer): -> a list with one tensor [B, nH_l, N_l] (or
+    [..., len(queries)], the indices checked against every pair's N_l) per (AttnBlock, MlpBlock) pair over all stages, tokens in the
+    order [globals | grid row-major] (`vil_tokens_to_grid` splits such a tensor; `model.feature_grid(H, W)` lists (nglo, nx, ny)); a
+    local token's entropy is over the keys it sees.  Any other backbone: TypeError.
 
     unit: "bits" (the reference's log2) or "nats".  Convention 0 log 0 = 0: a probability that underflowed to zero contributes nothing.
     The reference's `(-p * torch.log2(p)).sum(-1)` (analyze_models.py:116-135) evaluates 0 * -inf there and returns NaN for the row.
@@ -135,8 +169,17 @@ def attention_entropy(model, images, queries=None, unit="bits"):
                 e = e.index_select(2, _query_index(queries, e.shape[2], e.device))
             out.append(e * k if k != 1.0 else e)
         return out
-    raise TypeError("attention_entropy: VisionTransformer and SwinTransformer backbones only, not %s (its attention is neither one global "
-                    "softmax per image nor Swin's window maps)" % type(model).__name__)
+    if isinstance(model, MsViT):
+        stats = _vil_block_stats(model, images, range(model.depth))
+        out = []
+        for i in range(model.depth):
+            e = stats[i][0]
+            if queries is not None:
+                e = e.index_select(2, _query_index(queries, e.shape[2], e.device))
+            out.append(e * k if k != 1.0 else e)
+        return out
+    raise TypeError("attention_entropy: VisionTransformer and SwinTransformer backbones (and MsViT) only, not %s (its attention is neither "
+                    "one global softmax per image, nor Swin's window maps, nor Vision Longformer's sliding chunks)" % type(model).__name__)
 
 
 def swin_window_to_grid(values, H, W, window, shift):
@@ -221,6 +264,68 @@ def swin_attention_rows(model, images, points, blocks=None):
     return out
 
 
+def vil_tokens_to_grid(values, nglo, nx, ny):
+    """a per-token tensor of one Vision Longformer stage, [..., nglo + nx * ny] in the order [globals | grid row-major] (the entropies of
+    `attention_entropy`, a probability row), split as `vil_attention_rows` returns it -> (grid [..., nx, ny], glob [..., nglo])"""
+    nglo, nx, ny = int(nglo), int(nx), int(ny)
+    if values.dim() < 1 or values.shape[-1] != nglo + nx * ny:
+        raise ValueError("vil_tokens_to_grid: expected [..., %d] for %d global tokens and a %d x %d grid, got %s"
+                         % (nglo + nx * ny, nglo, nx, ny, tuple(values.shape)))
+    return values[..., nglo:].reshape(*values.shape[:-1], nx, ny), values[..., :nglo]
+
+
+def vil_attention_rows(model, images, points, blocks=None):
+    """what the `points` attend to in the chosen block pairs of an MsViT, on each stage's own token grid.  A point is a pixel position
+    (y, x) -- in stage l the token (y // s_l, x // s_l), s_l the product of the stage patch sizes, of the grid
+    model.feature_grid(H, W)[l]; a position outside it is a ValueError -- or an int g: global token g of the block's stage (a stage
+    without it: ValueError).  blocks: flat pair indices over all stages, negatives allowed (default: the last pair).  One backbone pass
+    that stops after the last chosen pair; no L x L tensor is formed where the kernels have their statistics modes.
+    -> one (rows, glob) pair per chosen block, in the given order: rows fp32 [B, nH, nq, nx_l, ny_l], the probabilities on the stage's
+    grid (zero outside the query's neighbourhood in a sliding-chunk stage), and glob fp32 [B, nH, nq, nglo_l], those on the stage's
+    global tokens: rows.sum((-1, -2)) + glob.sum(-1) = 1.  attention_mass_masks(rows.flatten(-2)) thresholds them.
+    images: a batch of any (H, W), or a list of batches -> a list of results."""
+    if isinstance(images, (list, tuple)):
+        return [vil_attention_rows(model, im, points, blocks) for im in images]
+    if not isinstance(model, MsViT):
+        raise TypeError("vil_attention_rows: MsViT backbones only, not %s" % type(model).__name__)
+    pts = [int(p) if isinstance(p, int) or (torch.is_tensor(p) and p.dim() == 0) else (int(p[0]), int(p[1])) for p in points]
+    if not pts:
+        raise ValueError("vil_attention_rows: at least one point")
+    stage_of = [li for li, cfg in enumerate(model.layer_cfgs) for _ in range(cfg['n'])]
+    depth = len(stage_of)
+    chosen = [depth - 1] if blocks is None else [int(b) for b in blocks]
+    if not chosen or any(not -depth <= b < depth for b in chosen):
+        raise ValueError("vil_attention_rows: block indices must lie in [%d, %d), got %r" % (-depth, depth, chosen))
+    chosen = [b % depth for b in chosen]
+    grids = model.feature_grid(images.shape[2], images.shape[3])
+    tokens, s = {}, 1
+    for li, cfg in enumerate(model.layer_cfgs):
+        s *= cfg['p']
+        if li not in set(stage_of[b] for b in chosen):
+            continue
+        nglo, nx, ny = grids[li]
+        tok = []
+        for p in pts:
+            if isinstance(p, int):
+                if not 0 <= p < nglo:
+                    raise ValueError("vil_attention_rows: stage %d has %d global tokens, no global token %d" % (li, nglo, p))
+                tok.append(p)
+            else:
+                y, x = p
+                if not (0 <= y // s < nx and 0 <= x // s < ny):
+                    raise ValueError("vil_attention_rows: point (%d, %d) lies outside the %d x %d token grid of stage %d (cell side %d)"
+                                     % (y, x, nx, ny, li, s))
+                tok.append(nglo + (y // s) * ny + x // s)
+        tokens[li] = tok
+    stats = _vil_block_stats(model, images, chosen, lambda i, li, N: tokens[li])
+    out = []
+    for b in chosen:
+        _, rows, (nglo, nx, ny) = stats[b]
+        assert (nglo, nx, ny) == tuple(grids[stage_of[b]]), ((nglo, nx, ny), grids[stage_of[b]])
+        out.append(vil_tokens_to_grid(rows, nglo, nx, ny))
+    return out
+
+
 def attention_mass_masks(rows, threshold=0.6):
     """the thresholded masks of analyze_models.py:168-176 for any batch of attention rows [..., N]: sort each row ascending, normalise it
     to sum 1, and keep the entries whose cumulative sum exceeds 1 - threshold (the largest entries, holding `threshold` of the mass)
@@ -249,6 +354,7 @@ class AttentionEntropyMeter:
             return self
         ent = attention_entropy(model, images, queries, self.unit)
         if isinstance(ent, list):  # Swin: a window is a sample of its block; the heads differ from stage to stage -> a list per block
+            # (MsViT: one row per image; mean(0) * B is the sum over the images)
             per = [e.double().mean(-1).mean(0) * images.shape[0] for e in ent]
             self.total = per if self.total is None else [a + b for a, b in zip(self.total, per)]
         else:

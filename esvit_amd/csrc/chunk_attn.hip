@@ -18,6 +18,9 @@
 //                   chunk_bwd_global_part / _combine  dK, dV of the global keys from all L queries and dQ of the global queries
 //                                        from all L keys, per 512-token range on the VALU, summed in range order.
 //                   Every output row is written by exactly one workgroup: no atomics, bit-reproducible launch to launch.
+//   statistics      ws | ESVIT_ATTN_SLIDING_CHUNK | ESVIT_ATTN_CHUNK_STATS: the entropy of every softmax row (chunk_stats_local: the local
+//                   forward up to its probabilities, K only; chunk_stats_global_part / _combine: the range-split global rows without
+//                   the V loop) and the probability rows of a few listed queries over all L tokens (chunk_stats_rows, VALU).
 //
 // Q, K, V and dO enter the MFMAs as the bf16 values they are and the scale multiplies the fp32 scores: scaling Q in LDS, as
 // window_attn_big.hip does, rounds scale * q to bf16 again (2^-9 relative for head dims 32 and 48, whose scale is no power of two),
@@ -639,13 +642,238 @@ __global__ __launch_bounds__(64) void chunk_bwd_global_combine_kernel(const floa
     }
 }
 
+// -------------------------------------------------------------------------------------------------------------
+// attention statistics (ws | ESVIT_ATTN_SLIDING_CHUNK | ESVIT_ATTN_CHUNK_STATS): what an attention analysis reads, without P and without V
+// -------------------------------------------------------------------------------------------------------------
+// entropy of the local queries' softmax rows, in nats: chunk_fwd_local_kernel up to its probabilities -- the same staging of K by slot,
+// the same 28 score tiles, scale, dead-slot value, maximum and exponentials -- and beside sum = sum_k e^(s_k - m) the second reduction
+// us = sum_k e^(s_k - m) (s_k - m), across the tile's lanes as the forward reduces sum.  H = ln sum - us / sum: sum >= 1 (the maximum's
+// own term is e^0) and us <= 0, both terms are >= 0 and nothing cancels.  A dead slot has e = exp(-1e30 - m) = 0 and adds an exact
+// (signed) zero to both.  No V image, no P V, no out: LDS 42 KB (hd 32) / 74 KB (hd 48, 64).
+template <int HD>
+__global__ __launch_bounds__(NTHR) void chunk_stats_local_kernel(const bf16* __restrict__ qkv, ChunkGeom gm, int L, int nH, float scale,
+                                                                 float* __restrict__ ent) {
+    using Cfg = CCfg<HD>;
+    constexpr int LDQ = Cfg::LDQ, KS = Cfg::KS;
+    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+    int* nbtok = reinterpret_cast<int*>(smem_raw);
+    int* owntok = nbtok + NBS;
+    bf16* Ks = reinterpret_cast<bf16*>(owntok + OWS);
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int c = lane & 15, g = lane >> 4;
+    bf16* Qs = Ks + Cfg::FULL + wave * Cfg::TILE;
+
+    const Unit u = unit_of(blockIdx.x, gm, nH);
+    const int C = nH * HD;
+    const long tok_base = (long)u.b * L;
+    const bf16* src = qkv + u.h * HD;
+
+    fill_tables(nbtok, owntok, gm, u.cr, u.cc);
+    __syncthreads();
+    {
+        RowStage<NBS, NTHR, HD> sk;
+        RowStage<16, 64, HD> sq;
+        sk.load(src + C, 3L * C, nbtok, tok_base, threadIdx.x);
+        sq.load(src, 3L * C, owntok + 16 * wave, tok_base, lane);
+        sk.store(Ks, threadIdx.x);
+        sq.store(Qs, lane);
+    }
+    __syncthreads();  // K complete; everything below is private to the wave
+    if (!tile_live(owntok, wave, lane)) return;
+
+    Frag<bf16> qf[KS];
+#pragma unroll
+    for (int ks = 0; ks < KS; ++ks) qf[ks] = frag_kc<bf16>(Qs, LDQ, 0, 32 * ks, c, g);
+    f32x4 p[NBT];
+    float m = -3.0e38f;
+#pragma unroll
+    for (int i = 0; i < NBT; ++i) {
+        f32x4 s = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int ks = 0; ks < KS; ++ks) mma(frag_kc<bf16>(Ks, LDQ, 16 * i, 32 * ks, c, g), qf[ks], s);
+        const i32x4 tk = *reinterpret_cast<const i32x4*>(nbtok + 16 * i + 4 * g);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            s[r] = tk[r] >= 0 ? s[r] * scale : -1.0e30f;
+            m = fmaxf(m, s[r]);
+        }
+        p[i] = s;
+    }
+    m = fmaxf(m, __shfl_xor(m, 16, 64));
+    m = fmaxf(m, __shfl_xor(m, 32, 64));
+    float sum = 0.f, us = 0.f;
+#pragma unroll
+    for (int i = 0; i < NBT; ++i)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const float d = p[i][r] - m;
+            const float e = __expf(d);  // a dead slot: exp(-1e30 - m) = 0, 0 * -1e30 = -0
+            sum += e;
+            us += e * d;
+        }
+    sum += __shfl_xor(sum, 16, 64);
+    sum += __shfl_xor(sum, 32, 64);
+    us += __shfl_xor(us, 16, 64);
+    us += __shfl_xor(us, 32, 64);
+    const int tok = owntok[16 * wave + c];
+    if (g == 0 && tok >= 0) ent[(long)u.z * L + tok] = __logf(sum) - us / sum;
+}
+
+// the global queries: per 512-key range (m_r, l_r = sum e^(s - m_r), T_r = sum e^(s - m_r)(s - m_r)) per global query, scores as
+// chunk_fwd_global_part_kernel forms them, no V loop
+constexpr int STAT_PART = GMAX * 3;  // per (z, range): [GMAX][max | sum | T]  (<= FWD_PART: the forward's scratch suffices)
+static_assert(STAT_PART <= FWD_PART, "the statistics partials must fit the forward's scratch");
+
+template <int HD>
+__global__ __launch_bounds__(NTHR) void chunk_stats_global_part_kernel(const bf16* __restrict__ qkv, int nglo, int L, int nH, float scale,
+                                                                       int nsplit, float* __restrict__ part) {
+    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+    typedef float row64[64];
+    typedef float rowsp[GSPLIT];
+    row64* qg = reinterpret_cast<row64*>(smem_raw);   // scale * q of the global queries
+    rowsp* sc = reinterpret_cast<rowsp*>(qg + GMAX);  // scores of this range
+    float* scratch = reinterpret_cast<float*>(sc + GMAX);
+    const int sp = blockIdx.x, z = blockIdx.y;
+    const int b = z / nH, h = z % nH, C = nH * HD;
+    const long tok_base = (long)b * L;
+    const int t0 = sp * GSPLIT, cnt = min(GSPLIT, L - t0);
+    load_global_rows(qg, qkv, tok_base, 3 * C, h * HD, HD, nglo, scale);
+    __syncthreads();
+    float mx[GMAX], sm[GMAX], tt[GMAX];
+#pragma unroll
+    for (int r = 0; r < GMAX; ++r) mx[r] = -3.0e38f;
+#pragma unroll 1
+    for (int jj = threadIdx.x; jj < cnt; jj += NTHR) {
+        float s[GMAX];
+        row_dots<HD>(qkv + (tok_base + t0 + jj) * 3L * C + C + h * HD, qg, nglo, s);
+#pragma unroll
+        for (int r = 0; r < GMAX; ++r) {
+            sc[r][jj] = s[r];
+            mx[r] = fmaxf(mx[r], s[r]);
+        }
+    }
+#pragma unroll
+    for (int r = 0; r < GMAX; ++r) {
+        mx[r] = block_max<NTHR>(mx[r], scratch);
+        sm[r] = 0.f;
+        tt[r] = 0.f;
+    }
+#pragma unroll 1
+    for (int jj = threadIdx.x; jj < cnt; jj += NTHR) {  // (a thread re-reads the entries it wrote)
+#pragma unroll
+        for (int r = 0; r < GMAX; ++r) {
+            const float d = sc[r][jj] - mx[r];
+            const float pe = r < nglo ? __expf(d) : 0.f;
+            sm[r] += pe;
+            tt[r] += pe * d;
+        }
+    }
+#pragma unroll
+    for (int r = 0; r < GMAX; ++r) {
+        sm[r] = block_sum<NTHR>(sm[r], scratch);
+        tt[r] = block_sum<NTHR>(tt[r], scratch);
+    }
+    if (threadIdx.x == 0) {
+        float* pw = part + ((long)z * nsplit + sp) * STAT_PART;
+#pragma unroll
+        for (int r = 0; r < GMAX; ++r) {
+            pw[r * 3 + 0] = mx[r];
+            pw[r * 3 + 1] = sm[r];
+            pw[r * 3 + 2] = tt[r];
+        }
+    }
+}
+
+// the ranges merged in range order: with M the row's maximum and w_r = e^(m_r - M), l = sum w_r l_r and T = sum w_r (T_r + (m_r - M) l_r)
+// (every term e^(s - m_r)(s - m_r) of range r becomes w_r e^(s - m_r)((s - m_r) + (m_r - M))); H = ln l - T / l.  An underflowed w_r is
+// 0 and multiplies finite numbers: it contributes an exact zero.  One thread per (image, head, global query).
+__global__ __launch_bounds__(64) void chunk_stats_global_combine_kernel(const float* __restrict__ part, int nglo, int L, int nsplit,
+                                                                        float* __restrict__ ent) {
+    const int z = blockIdx.x, r = threadIdx.x;
+    if (r >= nglo) return;
+    const float* pz = part + (long)z * nsplit * STAT_PART + r * 3;
+    float M = -3.0e38f;
+    for (int sp = 0; sp < nsplit; ++sp) M = fmaxf(M, pz[(long)sp * STAT_PART]);
+    float l = 0.f, T = 0.f;
+    for (int sp = 0; sp < nsplit; ++sp) {  // range order: the same sum in every launch
+        const float dm = pz[(long)sp * STAT_PART] - M, lr = pz[(long)sp * STAT_PART + 1], Tr = pz[(long)sp * STAT_PART + 2];
+        const float wgt = __expf(dm);
+        l += wgt * lr;
+        T += wgt * (Tr + dm * lr);
+    }
+    ent[(long)z * L + r] = __logf(l) - T / l;
+}
+
+// probability rows of the listed queries: one workgroup per (image, head, listed query) walks ALL L keys on the VALU.  A key the query
+// does not see (chunk_geom.h's neighbourhood in closed form: a local query sees the globals and the tokens whose chunk differs from its
+// own by at most one in both directions; a global query sees everything) gets an exact 0; a key it sees gets its score in the first
+// sweep, which the same thread replaces by e^(s - m) / l in the second (every element of the row has one writing thread; m and l are
+// the row's own maximum and sum).  A listed index outside [0, L) is skipped: its row stays unwritten, nothing is read.
+template <int HD>
+__global__ __launch_bounds__(NTHR) void chunk_stats_rows_kernel(const bf16* __restrict__ qkv, const int32_t* __restrict__ qidx, int nq,
+                                                                ChunkGeom gm, int L, int nH, float scale, float* __restrict__ rows) {
+    __shared__ float qs[64];
+    __shared__ float scratch[WAVES];
+    const int j = blockIdx.x, z = blockIdx.y;
+    const int t = qidx[j];
+    if (t < 0 || t >= L) return;  // (uniform over the workgroup)
+    const int b = z / nH, h = z % nH, C = nH * HD;
+    const long tok_base = (long)b * L;
+    if (threadIdx.x < 64) qs[threadIdx.x] = threadIdx.x < HD ? scale * (float)qkv[(tok_base + t) * 3L * C + h * HD + threadIdx.x] : 0.f;
+    __syncthreads();
+    const int nglo = gm.nglo;
+    const bool qglob = t < nglo;
+    const int qcx = qglob ? 0 : ((t - nglo) / gm.ny) / gm.w, qcy = qglob ? 0 : ((t - nglo) % gm.ny) / gm.w;
+    float* row = rows + ((long)z * nq + j) * L;
+    float m = -3.0e38f;
+#pragma unroll 1
+    for (int k = threadIdx.x; k < L; k += NTHR) {
+        bool see = qglob || k < nglo;
+        if (!see) {
+            const int dx = ((k - nglo) / gm.ny) / gm.w - qcx, dy = ((k - nglo) % gm.ny) / gm.w - qcy;
+            see = dx >= -1 && dx <= 1 && dy >= -1 && dy <= 1;
+        }
+        float s = 0.f;
+        if (see) {
+            const bf16* krow = qkv + (tok_base + k) * 3L * C + C + h * HD;
+#pragma unroll
+            for (int dv = 0; dv < HD / 8; ++dv) {
+                const bf16x8 x = *reinterpret_cast<const bf16x8*>(krow + dv * 8);
+#pragma unroll
+                for (int e = 0; e < 8; ++e) s += (float)x[e] * qs[dv * 8 + e];
+            }
+            m = fmaxf(m, s);
+        }
+        row[k] = s;
+    }
+    m = block_max<NTHR>(m, scratch);
+    float l = 0.f;
+#pragma unroll 1
+    for (int k = threadIdx.x; k < L; k += NTHR) {  // (a thread re-reads the entries it wrote)
+        bool see = qglob || k < nglo;
+        if (!see) {
+            const int dx = ((k - nglo) / gm.ny) / gm.w - qcx, dy = ((k - nglo) % gm.ny) / gm.w - qcy;
+            see = dx >= -1 && dx <= 1 && dy >= -1 && dy <= 1;
+        }
+        if (see) {
+            const float e = __expf(row[k] - m);
+            row[k] = e;
+            l += e;
+        }
+    }
+    l = block_sum<NTHR>(l, scratch);
+#pragma unroll 1
+    for (int k = threadIdx.x; k < L; k += NTHR) row[k] = row[k] / l;  // (l >= 1: the maximum's own term; an unseen key stays 0)
+}
+
 template <int HD>
 size_t local_lds(int per_wave_tiles, bool stats) {
     using Cfg = CCfg<HD>;
     return (size_t)(NBS + OWS) * 4 + (stats ? 2 * NBS * 4 : 0) + (size_t)(2 * Cfg::FULL + WAVES * per_wave_tiles * Cfg::TILE) * 2;
 }
 constexpr size_t FWD_GLOBAL_LDS = (size_t)(GMAX * 64 + GMAX * GSPLIT + WAVES * GMAX * 64 + WAVES) * 4;
-constexpr size_t BWD_GLOBAL_LDS = (size_t)(4 * GMAX * 64 + 3 * GMAX * GSPLIT + WAVES * GMAX * 64) * 4;
+constexpr size_t STATS_GLOBAL_LDS = (size_t)(GMAX * 64 + GMAX * GSPLIT + WAVES) * 4;
+constexpr size_t BWD_GLOBAL_LDS =(size_t)(4 * GMAX * 64 + 3 * GMAX * GSPLIT + WAVES * GMAX * 64) * 4;
 
 inline int nsplit_of(int L) { return (L + GSPLIT - 1) / GSPLIT; }
 
@@ -665,6 +893,32 @@ int fwd_launch(const bf16* qkv, const ChunkGeom& gm, int L, int nB, int nH, floa
         ESVIT_CHECK_LAUNCH("window_attn_fwd(sliding chunk, global rows)");
         hipLaunchKernelGGL(chunk_fwd_global_combine_kernel<HD>, dim3(Z, gm.nglo), dim3(64), 0, stream, ws, gm.nglo, L, nH, nsplit, out, lse);
         ESVIT_CHECK_LAUNCH("window_attn_fwd(sliding chunk, global rows combine)");
+    }
+    return ESVIT_OK;
+}
+
+template <int HD>
+int stats_launch(const bf16* qkv, const ChunkGeom& gm, int L, int nB, int nH, float scale, const int32_t* qidx, int nq, float* ent, float* rows,
+                 float* ws, hipStream_t stream) {
+    using Cfg = CCfg<HD>;
+    const int Z = nB * nH, nsplit = nsplit_of(L);
+    {
+        auto kern = chunk_stats_local_kernel<HD>;
+        const size_t lds = (size_t)(NBS + OWS) * 4 + (size_t)(Cfg::FULL + WAVES * Cfg::TILE) * 2;
+        static unsigned long long raised = 0;
+        esvit_raise_lds(kern, (int)lds, raised);
+        hipLaunchKernelGGL(kern, dim3(Z * cg_chunks(gm)), dim3(NTHR), lds, stream, qkv, gm, L, nH, scale, ent);
+        ESVIT_CHECK_LAUNCH("window_attn_fwd(sliding chunk stats, local)");
+    }
+    if (gm.nglo > 0) {
+        hipLaunchKernelGGL(chunk_stats_global_part_kernel<HD>, dim3(nsplit, Z), dim3(NTHR), STATS_GLOBAL_LDS, stream, qkv, gm.nglo, L, nH, scale, nsplit, ws);
+        ESVIT_CHECK_LAUNCH("window_attn_fwd(sliding chunk stats, global rows)");
+        hipLaunchKernelGGL(chunk_stats_global_combine_kernel, dim3(Z), dim3(64), 0, stream, (const float*)ws, gm.nglo, L, nsplit, ent);
+        ESVIT_CHECK_LAUNCH("window_attn_fwd(sliding chunk stats, global rows combine)");
+    }
+    if (nq > 0) {
+        hipLaunchKernelGGL(chunk_stats_rows_kernel<HD>, dim3(nq, Z), dim3(NTHR), 0, stream, qkv, qidx, nq, gm, L, nH, scale, rows);
+        ESVIT_CHECK_LAUNCH("window_attn_fwd(sliding chunk stats, listed rows)");
     }
     return ESVIT_OK;
 }
@@ -755,4 +1009,38 @@ int esvit_chunk_attn_bwd(int dtype, const void* qkv, const int32_t* chunk_table,
     if (hd == 32) return bwd_launch<32>((const bf16*)qkv, (const bf16*)dout, (const bf16*)fwd_out, lse, gm, L, nB, nH, scale, (bf16*)dqkv, scratch, stream);
     if (hd == 48) return bwd_launch<48>((const bf16*)qkv, (const bf16*)dout, (const bf16*)fwd_out, lse, gm, L, nB, nH, scale, (bf16*)dqkv, scratch, stream);
     return bwd_launch<64>((const bf16*)qkv, (const bf16*)dout, (const bf16*)fwd_out, lse, gm, L, nB, nH, scale, (bf16*)dqkv, scratch, stream);
+}
+
+// the statistics mode of the forward entry (ws | ESVIT_ATTN_SLIDING_CHUNK | ESVIT_ATTN_CHUNK_STATS, include/esvit_hip.h): every check
+// before any launch.  ws arrives with all its flags; forward_entry = false: the call came through esvit_window_attn_bwd
+int esvit_chunk_attn_stats(bool forward_entry, int dtype, const void* qkv, const float* qkv_bias, const int32_t* chunk_table, int L,
+                           const float* rel_table, int ws, float* scratch, const int32_t* region_ids, int nx, int nB, int Nq, int nH, int hd,
+                           float scale, const void* out, float* lse, float* attn_out, hipStream_t stream) {
+    const char* who = "esvit_window_attn_fwd (sliding chunk stats)";
+    ESVIT_CHECK_ARG(forward_entry, "esvit_window_attn_bwd: ESVIT_ATTN_CHUNK_STATS is valid in esvit_window_attn_fwd only (ws = 0x%x)", (unsigned)ws);
+    ESVIT_CHECK_ARG(!(ws & ESVIT_ATTN_GLOBAL), "%s: ESVIT_ATTN_CHUNK_STATS together with ESVIT_ATTN_GLOBAL (ws = 0x%x)", who, (unsigned)ws);
+    ESVIT_CHECK_ARG(!(ws & ESVIT_ATTN_STATS), "%s: ESVIT_ATTN_CHUNK_STATS together with ESVIT_ATTN_STATS (ws = 0x%x)", who, (unsigned)ws);
+    ESVIT_CHECK_ARG(!(ws & ESVIT_ATTN_WINDOW_STATS), "%s: ESVIT_ATTN_CHUNK_STATS together with ESVIT_ATTN_WINDOW_STATS (ws = 0x%x)", who, (unsigned)ws);
+    ESVIT_CHECK_ARG(!(ws & ESVIT_ATTN_SPLIT_DBIAS), "%s: ESVIT_ATTN_CHUNK_STATS together with ESVIT_ATTN_SPLIT_DBIAS (ws = 0x%x)", who, (unsigned)ws);
+    ESVIT_CHECK_ARG(ws & ESVIT_ATTN_SLIDING_CHUNK, "%s: ESVIT_ATTN_CHUNK_STATS is a mode of the sliding-chunk forward, ESVIT_ATTN_SLIDING_CHUNK is missing (ws = 0x%x)",
+                    who, (unsigned)ws);
+    ws &= ~(ESVIT_ATTN_SLIDING_CHUNK | ESVIT_ATTN_CHUNK_STATS);
+    ESVIT_CHECK_ARG(Nq > 0, "%s: N = ny | nq << 16 must be positive (got %d)", who, Nq);
+    const int ny = Nq & 0xffff, nq = Nq >> 16;
+    int nglo = 0;
+    const int rc = check_mode(who, dtype, L, ws, nx, ny, nB, nH, hd, &nglo);
+    if (rc != ESVIT_OK) return rc;
+    ESVIT_CHECK_ARG(qkv && chunk_table && scratch, "%s: qkv, the chunk table and the scratch are required", who);
+    ESVIT_CHECK_ARG(!qkv_bias && !rel_table && !region_ids, "%s: qkv_bias, rel_table and region_ids are not used, pass NULL", who);
+    ESVIT_CHECK_ARG(attn_out != nullptr, "%s: attn_out (the entropies, fp32 [nB, nH, L]) is required", who);
+    ESVIT_CHECK_ARG(nq == 0 || out != nullptr, "%s: nq = %d listed queries without the list (out: int32 [nq] on the device)", who, nq);
+    ESVIT_CHECK_ARG(nq == 0 || lse != nullptr, "%s: nq = %d listed queries without the rows output (lse: fp32 [nB, nH, nq, L])", who, nq);
+    ESVIT_CHECK_ARG(nq > 0 || !out, "%s: out must be NULL when no query is listed (nq = 0)", who);
+    ESVIT_CHECK_ARG(nq > 0 || !lse, "%s: lse must be NULL when no query is listed (nq = 0)", who);
+    ESVIT_CHECK_ARG((long)nB * nH <= 65535, "%s: nB * nH = %ld exceeds the 65535 rows of a launch grid", who, (long)nB * nH);
+    const ChunkGeom gm = cg_make(nglo, nx, ny, ws);
+    const int32_t* qidx = static_cast<const int32_t*>(out);
+    if (hd == 32) return stats_launch<32>((const bf16*)qkv, gm, L, nB, nH, scale, qidx, nq, attn_out, lse, scratch, stream);
+    if (hd == 48) return stats_launch<48>((const bf16*)qkv, gm, L, nB, nH, scale, qidx, nq, attn_out, lse, scratch, stream);
+    return stats_launch<64>((const bf16*)qkv, gm, L, nB, nH, scale, qidx, nq, attn_out, lse, scratch, stream);
 }

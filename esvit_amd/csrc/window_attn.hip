@@ -978,6 +978,9 @@ int esvit_chunk_attn_fwd(int dtype, const void* qkv, const int32_t* chunk_table,
                          int hd, float scale, void* out, float* lse, float* attn_out, hipStream_t stream);
 int esvit_chunk_attn_bwd(int dtype, const void* qkv, const int32_t* chunk_table, int L, const void* dout, const void* fwd_out, const float* lse,
                          int ws, float* scratch, int nx, int nB, int ny, int nH, int hd, float scale, void* dqkv, hipStream_t stream);
+int esvit_chunk_attn_stats(bool forward_entry, int dtype, const void* qkv, const float* qkv_bias, const int32_t* chunk_table, int L,
+                           const float* rel_table, int ws, float* scratch, const int32_t* region_ids, int nx, int nB, int Nq, int nH, int hd,
+                           float scale, const void* out, float* lse, float* attn_out, hipStream_t stream);
 
 // the global mode (flash_attn.hip)
 int esvit_flash_attn_fwd(int dtype, const void* qkv, int L, int ws, int nW, int nB, int N, int nH, int hd, float scale, void* out, float* lse,
@@ -1057,6 +1060,9 @@ extern "C" int esvit_window_attn_fwd(int dtype, const void* qkv, const float* qk
                                      const float* rel_table, int ws, float* bias_frag_ws, const int32_t* region_ids, int nW, int nB, int N,
                                      int nH, int hd, float scale, void* out, float* lse, float* attn_out, esvit_stream_t s_) {
     STREAM(s_);
+    if (ws > 0 && (ws & ESVIT_ATTN_CHUNK_STATS))  // entropy and listed rows of the sliding-chunk softmax
+        return esvit_chunk_attn_stats(true, dtype, qkv, qkv_bias, win2tok, L, rel_table, ws, bias_frag_ws, region_ids, nW, nB, N, nH, hd, scale, out,
+                                      lse, attn_out, stream);
     if (ws > 0 && (ws & ESVIT_ATTN_WINDOW_STATS))  // entropy and listed rows of the window softmax
         return window_attn_stats(dtype, qkv, qkv_bias, win2tok, L, rel_table, ws, bias_frag_ws, region_ids, nW, nB, N, nH, hd, scale, out, lse,
                                  attn_out, stream);
@@ -1101,6 +1107,9 @@ extern "C" int esvit_window_attn_bwd(int dtype, const void* qkv, const float* qk
                                      const int32_t* region_ids, int nW, int nB, int N, int nH, int hd, float scale, void* dqkv,
                                      float* dbias_ws, float* dpad_ws, esvit_stream_t s_) {
     STREAM(s_);
+    if (ws > 0 && (ws & ESVIT_ATTN_CHUNK_STATS))  // refused: a mode of the forward entry
+        return esvit_chunk_attn_stats(false, dtype, qkv, qkv_bias, win2tok, L, rel_table, ws, bias_frag_ws, region_ids, nW, nB, N, nH, hd, scale,
+                                      nullptr, nullptr, nullptr, stream);
     ESVIT_CHECK_ARG(!(ws > 0 && (ws & ESVIT_ATTN_WINDOW_STATS)),
                     "esvit_window_attn_bwd: ESVIT_ATTN_WINDOW_STATS is valid in esvit_window_attn_fwd only (ws = 0x%x)", (unsigned)ws);
     ESVIT_CHECK_ARG(!(ws > 0 && (ws & ESVIT_ATTN_STATS)) || (ws & ESVIT_ATTN_GLOBAL),

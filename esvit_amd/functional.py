@@ -2342,6 +2342,27 @@ class _long_attention:
 _STATS_SLICE_ELEMS = 1 << 26  # fall-back route: at most this many probabilities (256 MB in fp32) at a time
 
 
+def _dense_attention_stats(o, who, qkv, nB, N, nH, scale, queries, fp32=False, **route):
+    """the fall-back of the statistics: P of o.vit_attn_fwd(..., **route) for a slice of the batch at a time, reduced in torch.  fp32: the
+    slice's qkv enters the route as fp32, so that scores and P are not rounded to bf16 on the way to an fp32 result"""
+    idx = None
+    if queries is not None:
+        idx = torch.as_tensor(queries, device=qkv.device).reshape(-1).long()
+        if idx.numel() and not (0 <= int(idx.min()) and int(idx.max()) < N):
+            raise ValueError("%s: query indices must lie in [0, %d)" % (who, N))
+    step = max(1, _STATS_SLICE_ELEMS // (nH * N * N))
+    ents, rows = [], []
+    for b0 in range(0, nB, step):
+        nb = min(step, nB - b0)
+        part = qkv[b0 * N:(b0 + nb) * N]
+        p = o.vit_attn_fwd(part.float() if fp32 else part, nb, N, nH, scale, **route)[1][-1]
+        p = p.reshape(nb, nH, p.shape[-2], p.shape[-1])[:, :, :N, :N].float()
+        ents.append(torch.special.entr(p).sum(-1))
+        if idx is not None:
+            rows.append(p.index_select(2, idx))
+    return torch.cat(ents), (torch.cat(rows) if idx is not None else None)
+
+
 def vit_attention_stats(o, qkv, nB, N, nH, scale, queries=None):
     """what an attention analysis reads of a block's softmax(scale q k^T), qkv [nB * N, 3C] -> (entropy fp32 [nB, nH, N] in nats with
     0 log 0 = 0, rows fp32 [nB, nH, nq, N] of the listed query tokens or None).  The kernels of flash_attn.hip never form P; the
@@ -2350,21 +2371,7 @@ def vit_attention_stats(o, qkv, nB, N, nH, scale, queries=None):
     if _vit_stats_route(o, hd, qkv.dtype):
         ent, rows, _ = o.global_attn_stats(qkv, nB, N, nH, scale, queries=queries)
         return ent, rows
-    idx = None
-    if queries is not None:
-        idx = torch.as_tensor(queries, device=qkv.device).reshape(-1).long()
-        if idx.numel() and not (0 <= int(idx.min()) and int(idx.max()) < N):
-            raise ValueError("vit_attention_stats: query indices must lie in [0, %d)" % N)
-    step = max(1, _STATS_SLICE_ELEMS // (nH * N * N))
-    ents, rows = [], []
-    for b0 in range(0, nB, step):
-        nb = min(step, nB - b0)
-        p = o.vit_attn_fwd(qkv[b0 * N:(b0 + nb) * N], nb, N, nH, scale)[1][-1]
-        p = p.reshape(nb, nH, p.shape[-2], p.shape[-1])[:, :, :N, :N].float()
-        ents.append(torch.special.entr(p).sum(-1))
-        if idx is not None:
-            rows.append(p.index_select(2, idx))
-    return torch.cat(ents), (torch.cat(rows) if idx is not None else None)
+    return _dense_attention_stats(o, "vit_attention_stats", qkv, nB, N, nH, scale, queries)
 
 
 def vit_block_attention_stats(x, nH, prm_list, queries=None):
@@ -2387,3 +2394,51 @@ def vil_block(x, nH, dp, chunk, prm_list):
     inference pass keeps the unfused MLP branch at every width"""
     nB, N, C = x.shape
     return _vit_body(x.contiguous().view(nB * N, C), ((0, nB, N),), N, nH, dp, chunk, False, prm_list).view(nB, N, C)
+
+
+def _vil_stats_route(o, chunk, dtype, hd):
+    """do the statistics of a sliding-chunk stage take the kernels of chunk_attn.hip (ops.chunk_attn_stats)?  When the ops module has the
+    entry and supports the shape; an ops module without it (the CPU restatement, oracle/ops_ref.py) or an unsupported shape (fp32 parity
+    mode, other head dims or chunk sides) reduces P of the dense route."""
+    if not hasattr(o, "chunk_attn_stats") or not isinstance(chunk, tuple) or len(chunk) < 3:
+        return False
+    sup = getattr(o, "chunk_attn_stats_supported", None)
+    w = chunk[3] if len(chunk) > 3 else getattr(o, "CHUNK_W", 7)
+    return sup is not None and bool(sup(dtype, hd, w, chunk[1]))
+
+
+def vil_attention_stats(o, qkv, nB, N, nH, scale, chunk, queries=None):
+    """what an attention analysis reads of a sliding-chunk block's softmax, qkv [nB * N, 3C] (tokens [globals | (x, y) row-major]) ->
+    (entropy fp32 [nB, nH, N] in nats with 0 log 0 = 0, every row over the keys it sees; rows fp32 [nB, nH, nq, N] of the listed query
+    tokens over all N tokens, zero where the query does not see, or None).  chunk: (table, nglo, tokens per chunk row[, w]).  The
+    kernels of chunk_attn.hip never form P; the fall-back forms P of o.vit_attn_fwd(..., chunk=) for a slice of the batch at a time
+    and reduces it in torch.  It runs that route in fp32 whatever the activation dtype: the kernels keep scores and probabilities in
+    fp32, and the dense route in bf16 rounds both (2^-8 relative each; 0.015 - 0.027 nats in the entropy at the stage shapes), so the
+    two routes of this function would otherwise return different numbers for the same block depending on the shape alone."""
+    hd = qkv.shape[1] // 3 // nH
+    if _vil_stats_route(o, chunk, qkv.dtype, hd):
+        return o.chunk_attn_stats(qkv, nB, N, nH, scale, chunk, queries=queries)
+    return _dense_attention_stats(o, "vil_attention_stats", qkv, nB, N, nH, scale, queries, fp32=True, chunk=_chunk3(chunk))
+
+
+def _vil_block_qkv(o, x, nH, prm_list):
+    """LayerNorm and the `query | kv` (sliding-chunk stages) or `qkv` (full stages) projection of a block pair recomputed on its input
+    x fp32 [nB, N, C], as _vit_body_fwd forms them -> (qkv, nB, N, scale)"""
+    g1, b1, Wq_p, bq, Wkv_p, bkv = prm_list[:6]
+    nB, N, C = x.shape
+    xw = o.layernorm_fwd(x.contiguous().view(nB * N, C), g1, b1, LN_EPS)[0]
+    if Wkv_p is None:
+        qkv = o.linear_fwd(xw, _weight(Wq_p), bq)
+    else:
+        qkv = torch.cat((o.linear_fwd(xw, _weight(Wq_p), bq), o.linear_fwd(xw, _weight(Wkv_p), bkv)), dim=1)
+    return qkv, nB, N, (C // nH) ** -0.5
+
+
+def vil_block_attention_stats(x, nH, chunk, prm_list, queries=None):
+    """the statistics of a Vision Longformer block pair's attention on its input x fp32 [nB, N, C]; prm_list and chunk as vil_block takes
+    them (chunk = None: a full-attention stage, vit_attention_stats)"""
+    o = ops_module()
+    qkv, nB, N, scale = _vil_block_qkv(o, x, nH, prm_list)
+    if chunk is None:
+        return vit_attention_stats(o, qkv, nB, N, nH, scale, queries)
+    return vil_attention_stats(o, qkv, nB, N, nH, scale, chunk, queries)

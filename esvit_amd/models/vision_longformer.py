@@ -328,6 +328,14 @@ class MsViT(nn.Module):
     def _layers(self):
         return [l for l in (self.layer1, self.layer2, self.layer3, self.layer4) if l is not None]
 
+    def feature_grid(self, H, W):
+        """[(nglo, nx, ny)] per stage for an H x W image: the tokens of a stage are [nglo globals | an nx x ny grid, row-major]"""
+        out, nx, ny = [], int(H), int(W)
+        for cfg in self.layer_cfgs:
+            nx, ny = nx // cfg['p'], ny // cfg['p']
+            out.append((cfg['g'], nx, ny))
+        return out
+
     def forward_feature_maps(self, img):
         """-> LayerNorm-ed tokens of the last stage [nB, Nglo + nx ny, C]"""
         nB, _, H, W = img.shape

@@ -1889,3 +1889,45 @@ def sliding_chunk_attn_bwd(dout, saved, B, N, nH, scale, chunk, dqkv=None):
     check(lib.esvit_window_attn_bwd(_code(qkv.dtype), _p(qkv), None, _p(tab), N, _p(dout), _p(out), _p(lse), None, w | ATTN_SLIDING_CHUNK, _p(ws), None,
                                     nx, B, ny, nH, Cc // nH, float(scale), _p(dqkv), None, None, _stream()), "window_attn_bwd(sliding chunk)")
     return dqkv
+
+
+# ---- statistics of the sliding-chunk softmax (csrc/chunk_attn.hip): entropy of every row and a few rows of P, without P ------------
+ATTN_CHUNK_STATS = 0x02000000  # ESVIT_ATTN_CHUNK_STATS: OR'd into ws | ATTN_SLIDING_CHUNK, selects the statistics mode of esvit_window_attn_fwd
+
+
+def chunk_attn_stats_supported(dtype, hd, w, nglo):
+    """the statistics kernels exist for this shape: every shape the fused sliding-chunk forward has"""
+    return sliding_chunk_attn_supported(dtype, hd, w, nglo)
+
+
+def chunk_attn_stats(qkv, B, N, nH, scale, chunk, queries=None, ent_out=None, rows_out=None):
+    """what an attention analysis reads of the softmax sliding_chunk_attn_fwd computes, without a score tensor: qkv [B * N, 3C] (tokens
+    [globals | (x, y) row-major]) -> (entropy fp32 [B, nH, N] in nats with 0 log 0 = 0, every row over the keys it sees; rows fp32
+    [B, nH, nq, N] or None: the probability row of every listed query over all N tokens, exactly 0 where the query does not see).
+    chunk = (table, nglo, tokens per chunk row[, w]) as MsViT._stage builds it.  queries: a list or an integer tensor of token indices
+    in [0, N), the same for every image and head; duplicates allowed.  ent_out / rows_out: optional contiguous fp32 destinations of
+    those shapes."""
+    qkv = _actc(qkv)
+    tab, nglo, nx, ny, w = _chunk_grid(chunk, N)
+    Cc = qkv.shape[1] // 3
+    assert qkv.shape[0] == B * N
+    if ny >= 1 << 16:
+        raise ValueError("chunk_attn_stats: at most %d grid columns, got %d" % ((1 << 16) - 1, ny))
+    try:
+        qidx = _stats_queries(queries, N, qkv.device)
+    except ValueError as e:
+        raise ValueError(str(e).replace("global_attn_stats", "chunk_attn_stats")) from None
+    nq = 0 if qidx is None else qidx.numel()
+    if nq >= 1 << 15:
+        raise ValueError("chunk_attn_stats: at most %d listed queries, got %d" % ((1 << 15) - 1, nq))
+    ent = torch.empty((B, nH, N), dtype=torch.float32, device=qkv.device) if ent_out is None else ent_out
+    rows = None
+    if queries is not None:
+        rows = torch.empty((B, nH, nq, N), dtype=torch.float32, device=qkv.device) if rows_out is None else rows_out
+    for t, shape in ((ent, (B, nH, N)), (rows, (B, nH, nq, N))):
+        assert t is None or (t.shape == shape and t.dtype == torch.float32 and t.is_contiguous()), (shape, t.shape)
+    ws = workspace(query(Q_CHUNK_ATTN_WS, B * nH, N, 0), qkv.device, slot=3)
+    check(lib.esvit_window_attn_fwd(_code(qkv.dtype), _p(qkv), None, _p(tab), N, None, w | ATTN_SLIDING_CHUNK | ATTN_CHUNK_STATS, _p(ws), None, nx, B,
+                                    ny | (nq << 16), nH, Cc // nH, float(scale), _p(qidx) if nq else None, _p(rows) if nq else None, _p(ent), _stream()),
+          "window_attn_fwd(sliding chunk stats)")
+    return ent, rows

@@ -574,12 +574,35 @@ int esvit_attn_branch_fwd(int dtype, const float* x, const float* gamma, const f
  * Instances: every one the probability variant has -- N <= 64 at head_dim 32 / 64 in bf16 and fp32, 64 < N <= 224 at head_dim 32 in both
  * and at head_dim 64 in bf16, N < ws * ws as in the forward; anything else is ESVIT_ERR_ARG before any launch, as is the flag in
  * esvit_window_attn_bwd or together with any of the other three flags.  No atomics: two launches give identical bits.
+ *
+ * Statistics of the sliding-chunk mode (ws = 7 | ESVIT_ATTN_SLIDING_CHUNK | ESVIT_ATTN_CHUNK_STATS, esvit_window_attn_fwd only; chunk_attn.hip,
+ * DESIGN §11): the Vision Longformer counterpart of the two modes above -- for every (image, head) exactly the softmax the sliding-chunk
+ * forward computes (a local query over the globals and its 3 x 3 chunks with the forward's staging, scale and exponentials; a global
+ * query over all L keys per 512-key range) and no v, no P V, no out, no tensor that grows with L^2.  The flag is valid only together with
+ * ESVIT_ATTN_SLIDING_CHUNK: without it, in esvit_window_attn_bwd, or together with ESVIT_ATTN_GLOBAL, ESVIT_ATTN_STATS,
+ * ESVIT_ATTN_WINDOW_STATS or ESVIT_ATTN_SPLIT_DBIAS it is ESVIT_ERR_ARG before any launch.  The arguments mean:
+ *   qkv, win2tok (the chunk table), L, nW = nx, nB, nH, hd, scale: as in the sliding-chunk forward (bf16, head_dim 32 / 48 / 64, chunk
+ *                side 7, nglo = L - nx * ny <= 7);  qkv_bias, rel_table, region_ids: not used, pass NULL
+ *   N            ny | nq << 16, nq >= 0 the number of listed queries (ny < 65536: the caller refuses wider grids, nq < 32768)
+ *   bias_frag_ws fp32 scratch of esvit_query(ESVIT_Q_CHUNK_ATTN_WS, nB * nH, L, 0) floats, the forward's: that is 528 floats per
+ *                (image, head, 512-key range), of which the mode writes 24 -- (max, sum, sum e (s - max)) of the 8 global-row slots
+ *   attn_out     fp32 [nB, nH, L] (required): the entropy of every token's softmax row over the keys it sees, in nats, token order
+ *                [globals | grid row-major] as the forward's lse: H = ln l - sum_k e^(s_k - m) (s_k - m) / l, m and l the row's maximum and
+ *                sum; 0 log 0 = 0 by construction; dead neighbourhood slots and the padded MFMA columns do not enter
+ *   out          int32 [nq] on the device: the listed query tokens in [0, L), the same for every image and head; duplicates allowed.
+ *                The library cannot read the array: the caller checks the range (an index outside it is skipped, its row stays
+ *                unwritten, nothing is read or written out of bounds)
+ *   lse          fp32 [nB, nH, nq, L]: the probability row of every listed query over ALL L tokens in token order, from a normaliser
+ *                of its own; exactly 0 for every key the query does not see; every element written, by one thread
+ *   nq = 0: out and lse must be NULL.  nq > 0: both are required.
+ * No atomics: two launches give identical bits.
  */
 #define ESVIT_ATTN_SLIDING_CHUNK 0x40000000
 #define ESVIT_ATTN_GLOBAL 0x20000000
 #define ESVIT_ATTN_STATS 0x08000000
 #define ESVIT_ATTN_SPLIT_DBIAS 0x10000000
 #define ESVIT_ATTN_WINDOW_STATS 0x04000000
+#define ESVIT_ATTN_CHUNK_STATS 0x02000000
 int esvit_window_attn_fwd(int dtype, const void* qkv, const float* qkv_bias, const int32_t* win2tok, int L,
                           const float* rel_table, int ws, float* bias_frag_ws, const int32_t* region_ids, int nW, int nB,
                           int N, int nH, int hd, float scale, void* out, float* lse, float* attn_out,
